@@ -26,6 +26,8 @@ shape (1024x1024, batch 4) with the fp8 attention path, and the precise mode (`-
 OUTPUT (round 6: the round-5 line had grown to 21 KB and the driver could no longer parse it). Rank 0 prints
   * one `LEG {json}` line per leg as it completes (the full record of that leg), and writes headline + legs in full to
     `bench_legs.json` beside this file;
+  * with `--dump-outputs DIR`, what the headline's last timed step returned (the edited packed latents) as DIR/images.npy
+    (float32, at most 64 MB; the inputs are seeded, so two builds of the project compare output for output);
   * as the LAST stdout line ONE JSON object of at most 6 KB (`compact_line`; tests/test_host_cpu.py bounds it): the contract
     fields, `config`, `roofline` (dominant kernel, live HIP events; `traffic` from the committed PMC passes), `roofline_attention`,
     `cpu_baseline` (the oracle on this box's host cores, bounded sample), `parity` (the engine against the fp32 oracle on
@@ -457,10 +459,34 @@ def latent_hash(t) -> str:
     return hashlib.sha256(t.detach().float().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
 
 
-def run_leg(pw, dev, rank, world, *, B, hw, allmod, mc, precise, steps, warmup, events=True, seed=1234, seed_rank=None, want_hash=False):
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files of one run together
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: write each array as <out_dir>/<name>.npy in float32 (ranks > 1: <name>_rank<r>.npy). An array larger than
+    its share of DUMP_LIMIT_BYTES is replaced by a fixed sample of its flattened elements: the indices depend only on the array's
+    size (seed 0), so two builds that computed the same shape are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_LIMIT_BYTES // 4 // max(1, world) // max(1, len(arrays))       # float32 elements per file
+    written = {}
+    for name, t in arrays.items():
+        x = t.detach().float().cpu()
+        if x.numel() > cap:
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            x = x.reshape(-1)[idx]
+        fn = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(out_dir, fn + ".npy"), x.contiguous().numpy())
+        written[fn] = list(x.shape)
+    return written
+
+
+def run_leg(pw, dev, rank, world, *, B, hw, allmod, mc, precise, steps, warmup, events=True, seed=1234, seed_rank=None, want_hash=False,
+            dump_dir=None):
     """Warm-up + timed region of one workload on this rank; returns the measurement record (rank 0) or None.
     seed_rank: whose images this process edits (default: its own rank; --emulate-ranks replays another rank's seed on one GPU).
-    want_hash: the record carries `latent_sha16` = one hash per rank of the LAST timed batch's edited latents (gathered to rank 0)."""
+    want_hash: the record carries `latent_sha16` = one hash per rank of the LAST timed batch's edited latents (gathered to rank 0).
+    dump_dir: every rank writes the LAST timed batch's edited latents (what generate() returned) there (dump_outputs)."""
     from loongx_amd import _lib
     from loongx_amd import dist as lxd
     from loongx_amd import ops
@@ -524,6 +550,8 @@ def run_leg(pw, dev, rank, world, *, B, hw, allmod, mc, precise, steps, warmup, 
     elapsed_ms = lxd.barrier_max_ms(elapsed_ms, dev)
     model.transformer.engine.check_status(sync=True)              # a split-K pair time-out would invalidate the region
     finite = bool(torch.isfinite(out).all())
+    if dump_dir:
+        dump_outputs(dump_dir, {"images": out}, rank, world)
     f16_sat = model.transformer.engine.f16_overflow_count() if model.transformer.engine.f16 else None
     hashes = None
     if want_hash:
@@ -645,8 +673,13 @@ def main():
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="N = 1 only: run the workload of each of R ranks (rank r's seed) one after the other on this GPU and report their latent "
                          "hashes (config.latent_sha16) -- what an R-rank run must reproduce bit for bit; the timing fields describe rank 0's replay")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (the edited packed latents) as DIR/images.npy "
+                         "(float32; DIR/images_rank<r>.npy per rank when N > 1); inputs are seeded, so two builds compare output for output")
     ap.add_argument("--dry-run", action="store_true", help="print the per-rank plan of this invocation as one JSON line and exit: no GPU, no process group")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.tiny:
         global D, STEPS, ROOFLINE_STEPS, LAYERS
         D, STEPS, ROOFLINE_STEPS, LAYERS = 256, 4, (1, 2), 4
@@ -707,7 +740,7 @@ def main():
 
     want_hash = a.hash_latents or a.emulate_ranks > 0
     rec = run_leg(pw, dev, rank, world, B=B, hw=hw, allmod=allmod, mc=mc, precise=a.precise, steps=a.steps, warmup=a.warmup,
-                  events=not a.no_roofline_events, want_hash=want_hash)
+                  events=not a.no_roofline_events, want_hash=want_hash, dump_dir=a.dump_outputs)
     if a.emulate_ranks > 1 and world == 1:
         for r_ in range(1, a.emulate_ranks):
             rr = run_leg(pw, dev, 0, 1, B=B, hw=hw, allmod=allmod, mc=mc, precise=a.precise, steps=a.steps, warmup=a.warmup, events=False,

@@ -249,3 +249,24 @@ def test_bench_line_is_bounded():
     # a tolerance that is NOT held shows: the fp8-attention figures judged as the bf16 mode
     bad = bench.stamp_tolerance(dict(sec[4]["parity"]["512x512"]), {})
     assert bad["tolerance_ok"] is False
+
+
+def test_bench_dump_outputs_float32_bounded_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): an array within the budget is written whole, in float32, with its shape; a larger one is
+    replaced by a sample whose indices depend only on its size, so two runs (two builds) write the same elements of the same output."""
+    import numpy as np
+    import bench
+    small = torch.randn(2, 16, 64, dtype=torch.bfloat16)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"images": small}) == {"images": [2, 16, 64]}
+    got = np.load(tmp_path / "a" / "images.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 1000)
+    big = torch.arange(5000, dtype=torch.float64).reshape(50, 100)
+    bench.dump_outputs(str(tmp_path / "b"), {"images": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"images": big + 0.5})
+    b, c = np.load(tmp_path / "b" / "images.npy"), np.load(tmp_path / "c" / "images.npy")
+    assert b.dtype == np.float32 and b.shape == (1000,) and b.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert len(np.unique(b)) == 1000 and np.all(np.diff(b) > 0) and np.array_equal(c, b + 0.5)
+    # two ranks share the budget and write one file each
+    assert bench.dump_outputs(str(tmp_path / "d"), {"images": big}, rank=1, world=2) == {"images_rank1": [500]}
+    assert os.listdir(tmp_path / "d") == ["images_rank1.npy"]

@@ -1,5 +1,5 @@
-"""N > 1 on hardware: `python bench.py --gpus 2` starting its own two RCCL ranks (skipped on a one-GPU box: the gpurun boxes have
-one; the driver's scaling run is the first multi-GPU execution) -- and a REHEARSAL of the same control flow that does run on one GPU:
+"""N > 1 on hardware: `python bench.py --gpus 2` starting its own two RCCL ranks (on a one-GPU box: that the same command refuses;
+the driver's scaling run is the first multi-GPU execution) -- and a REHEARSAL of the same control flow that does run on one GPU:
 two ranks sharing device 0 over gloo (LX_DIST_ONE_DEVICE=1, LX_DIST_BACKEND=gloo; RCCL refuses two ranks on one device): self-launch
 under torch.distributed.run, rank 0 draws the weights, rank 1 allocates and receives all 23.85 GB, barrier-bracketed timed region,
 max-over-ranks, one JSON line."""
@@ -14,12 +14,27 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# Ranks that time-share one GPU cannot count on the partner workgroups of lx_gemm4_kernel's split form being resident together: the
+# bounded wait times out and the step is reported invalid (lx_gemm_workspace_status). The one-device rehearsals run without the split
+# form (LX_GEMM4_SK=0); with one process per GPU the default plan stands.
+NO_SPLIT_K = dict(LX_GEMM4_SK="0")
 
 
 def test_bench_two_ranks_over_rccl():
-    if not torch.cuda.is_available() or torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs")
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    """`bench.py --gpus 2` over RCCL, one rank per GPU. On a box with one GPU (RCCL refuses two ranks on one device) the same command
+    must refuse: rank 1 cannot select device 1, the run exits non-zero without a result line -- no silent fall-back to one rank, to
+    device 0 for both, or to gloo."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                           "LX_DIST_ONE_DEVICE", "LX_DIST_BACKEND")}
+    if torch.cuda.device_count() < 2:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode != 0, r.stdout[-2000:]
+        assert not [l for l in r.stdout.splitlines() if l.startswith("{")], r.stdout[-2000:]
+        assert "invalid device ordinal" in r.stderr.lower(), r.stderr[-3000:]
+        return
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -32,7 +47,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(LX_DIST_ONE_DEVICE="1", LX_DIST_BACKEND="gloo")
+    env.update(LX_DIST_ONE_DEVICE="1", LX_DIST_BACKEND="gloo", **NO_SPLIT_K)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -45,31 +60,37 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     assert 0.5 < line["value"] < 1.3, line["value"]
 
 
-def test_bench_eight_ranks_rehearsal_tiny_shapes_bit_equal_to_single_rank():
-    """The driver's 8-GPU scaling run must not be the first execution of the 8-rank path. `bench.py --gpus 8 --tiny` on ONE GPU (eight
-    ranks on device 0 over gloo): self-launch under torch.distributed.run, rank 0 draws the weights and the other seven receive them by
-    bucketed broadcast, shard by rank (every rank its own seed), barrier-bracketed timed region, max-over-ranks, all_gather of the per-rank
-    results, one bounded JSON line with n_gpus / scaling / rccl_ranks. Every rank's edited latents are BIT-equal to what one process
-    computes for that rank's seed (`--emulate-ranks 8`): data parallelism changes who computes an image, not the image.
-    The full-size run of the same command is profiles/r06_rehearsal8_line.json (23.85 GB broadcast in 1 GiB buckets)."""
+REHEARSAL_RANKS = 4     # ranks on the one device; with the pytest process that is 5 processes holding the GPU (a shared box allows 6)
+
+
+def test_bench_four_ranks_rehearsal_tiny_shapes_bit_equal_to_single_rank():
+    """The driver's 8-GPU scaling run must not be the first execution of the multi-rank path. `bench.py --gpus 4 --tiny` on ONE GPU
+    (four ranks on device 0 over gloo; eight would put nine processes on a GPU that allows six): self-launch under
+    torch.distributed.run, rank 0 draws the weights and the other ranks receive them by bucketed broadcast, shard by rank (every rank
+    its own seed), barrier-bracketed timed region, max-over-ranks, all_gather of the per-rank results, one bounded JSON line with
+    n_gpus / scaling / rccl_ranks. Every rank's edited latents are BIT-equal to what one process computes for that rank's seed
+    (`--emulate-ranks 4`): data parallelism changes who computes an image, not the image.
+    The full-size 8-rank run of the same command is profiles/r06_rehearsal8_line.json (23.85 GB broadcast in 1 GiB buckets)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    n = REHEARSAL_RANKS
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(NO_SPLIT_K)                                               # (the single-process run too: the same GEMM plan on both sides)
     common = ["--tiny", "--steps", "1", "--warmup", "1", "--hash-latents", "--no-roofline-events"]
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--emulate-ranks", "8"] + common,
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--emulate-ranks", str(n)] + common,
                          capture_output=True, text=True, env=env, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     single = json.loads(one.stdout.splitlines()[-1])
     want = single["config"]["latent_sha16"]
-    assert len(want) == 8 and len(set(want)) == 8                       # eight different images
+    assert len(want) == n and len(set(want)) == n                       # n different images
     env.update(LX_DIST_ONE_DEVICE="1", LX_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + common, capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + common, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.splitlines()[-1]
     assert len(last) < 6144
     line = json.loads(last)
-    assert line["n_gpus"] == 8 and line["scaling"] == "weak" and line["config"]["rccl_ranks"] == 8 and line["config"]["global_batch"] == 8
-    assert line["config"]["parallelism"] == "dp8" and line["config"]["weight_broadcast_GB"] > 0 and line["outputs_finite"] and line["value"] > 0
+    assert line["n_gpus"] == n and line["scaling"] == "weak" and line["config"]["rccl_ranks"] == n and line["config"]["global_batch"] == n
+    assert line["config"]["parallelism"] == f"dp{n}" and line["config"]["weight_broadcast_GB"] > 0 and line["outputs_finite"] and line["value"] > 0
     assert "not the metric" in line["metric"] and "--tiny" in line["config"]["workload"]
     assert line["config"]["latent_sha16"] == want, (line["config"]["latent_sha16"], want)
 
