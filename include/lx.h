@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 /* ABI history:
+ *  0.4.4  + lx_gemm_last_plan (which launch plan lx_gemm_bf16 / lx_gemm_bf16_ws chose)
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -40,7 +41,7 @@ extern "C" {
  *  0.3.0  lx_gemm_desc grew (LX_EPI_QKV e4m3 outputs: qkv_q8 ... qkv_v_scale, appended); + lx_qkv_prep_split_segs, lx_attn_fwd_split,
  *         lx_lora_down_terms
  *  0.2.0  caller-owned GEMM workspace, precise mode, VAE row kernels, channel-major fp32 GEMM */
-#define LX_VERSION 403
+#define LX_VERSION 404
 
 typedef enum lx_status {
   LX_OK = 0,
@@ -186,6 +187,17 @@ void lx_gemm_reload_env(void);
 size_t lx_gemm_workspace_bytes(void);
 int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* workspace, size_t ws_bytes, void* stream);
 int lx_gemm_workspace_status(void* workspace, void* stream);
+/* Which launch plan the calling thread's last successful lx_gemm_bf16 / lx_gemm_bf16_ws chose (a planner decision, exposed for benchmarks
+ * and tests; the operand format follows from the descriptors and is not encoded):
+ * LX_GEMM_PLAN_8WAVE_256 / _128: the 8-wave kernels, all tiles 256 / 128 rows high;
+ * LX_GEMM_PLAN_MIXED: full rounds of 256-row tiles + a 128-row-tile tail in one grid (lx_gemm_mixed_kernel);
+ * LX_GEMM_PLAN_MIXED_2L: the mixed plan as two launches (one of the two parts was empty);
+ * LX_GEMM_PLAN_G4: lx_gemm4_kernel (one wave per SIMD), whole tiles only;
+ * LX_GEMM_PLAN_G4_SPLIT2 / _SPLIT3: lx_gemm4_kernel with its split form (a partial last round, or every tile of a long-K launch, shared
+ *   by two / three workgroups). */
+enum { LX_GEMM_PLAN_NONE = 0, LX_GEMM_PLAN_8WAVE_256 = 1, LX_GEMM_PLAN_8WAVE_128 = 2, LX_GEMM_PLAN_MIXED = 3, LX_GEMM_PLAN_MIXED_2L = 4,
+       LX_GEMM_PLAN_G4 = 5, LX_GEMM_PLAN_G4_SPLIT2 = 6, LX_GEMM_PLAN_G4_SPLIT3 = 7 };
+int lx_gemm_last_plan(void);
 
 /* LoRA down-projection (peft lora_A): T_s[M, R] (fp32, ldt) = X[M, K_s] (bf16, ldx) . Adown[R, K_s]^T (bf16), R <= 16,
  * for n_split contiguous K slices s (n_split = 1: the whole K); slab s is written at T + s*split_stride. Splitting K

@@ -19,6 +19,9 @@ LIB_PATH = os.environ.get("LX_AMD_LIB", os.path.join(_HERE, "lib", "liblx_amd.so
 LX_EPI_STORE_BF16, LX_EPI_STORE_F32, LX_EPI_RESID_F32, LX_EPI_GELU, LX_W_TILED, LX_EPI_SPLIT_BF16 = 0, 1, 2, 0x100, 0x200, 0x400
 LX_EPI_STORE_FP8, LX_OPERANDS_FP8, LX_EPI_QKV, LX_OPERANDS_F16 = 3, 0x800, 0x1000, 0x2000
 LX_GEMM_MAX_GROUP = 4
+# lx_gemm_last_plan() values (include/lx.h)
+(LX_GEMM_PLAN_NONE, LX_GEMM_PLAN_8WAVE_256, LX_GEMM_PLAN_8WAVE_128, LX_GEMM_PLAN_MIXED, LX_GEMM_PLAN_MIXED_2L, LX_GEMM_PLAN_G4,
+ LX_GEMM_PLAN_G4_SPLIT2, LX_GEMM_PLAN_G4_SPLIT3) = range(8)
 
 
 class GemmDesc(C.Structure):
@@ -80,6 +83,7 @@ _SIGS = {
     "lx_gemm_workspace_bytes": (_Z, []),
     "lx_gemm_bf16_ws": (C.c_int, [C.POINTER(GemmDesc), _I, _P, _Z, _P]),
     "lx_gemm_workspace_status": (C.c_int, [_P, _P]),
+    "lx_gemm_last_plan": (C.c_int, []),
     "lx_lora_down": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lx_lora_down_f16": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lx_lora_down_terms": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p), _I, _P, _I, _I, _I, _I, _I, _P]),

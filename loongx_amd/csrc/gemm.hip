@@ -91,6 +91,14 @@ static void plan_add(GemmArgs& a, const lx_gemm_desc& p, int m_base, int bm) {
   for (int i = a.n + 1; i <= MAX_SUB; ++i) a.tile_start[i] = a.tile_start[a.n];
 }
 
+// the plan of the calling thread's last successful launch (lx_gemm_last_plan: tests and benchmarks see what the planner chose)
+static thread_local int lx_gemm_last = LX_GEMM_PLAN_NONE;
+extern "C" int lx_gemm_last_plan(void) { return lx_gemm_last; }
+static int planned(int rc, int plan) {
+  if (rc == LX_OK) lx_gemm_last = plan;
+  return rc;
+}
+
 extern "C" size_t lx_gemm_workspace_bytes(void) { return SK_WS_BYTES; }
 
 extern "C" int lx_gemm_workspace_status(void* workspace, void* stream) {
@@ -189,7 +197,7 @@ extern "C" int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* worksp
     all.tile_start[0] = 0;
     for (int i = 1; i <= MAX_SUB; ++i) all.tile_start[i] = 0;
     for (int i = 0; i < n; ++i) plan_add(all, problems[i], 0, bm);
-    return launch_plan(all, bm, s, LX_GV_FP8);
+    return planned(launch_plan(all, bm, s, LX_GV_FP8), bm == 256 ? LX_GEMM_PLAN_8WAVE_256 : LX_GEMM_PLAN_8WAVE_128);
   }
   const int NCU = device_cus() > 0 ? device_cus() : 256;   // one workgroup per CU: a launch runs in rounds of NCU tiles
   const GemmEnv& env = gemm_env();
@@ -267,7 +275,8 @@ extern "C" int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* worksp
       else if (f16) lx_gemm4_launch_f16(all, grid, sk_full, sk_parts, slots, flags, err, s, np);
       else lx_gemm4_launch_bf16(all, grid, sk_full, sk_parts, slots, flags, err, s, np);
       LX_LAUNCH_CHECK("lx_gemm_bf16");
-      return LX_OK;
+      // (the split-bf16 kernel has the two-way form only: np stays 2 there)
+      return planned(LX_OK, !(split_all || split_tail) ? LX_GEMM_PLAN_G4 : np == 3 ? LX_GEMM_PLAN_G4_SPLIT3 : LX_GEMM_PLAN_G4_SPLIT2);
     }
   }
   if (split) {   // precise mode on the 8-wave kernels: all 256-row tiles or all 128-row tiles (no mixed / pair plans)
@@ -278,7 +287,7 @@ extern "C" int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* worksp
     all.tile_start[0] = 0;
     for (int i = 1; i <= MAX_SUB; ++i) all.tile_start[i] = 0;
     for (int i = 0; i < n; ++i) plan_add(all, problems[i], 0, bm);
-    return launch_plan(all, bm, s, LX_GV_SPLIT);
+    return planned(launch_plan(all, bm, s, LX_GV_SPLIT), bm == 256 ? LX_GEMM_PLAN_8WAVE_256 : LX_GEMM_PLAN_8WAVE_128);
   }
   if (workspace) LX_CHECK_ARG(ws_bytes >= SK_WS_BYTES && ((uintptr_t)workspace & 255) == 0, "lx_gemm_bf16_ws: workspace needs %zu bytes (lx_gemm_workspace_bytes()), 256-byte aligned", SK_WS_BYTES);
   const int variant = f16 ? LX_GV_F16 : LX_GV_BF16;
@@ -322,17 +331,17 @@ extern "C" int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* worksp
       if (f16) lx_gemm8_mixed_launch_f16(big, tail, n_big_pad, s);
       else lx_gemm8_mixed_launch_bf16(big, tail, n_big_pad, s);
       LX_LAUNCH_CHECK("lx_gemm_bf16");
-      return LX_OK;
+      return planned(LX_OK, LX_GEMM_PLAN_MIXED);
     }
     const int rc = launch_plan(big, 256, s, variant);
     if (rc != LX_OK) return rc;
-    return launch_plan(tail, 128, s, variant);
+    return planned(launch_plan(tail, 128, s, variant), LX_GEMM_PLAN_MIXED_2L);
   }
   GemmArgs all;
   all.n = 0;
   all.tile_start[0] = 0;
   for (int i = 1; i <= MAX_SUB; ++i) all.tile_start[i] = 0;
   for (int i = 0; i < n; ++i) plan_add(all, problems[i], 0, choice == 0 ? 256 : 128);
-  return launch_plan(all, choice == 0 ? 256 : 128, s, variant);
+  return planned(launch_plan(all, choice == 0 ? 256 : 128, s, variant), choice == 0 ? LX_GEMM_PLAN_8WAVE_256 : LX_GEMM_PLAN_8WAVE_128);
 }
 

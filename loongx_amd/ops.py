@@ -213,6 +213,11 @@ def gemm(problems: Sequence[GemmDesc], workspace: Optional[torch.Tensor] = None)
     call()
 
 
+def gemm_last_plan() -> int:
+    """The launch plan of this thread's last successful gemm() (an LX_GEMM_PLAN_* value, include/lx.h)."""
+    return lib.lx_gemm_last_plan()
+
+
 def lora_down(X: torch.Tensor, Adown: torch.Tensor, T: torch.Tensor, n_split: int = 1, split_stride: int = 0) -> None:
     """T (slab 0) [M,R] fp32; with n_split > 1 slab s lives split_stride floats further (same row stride).
     X and Adown both bf16, or both fp16 (the operand images of the fp16-operand mode: lx_lora_down_f16)."""

@@ -12,7 +12,8 @@ def _declared():
     return sorted(set(re.findall(r"\b(lx_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_of_abi_404():
+    """(ABI 0.4.4: + lx_gemm_last_plan. The pinned version moves with every ABI change, so this test carries the version in its name.)"""
     import __graft_entry__ as g
     g.build()
     from loongx_amd import _lib
@@ -21,7 +22,9 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(_lib.lib, n), f"{n} declared in include/lx.h but not exported by liblx_amd.so"
     assert set(names) == set(_lib.EXPORTS), set(names) ^ set(_lib.EXPORTS)
-    assert _lib.lib.lx_version() == 403
+    assert _lib.lib.lx_version() == 404
+    hdr = re.search(r"#define LX_VERSION (\d+)", open(os.path.join(ROOT, "include", "lx.h")).read())
+    assert hdr and int(hdr.group(1)) == _lib.lib.lx_version(), "liblx_amd.so was built from another include/lx.h"
 
 
 def test_struct_layouts_match_header():

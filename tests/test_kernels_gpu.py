@@ -83,6 +83,12 @@ def _plan(monkeypatch, bm):
     return None
 
 
+def _assert_plan(ops, want):
+    from loongx_amd import _lib
+    got = ops.gemm_last_plan()
+    assert got == getattr(_lib, "LX_GEMM_PLAN_" + want), f"the planner chose plan {got}, not {want}"
+
+
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("bm", PLANS)
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 512, 128), (1000, 768, 256), (2560, 3072, 3072)])
@@ -94,6 +100,8 @@ def test_gemm_store_bf16_bias(ops, M, N, K, bm, fmt, monkeypatch):
     Cc = torch.full((M, N), float("nan"), dtype=out16(fmt), device=DEV)
     ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
     ops.gemm([ops.gemm_desc(A, W, Cc, bias=bias, **fkw(fmt, ovf))], ws)
+    # (LX_GEMM4=2 needs two K tiles: with K = 64 the planner keeps the launch on the 8-wave kernels -- one 256 x 256 tile: 128-row tiles by cost)
+    _assert_plan(ops, {256: "8WAVE_256", 128: "8WAVE_128"}.get(bm, "G4" if K >= 128 else "8WAVE_128"))
     ref = A.float() @ W.float().T + bias
     assert relerr(Cc.float().cpu(), ref.cpu()) < STORE_TOL[fmt]
     assert torch.isfinite(Cc.float()).all() and int(ovf) == 0
@@ -251,6 +259,8 @@ def test_gemm4_one_wave_per_simd_kernel(ops, monkeypatch, sk, fmt):
         ops.gemm([ops.gemm_desc(A1, Wt, X, bias=bias, epilogue=ops.LX_EPI_RESID_F32, gate=gate, rows_per_batch=256, lora_t=Tl[0, :, :r], lora_up=Bu,
                                 lora_nsplit=2, lora_split_stride=Tl.stride(0), **fkw(fmt)),
                   ops.gemm_desc(A2, Wt, C2, bias=bias, epilogue=ops.LX_EPI_STORE_BF16 | ops.LX_EPI_GELU, **fkw(fmt))], ws)
+        # (sk = 1: the 24-tile tail is at most a sixth of a round with 32 K tiles -- the three-way form)
+        _assert_plan(ops, "G4_SPLIT3" if sk else "G4")
         return X, C2
     X, C2 = run()
     t = A1.float() @ Ad.float().T
@@ -278,6 +288,7 @@ def test_gemm4_split_form_with_a_ragged_tile_row(ops):
     def run():
         X = X0.clone()
         ops.gemm([ops.gemm_desc(A, W, X, bias=bias, epilogue=ops.LX_EPI_RESID_F32, gate=gate, rows_per_batch=800)], ws)
+        _assert_plan(ops, "G4_SPLIT3")          # (60 tiles x 3 workgroups fit one round, 96 K tiles)
         return X
     X = run()
     ref = X0 + gate.repeat_interleave(800, 0) * (A.float() @ Wr.float().T + bias)
@@ -352,6 +363,7 @@ def test_gemm_three_way_split_form(ops, monkeypatch, fmt):
             ops.lib.lx_gemm_reload_env()
         X.copy_(X0)
         ops.gemm([d], None if mode == "none" else ws)
+        _assert_plan(ops, {"none": "8WAVE_128", "three": "G4_SPLIT3", "two": "G4_SPLIT2"}[mode])
         torch.cuda.synchronize()
         out[mode] = X.clone()
     monkeypatch.delenv("LX_GEMM4_SK")
@@ -383,6 +395,7 @@ def test_gemm_three_way_split_form(ops, monkeypatch, fmt):
     for mode in ("none", "three"):
         c = torch.empty(2560, N2, dtype=torch.float16 if fmt == "f16" else torch.bfloat16, device=DEV)
         ops.gemm([ops.gemm_desc(A2, W2, c, bias=b2, epilogue=ops.LX_EPI_STORE_BF16 | ops.LX_EPI_GELU, **fkw(fmt))], None if mode == "none" else ws)
+        _assert_plan(ops, "MIXED" if mode == "none" else "G4_SPLIT3")
         torch.cuda.synchronize()
         C[mode] = c.float().cpu()
     want = torch.nn.functional.gelu(A2.float() @ W2.float().T + b2, approximate="tanh").cpu()
@@ -444,6 +457,7 @@ def test_gemm_split_form_long_k(ops, monkeypatch, fmt):
     for mode in ("0", "2"):
         X.copy_(X0)
         ops.gemm([d], ws if mode == "2" else None)          # the split form runs iff a workspace is given
+        _assert_plan(ops, "G4_SPLIT2" if mode == "2" else "8WAVE_128")      # (120 tiles: 3 x 120 workgroups would not fit one round)
         torch.cuda.synchronize()
         out[mode] = X.clone()
     ops.gemm_workspace_status(ws)                            # no split workgroup timed out
@@ -498,6 +512,7 @@ def test_gemm_planner_mixed_tail(ops, monkeypatch, fmt):
     ops.lora_down(A[M1:], Ad, Tl)
     ops.gemm([ops.gemm_desc(A[:M1], W, X[:M1], bias=bias, epilogue=ops.LX_EPI_RESID_F32, gate=g1, rows_per_batch=512, **fkw(fmt)),
               ops.gemm_desc(A[M1:], W, X[M1:], bias=bias, epilogue=ops.LX_EPI_RESID_F32, gate=g2, rows_per_batch=256, lora_t=Tl, lora_up=Bu, **fkw(fmt))])
+    _assert_plan(ops, "MIXED")
     y = A.float() @ W.float().T + bias
     y[M1:] += (A[M1:].float() @ Ad.float().T) @ Bu.T
     ref = X0 + y * torch.cat([g1.repeat_interleave(512, 0), g2.repeat_interleave(256, 0)])

@@ -75,6 +75,20 @@ def gemm_plan(monkeypatch):
     _lib.lib.lx_gemm_reload_env()
 
 
+def _expected_plan(plan, probs, K, segs):
+    """The plan the gemm_plan setting must give a launch of these (M, N) problems: lx_gemm4_kernel needs two K tiles, its split form
+    (LX_GEMM4_SK = 1) 16 K tiles over all segments; the 8-wave split kernels take 256- or 128-row tiles by the planner's cost model."""
+    from loongx_amd import _lib
+    kt = K * segs // 64
+    if plan == "w8" or K < 128:
+        n = torch.cuda.get_device_properties(0).multi_processor_count
+        t256 = sum(-(-M // 256) * -(-N // 256) for M, N in probs)
+        t128 = sum(-(-M // 128) * -(-N // 256) for M, N in probs)
+        ca, cb = -(-t256 // n) * (15.0 + 1.81 * kt), -(-t128 // n) * (10.5 + 1.06 * kt)
+        return _lib.LX_GEMM_PLAN_8WAVE_128 if cb < ca else _lib.LX_GEMM_PLAN_8WAVE_256
+    return _lib.LX_GEMM_PLAN_G4_SPLIT2 if plan == "g4sk" and kt >= 16 else _lib.LX_GEMM_PLAN_G4
+
+
 @pytest.mark.parametrize("plan", ["w8", "g4", "g4sk"])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 512, 192), (2560, 768, 3072), (2304, 7680, 1024)])
 @pytest.mark.parametrize("segs", [2, 3])
@@ -98,11 +112,13 @@ def test_gemm_split_bf16(ops, M, N, K, segs, plan, gemm_plan):
         Wt = ops.tile_weight(Wd) if tiled else Wd
         C32 = torch.full((M, N), float("nan"), dtype=torch.float32, device=DEV)
         ops.gemm([ops.gemm_desc(A2, Wt, C32, bias=bias, epilogue=ops.LX_EPI_STORE_F32, K=K, N=N, k_segs=segs, a_lo_off=K + 64)], ws)
+        assert ops.gemm_last_plan() == _expected_plan(plan, [(M, N)], K, segs), ops.gemm_last_plan()
         assert relerr(C32, ref) < 3e-5, (segs, tiled)
     # hi/lo output pair with GELU
     Cp = torch.zeros(M, 2 * N + 64, dtype=torch.bfloat16, device=DEV)
     ops.gemm([ops.gemm_desc(A2, Wd, Cp, bias=bias, epilogue=ops.LX_EPI_STORE_BF16 | ops.LX_EPI_GELU, K=K, N=N, k_segs=segs,
                             a_lo_off=K + 64, c_lo_off=N + 64)], ws)
+    assert ops.gemm_last_plan() == _expected_plan(plan, [(M, N)], K, segs), ops.gemm_last_plan()
     want = torch.nn.functional.gelu(ref.double(), approximate="tanh").float()
     got = Cp[:, :N].float() + Cp[:, N + 64:2 * N + 64].float()
     assert relerr(got, want) < 5e-5
@@ -151,6 +167,7 @@ def test_gemm_split_bf16_lora_gate_residual(ops, plan, gemm_plan):
         outs.append(C)
         keep.append((A2, Wd, bias, gate, kw))          # (a descriptor holds raw pointers: the operands must outlive the launch)
     ops.gemm(probs, ws)
+    assert ops.gemm_last_plan() == _expected_plan(plan, [(M, N), (M, N)], K, 3), ops.gemm_last_plan()
     got = [o for o in outs if o.shape == (M, N)]
     for g, want in zip(got, ref_all):
         assert relerr(g, want) < 3e-5
