@@ -15,25 +15,28 @@ draws the weights and broadcasts them over RCCL/xGMI before the timed region.  P
 `python -m torch.distributed.run`, as the reference's inference.py:432-452 spawns its own workers).
 
 `--config {1,2,3,4}` sets batch / resolution / modalities / fp8-attention from BASELINE.json's configs (per-GPU batch = the
-config's global batch / N), e.g. `bench.py --gpus 8 --config 3` is the literal configs[3] run. With N = 1 and no explicit
-workload flags the run also measures short bounded LEGS outside the headline's timed region on this GPU -- the headline workload
-with fp16 GEMM operand images (`fp16_operands`: the north star's 1e-3 per forward) and on weights with a trained checkpoint's
-statistics (`realistic_stats`), then the other BASELINE configs: configs[2] (batch 16, all four modalities), configs[4]'s per-GPU
-shape (1024x1024, batch 4) with the fp8 attention path, and the precise mode (`--all-legs` adds the bf16 reference line of the
-1024x1024 shape and the 1024x1024 parity trajectory) -- each with its own roofline, power and full-depth parity figures;
-`--no-secondary` skips them.
+config's global batch / N), e.g. `bench.py --gpus 8 --config 3` is the literal configs[3] run.
+
+A run without `--full` does only what the headline needs: set-up, warm-up, the timed steps (whose last one carries the roofline's
+HIP events), `--dump-outputs` if given, the result line. `--full` (N = 1) adds what runs outside the timed region: `cpu_baseline`,
+the full-depth `parity` of the headline's mode and, with no explicit workload flags, short bounded LEGS on this GPU -- the headline
+workload with fp16 GEMM operand images (`fp16_operands`: the north star's 1e-3 per forward) and on weights with a trained
+checkpoint's statistics (`realistic_stats`), then the other BASELINE configs: configs[2] (batch 16, all four modalities), configs[4]'s
+per-GPU shape (1024x1024, batch 4) with the fp8 attention path, and the precise mode (`--all-legs` adds the bf16 reference line of
+the 1024x1024 shape and the 1024x1024 parity trajectory) -- each with its own roofline, power and full-depth parity figures;
+`--no-cpu-baseline`, `--no-parity` and `--no-secondary` leave out the parts of `--full` they name.
 
 OUTPUT (round 6: the round-5 line had grown to 21 KB and the driver could no longer parse it). Rank 0 prints
-  * one `LEG {json}` line per leg as it completes (the full record of that leg), and writes headline + legs in full to
-    `bench_legs.json` beside this file;
+  * with `--full`, one `LEG {json}` line per leg as it completes (the full record of that leg), and writes headline + legs in full
+    to `bench_legs.json` beside this file;
   * with `--dump-outputs DIR`, what the headline's last timed step returned (the edited packed latents) as DIR/images.npy
     (float32, at most 64 MB; the inputs are seeded, so two builds of the project compare output for output);
   * as the LAST stdout line ONE JSON object of at most 6 KB (`compact_line`; tests/test_host_cpu.py bounds it): the contract
     fields, `config`, `roofline` (dominant kernel, live HIP events; `traffic` from the committed PMC passes), `roofline_attention`,
+    `power`, `summary` (the headline and every leg: value, roofline fractions, parity, tolerance_ok) and, with `--full`,
     `cpu_baseline` (the oracle on this box's host cores, bounded sample), `parity` (the engine against the fp32 oracle on
-    identical inputs at FULL depth -- 57 blocks x 28 steps; N = 1 only; `tolerance_ok` against loongx_amd/tolerances.py), `power`,
-    `value_fp16_operands` + `parity_fp16_operands` (the 1e-3 mode beside the headline) and `summary` (every leg: value, roofline
-    fractions, parity, tolerance_ok).
+    identical inputs at FULL depth -- 57 blocks x 28 steps; N = 1 only; `tolerance_ok` against loongx_amd/tolerances.py) and
+    `value_fp16_operands` + `parity_fp16_operands` (the 1e-3 mode beside the headline).
 """
 import argparse
 import json
@@ -427,18 +430,20 @@ def compact_line(res, legs):
     for n, r in legs:
         summ[n] = _brief(r)
     out["summary"] = summ
-    out["legs_file"] = "bench_legs.json (+ one `LEG {json}` stdout line per leg)"
+    if legs:
+        out["legs_file"] = "bench_legs.json (+ one `LEG {json}` stdout line per leg)"
     return out
 
 
-def emit(res, legs, stream=None):
-    """LEG lines were printed as the legs completed; here: the sidecar file and the final bounded line."""
+def emit(res, legs, stream=None, sidecar=True):
+    """LEG lines were printed as the legs completed; here: the sidecar file (`sidecar`: --full runs) and the final bounded line."""
     stream = stream or sys.stdout
-    try:
-        with open(os.path.join(ROOT, "bench_legs.json"), "w") as f:
-            json.dump({"headline": res, "legs": dict(legs)}, f, indent=1)
-    except OSError:
-        pass
+    if sidecar:
+        try:
+            with open(os.path.join(ROOT, "bench_legs.json"), "w") as f:
+                json.dump({"headline": res, "legs": dict(legs)}, f, indent=1)
+        except OSError:
+            pass
     line = json.dumps(compact_line(res, legs))
     if len(line) > LINE_LIMIT:          # never again an unparseable line: shed the explanatory parts, then the per-leg parity detail
         c = compact_line(res, legs)
@@ -648,12 +653,15 @@ def main():
     ap.add_argument("--config", type=int, default=None, choices=(1, 2, 3, 4),
                     help="BASELINE.json configs[n]: sets batch (global batch / --gpus), resolution, modalities and the fp8 attention path")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline also measure cpu_baseline, the full-depth parity and (no explicit workload flags) the "
+                         "secondary legs, and write bench_legs.json; default: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--no-roofline-events", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the full-depth parity legs (N=1 only)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (the other BASELINE configs; N=1 default run only)")
-    ap.add_argument("--secondary-steps", type=int, default=2, help="timed batches per batch-1 leg (the batch-16 / 1024x1024 legs time one batch)")
-    ap.add_argument("--all-legs", action="store_true", help="also: the bf16 reference line of the 1024x1024 shape and the 1024x1024 parity trajectory (+95 s)")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the full-depth parity legs")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary legs (the other BASELINE configs)")
+    ap.add_argument("--secondary-steps", type=int, default=2, help="timed batches per batch-1 leg of --full (the batch-16 / 1024x1024 legs time one batch)")
+    ap.add_argument("--all-legs", action="store_true", help="with --full, also: the bf16 reference line of the 1024x1024 shape and the 1024x1024 parity trajectory (+95 s)")
     ap.add_argument("--precise", action="store_true", help="model_config precise mode (split-bf16 MFMA GEMMs, fp32-class attention)")
     ap.add_argument("--hw", type=int, default=None, help="packed latent grid side: 32 = 512x512 (the metric's config), 64 = 1024x1024 (configs[4])")
     ap.add_argument("--fp8", action="store_true", help="model_config attn_fp8 + gemm_fp8 (the e4m3 GEMMs are lossy: 1e-1 per forward)")
@@ -680,6 +688,8 @@ def main():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.all_legs and not a.full:
+        ap.error("--all-legs adds legs to --full")
     if a.tiny:
         global D, STEPS, ROOFLINE_STEPS, LAYERS
         D, STEPS, ROOFLINE_STEPS, LAYERS = 256, 4, (1, 2), 4
@@ -764,17 +774,18 @@ def main():
         res.update(rec)
         if a.tiny:
             a.no_cpu_baseline = a.no_parity = a.no_secondary = True          # (those legs are full-size by construction)
-        if world == 1 and not a.no_cpu_baseline:
+        full = a.full and world == 1
+        if full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(os.cpu_count() or 1)
         xmc = {k: mc[k] for k in ("attn_fp8", "gemm_fp8", "independent_condition", "operands") if mc.get(k)}
-        if world == 1 and not a.no_parity:
+        if full and not a.no_parity:
             try:
                 # the brain side is part of the checked composition, as it is part of the timed workload (batch 1 per checker run)
                 res["parity"] = stamp_tolerance(parity_check(a.precise, xmc, hw=hw, every=1 if hw == 32 else 7, brain="all" if allmod else "eeg"), xmc, a.precise)
             except Exception as e:          # the checker must never take the measurement down with it
                 res["parity"] = {"error": f"{type(e).__name__}: {e}"}
         legs_out = []
-        if world == 1 and plain and not a.no_secondary:
+        if full and plain and not a.no_secondary:
             # ---- the other BASELINE configs on this GPU, outside the headline's timed region (bounded) ----
             # fp16_operands: the headline workload with fp16 GEMM operand images (north star: 1e-3 per forward at the bf16 mode's matrix rate);
             # realistic_stats: the headline workload on weights with a trained checkpoint's statistics (oracle.parity.realistic_stats_: mixed
@@ -824,7 +835,7 @@ def main():
                 legs_out.append((lg["name"], r))
                 torch.cuda.empty_cache()
         res["bench_wall_s"] = round(time.time() - T_START, 1)
-        emit(res, legs_out)
+        emit(res, legs_out, sidecar=a.full)
     if world > 1:
         torch.distributed.destroy_process_group()
 

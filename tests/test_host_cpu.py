@@ -251,6 +251,32 @@ def test_bench_line_is_bounded():
     assert bad["tolerance_ok"] is False
 
 
+def test_bench_run_without_full_emits_the_headline_only(tmp_path, monkeypatch):
+    """A run without --full measures the headline alone: its line carries the contract fields and no cpu_baseline / parity / leg
+    fields, and it writes no bench_legs.json (a --full run does); --all-legs without --full is refused before anything starts."""
+    import io
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = json.load(open(os.path.join(root, "profiles", "r05fin_bench_line.json")))
+    for k in ("secondary", "summary", "cpu_baseline", "parity"):
+        r.pop(k)
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    buf = io.StringIO()
+    bench.emit(r, [], stream=buf, sidecar=False)
+    assert os.listdir(tmp_path) == []
+    d = json.loads(buf.getvalue())
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline", "summary"):
+        assert k in d, k
+    assert not {"cpu_baseline", "parity", "value_fp16_operands", "legs_file"} & set(d) and set(d["summary"]) == {"headline"}
+    bench.emit(r, [], stream=io.StringIO())
+    assert os.listdir(tmp_path) == ["bench_legs.json"]
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--all-legs"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--full" in p.stderr and not p.stdout, (p.stdout, p.stderr[-500:])
+
+
 def test_bench_dump_outputs_float32_bounded_and_fixed_sample(tmp_path, monkeypatch):
     """bench.dump_outputs (--dump-outputs): an array within the budget is written whole, in float32, with its shape; a larger one is
     replaced by a sample whose indices depend only on its size, so two runs (two builds) write the same elements of the same output."""

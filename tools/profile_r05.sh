@@ -1,5 +1,5 @@
 # usage (on the GPU box, from the repo root): bash tools/profile_r05.sh <tag> [parts]
-# parts (default "line kt pmc legs modes cs3"): line = the default bench line (headline + secondary legs); kt = rocprofv3 kernel stats of
+# parts (default "line kt pmc legs modes cs3"): line = the `bench.py --full` line (headline + secondary legs); kt = rocprofv3 kernel stats of
 # the headline; pmc = FETCH / WRITE / SQ passes of the headline; legs = FETCH / WRITE passes of configs[2] (batch 16) and the 1024 x 1024
 # batch-4 shape -> pmc_traffic.json keyed by workload; modes = kernel stats of the precise and fp8-attention modes; cs3 = the CS3 / DGF batch.
 # Every rocprofv3 call sits under its own timeout (a hung profiler once cost 15 GPU-minutes). Leaves text / json summaries only.
@@ -16,7 +16,7 @@ PMCB="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no
 S="python $R/tools/db_summary.py"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 cd /tmp
-if has line; then timeout 1800 python $R/bench.py > $O/bench_line.json 2> $O/bench.err; fi
+if has line; then timeout 1800 python $R/bench.py --full > $O/bench_line.json 2> $O/bench.err; fi
 if has kt; then
   timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o p -- $BENCH > $O/bench_line_under_rocprof.json 2>> $O/bench.err
   $S /tmp/p_kt/p_results.db 0.002 > $O/bench_kernel_stats.txt 2>/dev/null
