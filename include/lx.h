@@ -233,7 +233,7 @@ int lx_rope_table(const float* ids, int L, int a0, int a1, int a2, double theta,
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no affine, eps) + AdaLN modulation: Y(bf16)[m,:] = LN(X(fp32)[m,:]) * (1 + scale[b,:]) + shift[b,:]
  * b = m / rows_per_batch.  Replaces norm1/norm1_context/norm/norm2(+mod)/norm_out (block.py:192-207,238-253,301,305).
- * shift/scale: fp32 [n_batches, mod_ld].  D % 8 == 0, D <= 8192.
+ * shift/scale: fp32 [n_batches, mod_ld].  D % 4 == 0, D <= 16384; ldx, ldy, mod_ld multiples of 4.
  * ------------------------------------------------------------------------------------------------ */
 int lx_ln_modulate(const float* X, int ldx, const float* shift, const float* scale, int mod_ld, void* Y, int ldy,
                    int M, int D, int rows_per_batch, float eps, void* stream);
