@@ -25,7 +25,8 @@ extern "C" {
 #endif
 
 /* ABI history:
- *  0.4.4  + lx_gemm_last_plan (which launch plan lx_gemm_bf16 / lx_gemm_bf16_ws chose)
+ *  0.4.4  + lx_gemm_last_plan (which launch plan lx_gemm_bf16 / lx_gemm_bf16_ws chose); additive extension of 0.4.4 (no layout change,
+ *         lx_attn_desc unchanged): + lx_attn_mask_desc, lx_attn_mask_workspace, lx_attn_mask_prep, lx_attn_fwd_masked
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -337,6 +338,37 @@ int lx_attn_fwd(const lx_attn_desc* d, void* stream);
  *   launches of at least two rounds of workgroups with at most 64 key tiles per query tile (LX_ATTN_PREFER_4WAVE / LX_ATTN_INVARIANT pin the choice per launch). */
 enum { LX_ATTN_KERNEL_NONE = 0, LX_ATTN_KERNEL_8WAVE = 1, LX_ATTN_KERNEL_4WAVE = 2 };
 int lx_attn_last_kernel(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * Joint attention under a caller's mask -- replaces F.scaled_dot_product_attention(..., attn_mask=attention_mask) of
+ * block.py:12,101-131 when the caller hands attn_forward an attention_mask (loongx_amd/csrc/attn_mask.hip).
+ * The operands, the layout and the segment bias table are those of lx_attn_fwd; on top of that a per-(query, key) mask in the LOGICAL
+ * order of the concatenated sequence [seg 0 | seg 1 | seg 2] (length S = sum of seg_len), of shape dims = [Bm, Hm, Sq, Sk] with
+ * Bm in {1, B}, Hm in {1, H}, Sq in {1, S}, Sk = S, and element strides (ignored on dims of size 1: broadcast, never materialised):
+ *   LX_ATTN_MASK_BOOL  (1 byte): non-zero = attend (torch's bool convention);
+ *   LX_ATTN_MASK_F32 / _BF16 / _F16: additive score bias in natural-log units, -inf masks the pair.
+ * A query row that attends to no key is written as zeros (what SDPA returns for it). The segment bias table still applies (a -inf pair
+ * masks the whole block), so an all-attending mask computes the lx_attn_fwd contract.
+ *   lx_attn_mask_workspace: host only; *bytes = the workspace a (descriptor, mask shape, dtype) needs.
+ *   lx_attn_mask_prep: reads the mask once (device, no synchronisation) into the workspace: the class of every (mask plane, 256-row query
+ *     tile, 64-key tile) -- EMPTY / FULL / PARTIAL -- the list of each query tile's non-EMPTY key tiles, and per-row bits / biases.
+ *   lx_attn_fwd_masked: the attention pass; reads what the last lx_attn_mask_prep on the same workspace, descriptor segments and mask shape
+ *     wrote (enqueue it first on the same stream). Flags: LX_ATTN_Q_LOG2, LX_ATTN_O_F16 (f16_ovf as in lx_attn_fwd); n_qseg and qseg_mask
+ *     must be 0. Always a running maximum. Cost scales with the number of non-EMPTY tiles.
+ * ------------------------------------------------------------------------------------------------ */
+enum { LX_ATTN_MASK_BOOL = 0, LX_ATTN_MASK_F32 = 1, LX_ATTN_MASK_BF16 = 2, LX_ATTN_MASK_F16 = 3 };
+typedef struct lx_attn_mask_desc {
+  const void* mask;          /* device pointer to element [0, 0, 0, 0] */
+  int32_t dtype;             /* LX_ATTN_MASK_* */
+  int32_t dims[4];           /* Bm, Hm, Sq, Sk */
+  int32_t _pad;
+  int64_t strides[4];        /* in elements, >= 0 */
+  void* workspace;           /* device, 256-byte aligned, caller-owned */
+  size_t workspace_bytes;
+} lx_attn_mask_desc;
+int lx_attn_mask_workspace(const lx_attn_desc* d, const lx_attn_mask_desc* m, size_t* bytes);
+int lx_attn_mask_prep(const lx_attn_desc* d, const lx_attn_mask_desc* m, void* stream);
+int lx_attn_fwd_masked(const lx_attn_desc* d, const lx_attn_mask_desc* m, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * fp8 (OCP e4m3) attention path -- BASELINE configs[4] ("fp8 MFMA attention path"); opt-in, the bf16 path above is the

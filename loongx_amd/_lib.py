@@ -53,6 +53,12 @@ class AttnDesc(C.Structure):
 
 
 LX_ATTN_Q_LOG2, LX_ATTN_BOUNDED, LX_ATTN_INVARIANT, LX_ATTN_O_F16, LX_ATTN_PREFER_4WAVE, LX_ATTN_P_EXP2 = 1, 2, 4, 8, 16, 32
+LX_ATTN_MASK_BOOL, LX_ATTN_MASK_F32, LX_ATTN_MASK_BF16, LX_ATTN_MASK_F16 = 0, 1, 2, 3
+
+
+class AttnMaskDesc(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("dtype", C.c_int32), ("dims", C.c_int32 * 4), ("_pad", C.c_int32),
+                ("strides", C.c_int64 * 4), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 class AttnF32Desc(C.Structure):
@@ -100,6 +106,9 @@ _SIGS = {
     "lx_qkv_prep": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _I, _P]),
     "lx_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _P]),
     "lx_attn_last_kernel": (C.c_int, []),
+    "lx_attn_mask_workspace": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnMaskDesc), C.POINTER(C.c_size_t)]),
+    "lx_attn_mask_prep": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnMaskDesc), _P]),
+    "lx_attn_fwd_masked": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnMaskDesc), _P]),
     "lx_qkv_prep_fp8_segs": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(QkvSeg), _I, _I, _I, _F, _P, _P, _I, _P, _I, _F, _F, _F, _P]),
     "lx_qkv_prep_fp8_f16in_segs": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(QkvSeg), _I, _I, _I, _F, _P, _P, _I, _P, _I, _F, _F, _F, _P]),
     "lx_attn_fwd_fp8": (C.c_int, [C.POINTER(AttnDesc), _F, _F, _P]),

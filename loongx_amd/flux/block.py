@@ -42,15 +42,42 @@ def _configure(eng, B, T, N, C, model_config, c_factor, image_rotary_emb, cond_r
     eng.configure(B, T, N, C, model_config, c_factor, image_rotary_emb, cond_rotary_emb if C else None)
 
 
+def _user_mask(eng, mask: torch.Tensor, B: int, S: int, C: int, model_config) -> Optional[torch.Tensor]:
+    """The caller's attention_mask as lx_attn_fwd_masked takes it ([Bm, Hm, Sq, S]), or None where the reference replaces it
+    (block.py:106-128: union_cond_attn = False or independent_condition with a condition stream, or a c_factor -- the engine's
+    segment bias table then carries the reference's own mask)."""
+    mc = model_config or {}
+    if eng.c_factor is not None or (C and (not mc.get("union_cond_attn", True) or mc.get("independent_condition", False))):
+        return None
+    if mask.dim() > 4:
+        raise ValueError(f"attention_mask: rank {mask.dim()} (expected 2..4)")
+    if mask.device.type != eng.device.type or (eng.device.index is not None and mask.device.index != eng.device.index):
+        raise ValueError(f"attention_mask: on {mask.device}, the engine runs on {eng.device}")
+    if mask.dtype not in (torch.bool, torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"attention_mask: dtype {mask.dtype} (expected bool, float32, bfloat16 or float16)")
+    m = mask
+    while m.dim() < 4:
+        m = m.unsqueeze(0)
+    H = eng.cfg.num_attention_heads
+    if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, S) or m.shape[3] != S:
+        raise ValueError(f"attention_mask: shape {tuple(mask.shape)} does not broadcast to [B={B}, H={H}, S={S}, S={S}] "
+                         "over the concatenated [text | image | condition] sequence")
+    return m
+
+
 def attn_forward(attn: LxAttention, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor = None,
                  condition_latents: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                  image_rotary_emb=None, cond_rotary_emb=None, model_config: Optional[Dict[str, Any]] = {}):
     """Inputs are the already-normalised streams. Double-block handles return (hidden, encoder[, condition]) after
     to_out / to_add_out; single-block handles return hidden or (hidden, condition) straight from attention.
     For single-block handles `hidden_states` is the [text; image] concatenation and `attn.text_len` gives the split
-    (the reference needs no split because its rows stay concatenated)."""
-    if attention_mask is not None:
-        raise NotImplementedError("explicit attention_mask tensors are not supported; masks come from model_config / c_factor")
+    (the reference needs no split because its rows stay concatenated).
+    attention_mask: what F.scaled_dot_product_attention would take over the concatenated [text | image | condition] sequence of
+    length S -- bool (True = attend) or additive float (-inf masks), broadcastable as [1|B, 1|H, 1|S, S] (rank 2..4). As in the
+    reference it is used only with union_cond_attn (default True), without independent_condition and without a c_factor; otherwise
+    the reference's own mask replaces it. Not supported in precise and attn_fp8 modes (NotImplementedError)."""
+    if attention_mask is not None and (not isinstance(attention_mask, torch.Tensor) or attention_mask.dim() < 2):
+        raise NotImplementedError("attention_mask must be a tensor of rank 2..4 over the concatenated [text | image | condition] sequence")
     eng = attn.engine
     D = eng.cfg.inner_dim
     dt = hidden_states.dtype
@@ -64,9 +91,19 @@ def attn_forward(attn: LxAttention, hidden_states: torch.Tensor, encoder_hidden_
         B, N = hidden_states.shape[0], hidden_states.shape[1] - T
         enc, hid = hidden_states[:, :T], hidden_states[:, T:]
     C = 0 if condition_latents is None else condition_latents.shape[1]
+    if attention_mask is not None:      # (before configure, which would first set the mode up)
+        if bool((model_config or {}).get("precise", eng.precise_default)):
+            raise NotImplementedError("attention_mask is not supported in precise mode")
+        if (model_config or {}).get("attn_fp8", False):
+            raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
     _configure(eng, B, T, N, C, model_config, attn._c_factor(), image_rotary_emb, cond_rotary_emb)
+    mask = None if attention_mask is None else _user_mask(eng, attention_mask, B, T + N + C, C, model_config)
     eng.load_streams(enc if T else None, hid, condition_latents, dst="XN")
-    eng.attention_module(attn.kind, attn.idx, project_out=attn.kind == "double")
+    eng.attn_mask = mask
+    try:
+        eng.attention_module(attn.kind, attn.idx, project_out=attn.kind == "double")
+    finally:
+        eng.attn_mask = None
     if attn.kind == "double":
         h = eng.read_stream("img", N).to(dt)
         e = eng.read_stream("txt", T).to(dt)

@@ -54,6 +54,9 @@ class DiTEngine:
         self.ln_lora = True
         self.model_config: Dict = {}
         self.c_factor: Optional[float] = None
+        # A caller's attention_mask (block.attn_forward only): [Bm, Hm, Sq, S] over the concatenated [txt | img | cond] sequence, set for the
+        # duration of one attn_forward call; None everywhere else (forward(), the captured graphs and generate() never see one).
+        self.attn_mask: Optional[torch.Tensor] = None
         # Split-K pair plan of the GEMM (lx_gemm_bf16_ws): needs a caller-owned workspace, one per stream -- this engine owns one
         # and runs on one stream at a time. LX_PAIR_PLAN=0 (or engine.pair_plan = False before the first step) gives launch plans
         # that do not depend on the batch size, i.e. data-parallel shards equal the single-GPU batch bit for bit.
@@ -742,6 +745,18 @@ class DiTEngine:
             okw["qseg_mask"] = 1 << [s for s, _ in streams].index("img")
         if self.f16:
             flags |= ops.ATTN_O_F16
+        if self.attn_mask is not None:
+            # the caller's mask (lx_attn_fwd_masked): always a running maximum -- BOUNDED / INVARIANT do not apply to it
+            if self.model_config.get("attn_fp8", False):
+                raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
+            if cached or img_only:
+                raise NotImplementedError("attention_mask is supported on block-level attention calls only")
+            if not prepped:
+                ops.qkv_prep_segs(Y, 2 * D, 0, D, qsegs, B, H, self.VT, in_f16=self.f16)
+            mflags = (ops.ATTN_Q_LOG2 if self._layer_nomax(wq) else 0) | (ops.ATTN_O_F16 if self.f16 else 0)
+            ops.attn_fwd_masked(Y, Y, self.VT, Y, self.attn_mask, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
+                                seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, flags=mflags, **({"f16_ovf": self.f16_ovf} if self.f16 else {}))
+            return
         if self.model_config.get("attn_fp8", False):
             # opt-in fp8 (e4m3) attention (BASELINE configs[4]): q / k / v^T go to byte images, both attention products run on
             # the 64-deep f8f6f4 MFMA; softmax statistics and the output accumulators stay fp32 (include/lx.h, lx_attn_fwd_fp8)

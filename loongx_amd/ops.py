@@ -382,6 +382,79 @@ def attn_fwd(Q, K, VT, O, *, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_v
     check(lib.lx_attn_fwd(C.byref(d), _stream()), "lx_attn_fwd")
 
 
+# ---- attention under a caller's mask (include/lx.h lx_attn_fwd_masked) ------------------------------------------------------------
+_MASK_DTYPES = {torch.bool: L.LX_ATTN_MASK_BOOL, torch.float32: L.LX_ATTN_MASK_F32, torch.bfloat16: L.LX_ATTN_MASK_BF16,
+                torch.float16: L.LX_ATTN_MASK_F16}
+
+
+def _mask_desc(mask: torch.Tensor, workspace: Optional[torch.Tensor]) -> "L.AttnMaskDesc":
+    """mask: [Bm, Hm, Sq, Sk] (rank 2 / 3: leading dims of size 1 added), any strides, bool or fp32 / bf16 / fp16 additive"""
+    if mask.dtype not in _MASK_DTYPES:
+        raise TypeError(f"attention mask: dtype {mask.dtype} is not one of bool, float32, bfloat16, float16")
+    if not mask.is_cuda:
+        raise ValueError("attention mask: must live on the GPU (the hot path has no CPU fallback)")
+    if not 2 <= mask.dim() <= 4:
+        raise ValueError(f"attention mask: rank {mask.dim()} (expected 2..4)")
+    while mask.dim() < 4:
+        mask = mask.unsqueeze(0)
+    m = L.AttnMaskDesc()
+    m.mask, m.dtype = mask.data_ptr(), _MASK_DTYPES[mask.dtype]
+    for i in range(4):
+        m.dims[i], m.strides[i] = mask.shape[i], mask.stride(i)
+    if workspace is not None:
+        m.workspace, m.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return m
+
+
+def _seg_desc(B, H, seg_len, seg_vt0, bias) -> AttnDesc:
+    d = AttnDesc()
+    d.B, d.H, d.n_seg = B, H, len(seg_len)
+    for i in range(len(seg_len)):
+        d.seg_len[i], d.seg_vt0[i] = seg_len[i], seg_vt0[i]
+    for i in range(3):
+        for j in range(3):
+            d.bias[i][j] = 0.0 if bias is None else float(bias[i][j])
+    return d
+
+
+def attn_mask_workspace(mask, *, B, H, seg_len, seg_vt0, bias=None, device=None) -> torch.Tensor:
+    """A workspace (uint8 tensor) of the size lx_attn_mask_workspace asks for this mask shape / dtype and these segments."""
+    d, m = _seg_desc(B, H, seg_len, seg_vt0, bias), _mask_desc(mask, None)
+    n = C.c_size_t(0)
+    check(lib.lx_attn_mask_workspace(C.byref(d), C.byref(m), C.byref(n)), "lx_attn_mask_workspace")
+    return torch.empty(max(n.value, 1), dtype=torch.uint8, device=device if device is not None else mask.device)
+
+
+def attn_mask_prep(mask, workspace, *, B, H, seg_len, seg_vt0, bias=None) -> None:
+    """Read `mask` once into `workspace` (tile classes, per-query-tile lists of non-EMPTY key tiles, row bits / biases) for
+    attn_fwd_masked(..., prepped=True) with the same segments and mask shape."""
+    d, m = _seg_desc(B, H, seg_len, seg_vt0, bias), _mask_desc(mask, workspace)
+    check(lib.lx_attn_mask_prep(C.byref(d), C.byref(m), _stream()), "lx_attn_mask_prep")
+
+
+def attn_fwd_masked(Q, K, VT, O, mask, *, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias=None, scale=None, flags=0,
+                    f16_ovf=None, workspace=None, prepped=False) -> torch.Tensor:
+    """attn_fwd under a per-(query, key) mask over the concatenated segments (SDPA's attn_mask: bool = attend, float = additive,
+    -inf masks); flags: 0 | ATTN_Q_LOG2 | ATTN_O_F16. Runs lx_attn_mask_prep first unless `prepped` (the workspace then holds what an
+    attn_mask_prep of the same mask wrote). Returns the workspace."""
+    if workspace is None:
+        workspace = attn_mask_workspace(mask, B=B, H=H, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, device=Q.device)
+    d = _attn_desc(Q, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
+    d.flags, d.f16_ovf = flags, _p(f16_ovf)
+    m = _mask_desc(mask, workspace)
+    if not prepped:
+        check(lib.lx_attn_mask_prep(C.byref(d), C.byref(m), _stream()), "lx_attn_mask_prep")
+    if TIMER is not None and TIMER.active:
+        S = sum(seg_len)
+        s, e = TIMER.bracket("attn", 4.0 * B * H * S * S * 128)
+        s.record()
+        check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked")
+        e.record()
+        return workspace
+    check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked")
+    return workspace
+
+
 # fp8 (e4m3) attention path: fixed operand scales. q and k are RMS-normalised (|x| <= sqrt(128) * |w|), so 16 keeps them inside
 # e4m3's normal range [2^-6, 448] with headroom; v is a raw projection output and is stored unscaled (clamped to +-448).
 # q scale: chosen so that (1/sqrt(128)) x log2(e) / (q scale x k scale) = 2^-11 exactly -- the attention kernel then applies the whole
