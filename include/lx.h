@@ -498,7 +498,16 @@ int lx_chan_gemm_f32(const float* X, long x_bstride, int ldx, const float* W, in
  * DGF (Dynamic Gated Fusion; `DUAN` in the reference, src/train/model.py:947-1035). fp32 [B,C,L].
  * gate: conv1x1 C->Hd (gw1 [Hd,C], gb1) ReLU conv1x1 Hd->C (gw2 [C,Hd], gb2) sigmoid, averaged over L;
  * mlp: conv1x1 C->Hd (mw1, mb1) ReLU conv1x1 Hd->2C (mw2 [2C,Hd], mb2) on the L-pooled condition.
- * ws: >= lx_duan_workspace_bytes(B,C,L,Hd) bytes of scratch.
+ * ws: >= lx_duan_workspace_bytes(B,C,L,Hd) bytes of scratch. Its contents after a call are intermediate results at a fixed layout
+ * (T = ceil(L/64); a256 = rounded up to 256 bytes; fp32 unless noted; a region starts where the previous one ends unless aligned):
+ *   stats [B][C][4]  at a256(ws)          mean of x, variance of x, mean of c (not written by the wide form), unused
+ *   gpart [B][T][C]                       sum of the gate's sigmoids over each 64 positions
+ *   coef  [B][C][2]                       (A, Bc) of y = A x + Bc
+ *   imp   [B][C]                          mean |y| before the top-k mask
+ *   hid   [B][Hd][L] at a256(end of imp)  relu(gw1 c + gb1); written when C, Hd and L are multiples of 4 (the MFMA gate)
+ *   cpart [B][T][C]  at a256(end of hid)  sum of c over each 64 positions; wide form only
+ *   bf16 hi / lo images of gw1, gw2 (4 x Hd*C uint16) at a256(end of cpart); wide form only
+ * wide form: the MFMA gate with Hd % 128 == 0, C % 128 == 0, C > 128 and gb1, gb2 16-byte aligned. Nothing else in ws is written.
  * ------------------------------------------------------------------------------------------------ */
 size_t lx_duan_workspace_bytes(int B, int C, int L, int Hd);
 int lx_duan_fwd(const float* x, const float* c, const float* gw1, const float* gb1, const float* gw2, const float* gb2,

@@ -289,25 +289,29 @@ __global__ void pyramid_pool_kernel(const float* __restrict__ x, float* __restri
   y[(size_t)row * ldy + y_col0 + col] = a / (float)(en - st);
 }
 
+// Statistics are taken of x - x[0]: a row that sits on a large offset (mean 1e3, deviations of a few units) would otherwise lose the
+// fp32 rounding of its MEAN (half an ulp of 1e3 = 3e-5) in every x - mean, 2e-5 of the output; the differences from the row's first
+// element are small and (nearly) exact, and LayerNorm does not depend on the shift.
 __global__ __launch_bounds__(256) void layernorm_relu_kernel(float* __restrict__ x, const float* __restrict__ g,
                                                              const float* __restrict__ bta, int D, float eps) {
   __shared__ float red[8];
   float* xr = x + (size_t)blockIdx.x * D;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float piv = xr[0];
   float s = 0.f;
-  for (int i = tid; i < D; i += 256) s += xr[i];
+  for (int i = tid; i < D; i += 256) s += xr[i] - piv;
   s = wave_sum(s);
   if (lane == 0) red[wave] = s;
   __syncthreads();
-  const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)D;
+  const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)D;      // of x - piv
   float q = 0.f;
-  for (int i = tid; i < D; i += 256) { const float d = xr[i] - mean; q += d * d; }
+  for (int i = tid; i < D; i += 256) { const float d = (xr[i] - piv) - mean; q += d * d; }
   q = wave_sum(q);
   if (lane == 0) red[4 + wave] = q;
-  __syncthreads();
+  __syncthreads();                                                         // (every thread has read xr[0] before anyone overwrites it)
   const float rstd = rsqrtf((red[4] + red[5] + red[6] + red[7]) / (float)D + eps);
   for (int i = tid; i < D; i += 256) {
-    const float v = (xr[i] - mean) * rstd * g[i] + bta[i];
+    const float v = ((xr[i] - piv) - mean) * rstd * g[i] + bta[i];
     xr[i] = v > 0.f ? v : 0.f;
   }
 }

@@ -303,6 +303,16 @@ __global__ __launch_bounds__(256) void duan_mask_kernel(const float* __restrict_
 
 }  // namespace
 
+// Workspace layout (include/lx.h states the same; tests/test_cs3_tiles_gpu.py reads every region back at these offsets). T = ceil(L / 64),
+// a256(p) = p rounded up to 256 bytes, all regions fp32 unless noted, each starting where the previous one ends unless aligned:
+//   stats  [B][C][4]     a256(ws)           mean of x, variance of x, mean of c (NOT written by the wide form), unused
+//   gpart  [B][T][C]                        per 64 positions: sum of the gate's sigmoids
+//   coef   [B][C][2]                        (A, Bc) of y = A x + Bc
+//   imp    [B][C]                           mean |y| before the mask
+//   hid    [B][Hd][L]    a256(end of imp)   relu(W1 c + b1): MFMA gate only (C, Hd, L multiples of 4)
+//   cpart  [B][T][C]     a256(end of hid)   per 64 positions: sum of c; wide form only
+//   w1h, w1l, w2h, w2l   a256(end of cpart) bf16 hi / lo images of gw1 and gw2, Hd * C uint16 each; wide form only
+// (wide form: MFMA gate, Hd % 128 == 0, C % 128 == 0, C > 128, gb1 and gb2 16-byte aligned). The four alignments cost < 1024 of the 2048 spare bytes.
 extern "C" size_t lx_duan_workspace_bytes(int B, int C, int L, int Hd) {
   const size_t ntile = (size_t)(L + 63) / 64;
   // + the gate network's hidden activations [B, Hd, L] for the MFMA form of the gate (C % 4 == 0)

@@ -36,3 +36,194 @@ def relerr(a, b):
         with open(rec, "a") as f:
             f.write(json.dumps({"test": os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0], "line": fr.lineno, "relerr": e}) + "\n")
     return e
+
+
+# ------------------------------------------------------------------------------------------------ CS3 / DGF float64 references
+# Plain float64 restatements of csrc/cs3.hip and csrc/dgf.hip, one function per launch (tests/test_cs3_tiles_gpu.py compares every launch
+# with them; tests/test_cs3_ref_cpu.py pins them to oracle.cs3.DUAN and the goldens on the CPU). Inputs may live on any device.
+U24 = 2.0 ** -24          # fp32 unit roundoff
+
+
+def gamma_n(n):
+    """(1 + u)^n - 1 <= n u / (1 - n u): the classic bound on n chained fp32 roundings, in any order."""
+    return n * U24 / (1.0 - n * U24)
+
+
+def chan_gemm_ref(X, W, bias=None):
+    """z[b, n, l] = sum_k W[n, k] X[b, k, l] + bias[n] in float64, and mag = sum_k |W||X| + |bias| (what a rounding error is relative to)."""
+    X, W = X.double(), W.double()
+    z = torch.einsum("nk,bkl->bnl", W, X)
+    mag = torch.einsum("nk,bkl->bnl", W.abs(), X.abs())
+    if bias is not None:
+        z = z + bias.double()[None, :, None]
+        mag = mag + bias.double().abs()[None, :, None]
+    return z, mag
+
+
+def tile_sums(v, tile=64):
+    """[B, C, L] -> [B, ceil(L / tile), C]: sums over each `tile` positions (the ragged last tile sums what it has)."""
+    B, C, L = v.shape
+    nt = (L + tile - 1) // tile
+    p = torch.zeros(B, C, nt * tile, dtype=v.dtype, device=v.device)
+    p[:, :, :L] = v
+    return p.view(B, C, nt, tile).sum(3).permute(0, 2, 1).contiguous()
+
+
+def linear_ref(X, W, bias=None):
+    """X [M, K] W[N, K]^T + bias in float64, and the magnitude sum_k |x||w| + |bias|."""
+    X, W = X.double(), W.double()
+    y, mag = X @ W.T, X.abs() @ W.abs().T
+    if bias is not None:
+        y, mag = y + bias.double(), mag + bias.double().abs()
+    return y, mag
+
+
+def gelu_erf(x):
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def chanmix_ref(x, W, bias=None, resid=None, ln_g=None, ln_b=None, act=0, eps=1e-5):
+    """y[b, o, l] = LN_o(sum_i W[o, i] act(x[b, i, l]) + bias[o] + resid[b, o, l]); exact-erf GELU when act = 1; LayerNorm over channels."""
+    x = x.double()
+    if act == 1:
+        x = gelu_erf(x)
+    z = torch.einsum("oi,bil->bol", W.double(), x)
+    if bias is not None:
+        z = z + bias.double()[None, :, None]
+    if resid is not None:
+        z = z + resid.double()
+    if ln_g is not None:
+        m = z.mean(1, keepdim=True)
+        v = ((z - m) ** 2).mean(1, keepdim=True)
+        z = (z - m) / torch.sqrt(v + eps) * ln_g.double()[None, :, None] + ln_b.double()[None, :, None]
+    return z
+
+
+def pyramid_pool_ref(x, sizes):
+    """nn.AdaptiveAvgPool1d's bins (start = floor(j L / s), end = ceil((j + 1) L / s)) for every size, concatenated; float64."""
+    x = x.double()
+    L = x.shape[-1]
+    cols = []
+    for s in sizes:
+        for j in range(s):
+            st, en = (j * L) // s, -((-(j + 1) * L) // s)
+            cols.append(x[..., st:en].mean(-1))
+    return torch.stack(cols, -1)
+
+
+def layernorm_relu_ref(x, g, b, eps=1e-5):
+    x = x.double()
+    m = x.mean(-1, keepdim=True)
+    v = ((x - m) ** 2).mean(-1, keepdim=True)
+    return torch.relu((x - m) / torch.sqrt(v + eps) * g.double() + b.double())
+
+
+def s4_fft_conv(u, K, D):
+    """y[b, h, l] = sum_{j <= l} K[h, j] u[b, h, l - j] + D[h] u[b, h, l] by a zero-padded float64 FFT (u [B, H, L], K [H, L], numpy)."""
+    u, K = np.asarray(u, np.float64), np.asarray(K, np.float64)
+    L = u.shape[-1]
+    y = np.fft.irfft(np.fft.rfft(u, 2 * L, axis=-1) * np.fft.rfft(K, 2 * L, axis=-1)[None], 2 * L, axis=-1)[..., :L]
+    return y + np.asarray(D, np.float64)[None, :, None] * u
+
+
+def stable_topk_mask(imp, keep_k):
+    """[B, C] bool: the keep_k largest importances of every batch element, ties to the lower channel index (a stable descending sort)."""
+    B, C = imp.shape
+    keep = torch.zeros(B, C, dtype=torch.bool)
+    for b in range(B):
+        v = imp[b].detach().cpu().double().numpy()
+        order = np.argsort(-v, kind="stable")
+        keep[b, torch.from_numpy(order[:keep_k].copy())] = True
+    return keep.to(imp.device)
+
+
+def duan_params(d):
+    """oracle.cs3.DUAN state dict -> the [out, in] matrices lx_duan_fwd takes."""
+    return {k: (v.detach().reshape(v.shape[0], -1) if v.dim() == 3 else v.detach()).contiguous() for k, v in d.state_dict().items()}
+
+
+def duan_gate_ref(c, p):
+    """hid = relu(W1 c + b1) [B, Hd, L], its magnitude, and z = W2 hid + b2 [B, C, L] with its magnitude; float64."""
+    h, hmag = chan_gemm_ref(c, p["gate.0.weight"], p["gate.0.bias"])
+    hid = torch.relu(h)
+    z, zmag = chan_gemm_ref(hid, p["gate.2.weight"], p["gate.2.bias"])
+    return hid, hmag, z, zmag
+
+
+def duan_coef_ref(mean, var, gmean, cmean, p, eps):
+    """(A, Bc) of y = A x + Bc per (b, c) from the row statistics, the gate's mean over L and the condition's mean over L; float64.
+    The layer statistics combine the rows exactly: mu_l = mean_c mean, var_l = mean_c (var + (mean - mu_l)^2)."""
+    mean, var, gmean, cmean = mean.double(), var.double(), gmean.double(), cmean.double()
+    C = mean.shape[1]
+    mu_l = mean.mean(1, keepdim=True)
+    var_l = (var + (mean - mu_l) ** 2).mean(1, keepdim=True)
+    hid2 = torch.relu(cmean @ p["mlp.0.weight"].double().T + p["mlp.0.bias"].double())
+    gb = hid2 @ p["mlp.2.weight"].double().T + p["mlp.2.bias"].double()
+    gam, bet = gb[:, :C], gb[:, C:]
+    mu = gmean * mean + (1 - gmean) * mu_l
+    sig = gmean * torch.sqrt(var + eps) + (1 - gmean) * torch.sqrt(var_l + eps)
+    A = (1 + gam) / sig
+    return A, bet - A * mu
+
+
+def duan_ref_stages(x, c, p, keep_k, eps=1e-3):
+    """The DUAN in float64, split at the places lx_duan_fwd leaves intermediate results: every value of the dict is what one launch writes."""
+    x, c = x.double(), c.double()
+    L = x.shape[2]
+    st = {"mean": x.mean(2), "cmean": c.mean(2)}
+    st["var"] = ((x - st["mean"][:, :, None]) ** 2).mean(2)
+    st["hid"], st["hid_mag"], st["z"], st["z_mag"] = duan_gate_ref(c, p)
+    st["gpart"] = tile_sums(torch.sigmoid(st["z"]))
+    st["cpart"] = tile_sums(c)
+    st["gmean"] = st["gpart"].sum(1) / L
+    st["A"], st["Bc"] = duan_coef_ref(st["mean"], st["var"], st["gmean"], st["cmean"], p, eps)
+    st["y_full"] = st["A"][:, :, None] * x + st["Bc"][:, :, None]
+    st["imp"] = st["y_full"].abs().mean(2)
+    st["keep"] = stable_topk_mask(st["imp"], keep_k)
+    st["y"] = st["y_full"] * st["keep"][:, :, None]
+    return st
+
+
+def kept_set_margin(imp, keep_k, delta):
+    """[B, C] bool: channels whose float64 importance lies within delta (relative) of the boundary between ranks keep_k - 1 and keep_k
+    (the mean of the two importances there). Either outcome is acceptable for them; nothing is undecided when keep_k == C."""
+    B, C = imp.shape
+    if keep_k >= C:
+        return torch.zeros(B, C, dtype=torch.bool, device=imp.device)
+    s = imp.double().sort(1, descending=True).values
+    edge = 0.5 * (s[:, keep_k - 1] + s[:, keep_k])[:, None]
+    return (imp.double() - edge).abs() <= delta * edge
+
+
+def duan_case(C, Hd, B, L, seed, x_offset=0.0):
+    """A seeded oracle.cs3.DUAN(C, Hd) with non-trivial biases, and its inputs x, c [B, C, L] (fp32, CPU)."""
+    from oracle import cs3
+    torch.manual_seed(seed)
+    d = cs3.DUAN(C, hidden_dim=Hd).eval()
+    g = torch.Generator().manual_seed(seed + 1000)
+    x = torch.randn(B, C, L, generator=g) * (0.5 + torch.rand(1, C, 1, generator=g)) + x_offset + 0.3 * torch.randn(1, C, 1, generator=g)
+    c = torch.randn(B, C, L, generator=g)
+    return d, x, c
+
+
+# (C, L, seed, keep_k) of the full-size kept-set check: seeds for which the float64 reference itself leaves at most 1 % of the channels of
+# every batch element within 2e-5 of the rank boundary (tests/test_cs3_ref_cpu.py verifies that on the CPU)
+DUAN_KEPT_CASES = [(512, 4096, 1, 358), (512, 4096, 7, 358)]
+DUAN_KEPT_DELTA = 2e-5     # the DUAN's y bound: importance is a mean of |y|
+
+
+def duan_tie_case(seed=3):
+    """Ties across the top-k boundary: gate.2.weight = mlp.2.weight = 0 and channel-constant biases make g, gamma, beta the same for every
+    channel, and the 16 rows of x are 4 distinct rows repeated 4 times (channel i is row i % 4): channels i, i + 4, i + 8, i + 12 have
+    equal importance, and keep_k = 6 cuts through the second group, of which the two LOWEST channel indices must survive."""
+    C, Hd, B, L, keep_k = 16, 64, 3, 256, 6
+    d, x, c = duan_case(C, Hd, B, L, seed)
+    with torch.no_grad():
+        d.gate[2].weight.zero_()
+        d.mlp[2].weight.zero_()
+        d.gate[2].bias.fill_(0.3)
+        d.mlp[2].bias[:C].fill_(0.2)
+        d.mlp[2].bias[C:].fill_(0.1)
+    scale = torch.tensor([1.0, 2.0, 0.5, 3.0]).view(1, 4, 1)
+    x = (x[:, :4] * scale).repeat(1, 4, 1).contiguous()
+    return d, x, c, keep_k
