@@ -353,8 +353,12 @@ int lx_attn_last_kernel(void);
  *   lx_attn_mask_prep: reads the mask once (device, no synchronisation) into the workspace: the class of every (mask plane, 256-row query
  *     tile, 64-key tile) -- EMPTY / FULL / PARTIAL -- the list of each query tile's non-EMPTY key tiles, and per-row bits / biases.
  *   lx_attn_fwd_masked: the attention pass; reads what the last lx_attn_mask_prep on the same workspace, descriptor segments and mask shape
- *     wrote (enqueue it first on the same stream). Flags: LX_ATTN_Q_LOG2, LX_ATTN_O_F16 (f16_ovf as in lx_attn_fwd); n_qseg and qseg_mask
- *     must be 0. Always a running maximum. Cost scales with the number of non-EMPTY tiles.
+ *     wrote (enqueue it first on the same stream). Flags: LX_ATTN_Q_LOG2, LX_ATTN_O_F16 (f16_ovf as in lx_attn_fwd). n_qseg and qseg_mask
+ *     mean what they mean in lx_attn_fwd: segments without queries serve keys and values, their rows of O are not written, and the grid
+ *     covers the query tiles of the query segments only (rejected when a segment without queries shares rows of O with a query
+ *     segment: its rows could not stay unwritten). The two fields are the attention pass's alone: the prep pass ignores them and
+ *     classifies every query tile, so one prepared workspace serves launches with different query subsets (a forward's 56 full launches
+ *     and the image-only launch of its last block). Always a running maximum. Cost scales with the number of non-EMPTY tiles.
  * ------------------------------------------------------------------------------------------------ */
 enum { LX_ATTN_MASK_BOOL = 0, LX_ATTN_MASK_F32 = 1, LX_ATTN_MASK_BF16 = 2, LX_ATTN_MASK_F16 = 3 };
 typedef struct lx_attn_mask_desc {

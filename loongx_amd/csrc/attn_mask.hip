@@ -11,7 +11,8 @@
 //     log2 units for float masks. Both are stored in the order the attention kernel holds its scores: position p = lhi*32 + kb*16 + r of a
 //     row is key kb*32 + 8*(r>>2) + 4*lhi + (r&3) of the tile (lane half lhi, score block kb, accumulator register r), so a lane reads one
 //     32-bit word of bits or 32 contiguous floats.
-//   attention (lx_attn_fwd_masked): one workgroup = 8 waves = 256 query rows of one (batch, head), the work decode of lx_attn_fwd; it walks
+//   attention (lx_attn_fwd_masked): one workgroup = 8 waves = 256 query rows of one (batch, head), the work decode of lx_attn_fwd over the
+//     query tiles of the segments that have queries (n_qseg / qseg_mask: the others serve keys and values only); it walks
 //     the query tile's list only, so EMPTY tiles are never staged or multiplied. K [64 keys][128] and V^T [128][64 keys] tiles are staged by
 //     LDS-DMA into a double buffer (one barrier per tile); S^T = K.Q^T and O^T += V^T.P^T on v_mfma_f32_32x32x16_bf16; online softmax in
 //     fp32 with a running maximum (an arbitrary mask voids the bounded-score argument). FULL tiles do no mask work, PARTIAL tiles read the
@@ -117,6 +118,7 @@ __global__ __launch_bounds__(256) void lx_attn_mask_list_kernel(const PrepArgs a
 struct MaskAttnArgs {
   lx_attn_desc d;
   MaskGeom g;
+  int qq_start[4];            // prefix of 256-row query tiles over the segments that HAVE queries (n_qseg / qseg_mask): the launch's items
   int wide_store;
   const int* list;
   const void* data;
@@ -135,10 +137,13 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lhi = lane >> 5;
   const int BH = D.B * D.H;
-  int qt, bh;
-  lx_item_decode((int)blockIdx.x, (int)gridDim.x, BH, G.n_qt, qt, bh);
+  // items = the query tiles of the segments with queries only; qc counts those, qt is the tile's index among ALL segments' tiles (what
+  // the prep pass keyed its lists and row data by). A segment without queries has an empty range in qq_start and is never decoded.
+  int qc, bh;
+  lx_item_decode((int)blockIdx.x, (int)gridDim.x, BH, args.qq_start[3], qc, bh);
   const int b = bh / D.H, h = bh % D.H;
-  const int sq = seg_of(qt, G.qt_start, G.n_seg);
+  const int sq = seg_of(qc, args.qq_start, G.n_seg);
+  const int qt = G.qt_start[sq] + (qc - args.qq_start[sq]);
   const int q_len = D.seg_len[sq];
   const int q_in_seg = (qt - G.qt_start[sq]) * MQBLK + wave * 32 + l31;
   const bool q_valid = q_in_seg < q_len;
@@ -418,7 +423,18 @@ extern "C" int lx_attn_fwd_masked(const lx_attn_desc* d, const lx_attn_mask_desc
   LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd_masked: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required");
   LX_CHECK_ARG(d->q_col % 8 == 0 && d->k_col % 8 == 0 && d->o_col % 4 == 0, "lx_attn_fwd_masked: column offsets must be 16-byte aligned");
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_Q_LOG2 | LX_ATTN_O_F16)) == 0, "lx_attn_fwd_masked: flags=%d: only LX_ATTN_Q_LOG2 and LX_ATTN_O_F16 are accepted", d->flags);
-  LX_CHECK_ARG(d->n_qseg == 0 && d->qseg_mask == 0, "lx_attn_fwd_masked: n_qseg / qseg_mask must be 0 (every segment has queries)");
+  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd_masked: n_qseg=%d must be 0..n_seg", d->n_qseg);
+  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd_masked: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
+  // which segments have queries, as in lx_attn_fwd: qseg_mask when given, else the first n_qseg (0: all)
+  const int qmask = d->qseg_mask != 0 ? d->qseg_mask : (1 << (d->n_qseg > 0 ? d->n_qseg : d->n_seg)) - 1;
+  // "the rows of O of a segment without queries are not written" can only hold if no query segment's rows [seg_row0, + B * seg_len) share them
+  for (int s = 0; s < d->n_seg; ++s)
+    for (int t = 0; t < d->n_seg; ++t) {
+      if (((qmask >> s) & 1) || !((qmask >> t) & 1)) continue;
+      const long long s0 = d->seg_row0[s], s1 = s0 + (long long)d->B * d->seg_len[s], t0 = d->seg_row0[t], t1 = t0 + (long long)d->B * d->seg_len[t];
+      LX_CHECK_ARG(s1 <= t0 || t1 <= s0, "lx_attn_fwd_masked: n_qseg / qseg_mask leave segment %d without queries, but its rows [%lld, %lld) of O overlap "
+                   "query segment %d's rows [%lld, %lld)", s, s0, s1, t, t0, t1);
+    }
   for (int s = 0; s < d->n_seg; ++s) {
     const long long vt_end = (long long)d->seg_vt0[s] + (d->seg_len[s] + KVBLK - 1) / KVBLK * KVBLK;
     LX_CHECK_ARG(vt_end <= d->vt_ld, "lx_attn_fwd_masked: segment %d's V^T tiles end at %lld > vt_ld=%d", s, vt_end, d->vt_ld);
@@ -430,7 +446,14 @@ extern "C" int lx_attn_fwd_masked(const lx_attn_desc* d, const lx_attn_mask_desc
   a.wide_store = d->ldo % 8 == 0 && d->o_col % 8 == 0 && ((uintptr_t)d->O & 15) == 0;
   a.list = (const int*)((const char*)m->workspace + g.list_off);
   a.data = (const char*)m->workspace + g.data_off;
-  const int grid = g.n_qt * d->B * d->H;
+  // The prep pass classified every query tile; this launch covers the tiles of the query segments only.
+  int nq = 0;
+  for (int s = 0; s < 3; ++s) {
+    a.qq_start[s] = nq;
+    if (s < d->n_seg && ((qmask >> s) & 1)) nq += g.qt_start[s + 1] - g.qt_start[s];
+  }
+  a.qq_start[3] = nq;
+  const int grid = nq * d->B * d->H;
   hipStream_t s = (hipStream_t)stream;
   if (m->dtype == LX_ATTN_MASK_BOOL) hipLaunchKernelGGL(lx_attn_mask_kernel<false>, dim3(grid), dim3(512), 0, s, a);
   else hipLaunchKernelGGL(lx_attn_mask_kernel<true>, dim3(grid), dim3(512), 0, s, a);

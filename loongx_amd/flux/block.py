@@ -13,6 +13,8 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from .engine import mask_argument, refuse_masked_modes
+
 
 class LxAttention:
     def __init__(self, engine, kind: str, idx: int):
@@ -42,29 +44,6 @@ def _configure(eng, B, T, N, C, model_config, c_factor, image_rotary_emb, cond_r
     eng.configure(B, T, N, C, model_config, c_factor, image_rotary_emb, cond_rotary_emb if C else None)
 
 
-def _user_mask(eng, mask: torch.Tensor, B: int, S: int, C: int, model_config) -> Optional[torch.Tensor]:
-    """The caller's attention_mask as lx_attn_fwd_masked takes it ([Bm, Hm, Sq, S]), or None where the reference replaces it
-    (block.py:106-128: union_cond_attn = False or independent_condition with a condition stream, or a c_factor -- the engine's
-    segment bias table then carries the reference's own mask)."""
-    mc = model_config or {}
-    if eng.c_factor is not None or (C and (not mc.get("union_cond_attn", True) or mc.get("independent_condition", False))):
-        return None
-    if mask.dim() > 4:
-        raise ValueError(f"attention_mask: rank {mask.dim()} (expected 2..4)")
-    if mask.device.type != eng.device.type or (eng.device.index is not None and mask.device.index != eng.device.index):
-        raise ValueError(f"attention_mask: on {mask.device}, the engine runs on {eng.device}")
-    if mask.dtype not in (torch.bool, torch.float32, torch.bfloat16, torch.float16):
-        raise ValueError(f"attention_mask: dtype {mask.dtype} (expected bool, float32, bfloat16 or float16)")
-    m = mask
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    H = eng.cfg.num_attention_heads
-    if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, S) or m.shape[3] != S:
-        raise ValueError(f"attention_mask: shape {tuple(mask.shape)} does not broadcast to [B={B}, H={H}, S={S}, S={S}] "
-                         "over the concatenated [text | image | condition] sequence")
-    return m
-
-
 def attn_forward(attn: LxAttention, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor = None,
                  condition_latents: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                  image_rotary_emb=None, cond_rotary_emb=None, model_config: Optional[Dict[str, Any]] = {}):
@@ -76,8 +55,8 @@ def attn_forward(attn: LxAttention, hidden_states: torch.Tensor, encoder_hidden_
     length S -- bool (True = attend) or additive float (-inf masks), broadcastable as [1|B, 1|H, 1|S, S] (rank 2..4). As in the
     reference it is used only with union_cond_attn (default True), without independent_condition and without a c_factor; otherwise
     the reference's own mask replaces it. Not supported in precise and attn_fp8 modes (NotImplementedError)."""
-    if attention_mask is not None and (not isinstance(attention_mask, torch.Tensor) or attention_mask.dim() < 2):
-        raise NotImplementedError("attention_mask must be a tensor of rank 2..4 over the concatenated [text | image | condition] sequence")
+    if attention_mask is not None:
+        mask_argument(attention_mask)
     eng = attn.engine
     D = eng.cfg.inner_dim
     dt = hidden_states.dtype
@@ -92,12 +71,9 @@ def attn_forward(attn: LxAttention, hidden_states: torch.Tensor, encoder_hidden_
         enc, hid = hidden_states[:, :T], hidden_states[:, T:]
     C = 0 if condition_latents is None else condition_latents.shape[1]
     if attention_mask is not None:      # (before configure, which would first set the mode up)
-        if bool((model_config or {}).get("precise", eng.precise_default)):
-            raise NotImplementedError("attention_mask is not supported in precise mode")
-        if (model_config or {}).get("attn_fp8", False):
-            raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
+        refuse_masked_modes(model_config, eng.precise_default)
     _configure(eng, B, T, N, C, model_config, attn._c_factor(), image_rotary_emb, cond_rotary_emb)
-    mask = None if attention_mask is None else _user_mask(eng, attention_mask, B, T + N + C, C, model_config)
+    mask = None if attention_mask is None else eng.user_mask(attention_mask, B, T + N + C, C, model_config, eng.c_factor)
     eng.load_streams(enc if T else None, hid, condition_latents, dst="XN")
     eng.attn_mask = mask
     try:

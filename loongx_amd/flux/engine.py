@@ -32,6 +32,21 @@ def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def mask_argument(attention_mask) -> None:
+    """What an attention_mask argument must be before anything else is looked at (attn_forward, tranformer_forward, set_conditioning)."""
+    if not isinstance(attention_mask, torch.Tensor) or attention_mask.dim() < 2:
+        raise NotImplementedError("attention_mask must be a tensor of rank 2..4 over the concatenated [text | image | condition] sequence")
+
+
+def refuse_masked_modes(model_config: Optional[Dict], precise_default: bool) -> None:
+    """The arithmetic modes that have no masked attention kernel."""
+    mc = model_config or {}
+    if bool(mc.get("precise", precise_default)):
+        raise NotImplementedError("attention_mask is not supported in precise mode")
+    if mc.get("attn_fp8", False):
+        raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
+
+
 class DiTEngine:
     def __init__(self, weights: PackedWeights, device="cuda"):
         self.w = weights
@@ -54,9 +69,14 @@ class DiTEngine:
         self.ln_lora = True
         self.model_config: Dict = {}
         self.c_factor: Optional[float] = None
-        # A caller's attention_mask (block.attn_forward only): [Bm, Hm, Sq, S] over the concatenated [txt | img | cond] sequence, set for the
-        # duration of one attn_forward call; None everywhere else (forward(), the captured graphs and generate() never see one).
+        # A caller's attention_mask, [Bm, Hm, Sq, S] over the concatenated [txt | img | cond] sequence.
+        #   attn_mask: block.attn_forward's, set for the duration of one call (the mask is prepared inside every such call);
+        #   cond_mask: the conditioning's (set_conditioning(attention_mask=...)): prepared ONCE there into `_mask_ws`, which all 57 attention
+        #     launches of every forward of that conditioning read (attn_fwd_masked(prepped=True)), eagerly or from the captured step graph.
+        # Both None: the unmasked kernels, untouched.
         self.attn_mask: Optional[torch.Tensor] = None
+        self.cond_mask: Optional[torch.Tensor] = None
+        self._mask_ws: Optional[torch.Tensor] = None
         # Split-K pair plan of the GEMM (lx_gemm_bf16_ws): needs a caller-owned workspace, one per stream -- this engine owns one
         # and runs on one stream at a time. LX_PAIR_PLAN=0 (or engine.pair_plan = False before the first step) gives launch plans
         # that do not depend on the batch size, i.e. data-parallel shards equal the single-GPU batch bit for bit.
@@ -480,14 +500,65 @@ class DiTEngine:
                     b["cond"][o] = lb
         return b
 
+    # --------------------------------------------------------------------------------- the caller's attention mask
+    def user_mask(self, mask: torch.Tensor, B: int, S: int, C: int, model_config, c_factor: Optional[float]) -> Optional[torch.Tensor]:
+        """The caller's attention_mask as lx_attn_fwd_masked takes it ([Bm, Hm, Sq, S]), or None where the reference replaces it
+        (block.py:106-128: union_cond_attn = False or independent_condition with a condition stream, or a c_factor -- the engine's
+        segment bias table then carries the reference's own mask)."""
+        mc = model_config or {}
+        if c_factor is not None or (C and (not mc.get("union_cond_attn", True) or mc.get("independent_condition", False))):
+            return None
+        if mask.dim() > 4:
+            raise ValueError(f"attention_mask: rank {mask.dim()} (expected 2..4)")
+        if mask.device.type != self.device.type or (self.device.index is not None and mask.device.index != self.device.index):
+            raise ValueError(f"attention_mask: on {mask.device}, the engine runs on {self.device}")
+        if mask.dtype not in (torch.bool, torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"attention_mask: dtype {mask.dtype} (expected bool, float32, bfloat16 or float16)")
+        m = mask
+        while m.dim() < 4:
+            m = m.unsqueeze(0)
+        H = self.cfg.num_attention_heads
+        if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, S) or m.shape[3] != S:
+            raise ValueError(f"attention_mask: shape {tuple(mask.shape)} does not broadcast to [B={B}, H={H}, S={S}, S={S}] "
+                             "over the concatenated [text | image | condition] sequence")
+        return m
+
+    def _mask_segments(self):
+        """(seg_len, seg_vt0, bias) of the forward's attention launches, as the mask prep and _attention both describe them"""
+        streams = self._all_streams()
+        bias = [[0.0] * 3 for _ in range(3)]
+        for qi, (qs, _) in enumerate(streams):
+            for ki, (ks, _) in enumerate(streams):
+                bias[qi][ki] = self.attn_bias[qs][ks]
+        return [L for _, L in streams], [self.vt0[s] for s, _ in streams], bias
+
+    def _prep_cond_mask(self) -> None:
+        """ONE lx_attn_mask_prep per conditioning, into an engine-owned workspace (allocated here, outside any stream capture; kept while
+        it is large enough, so the step graphs that hold its address stay valid from image to image)."""
+        seg_len, seg_vt0, bias = self._mask_segments()
+        kw = dict(B=self.B, H=self.cfg.num_attention_heads, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias)
+        need = ops.attn_mask_workspace_bytes(self.cond_mask, **kw)
+        if self._mask_ws is None or self._mask_ws.numel() < need:
+            self._mask_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        ops.attn_mask_prep(self.cond_mask, self._mask_ws, **kw)
+
     # --------------------------------------------------------------------------------- step-invariant part
     def set_conditioning(self, prompt_embeds, pooled, guidance, txt_ids, img_ids, condition_latents=None,
                          condition_ids=None, c_t: float = 0.0, model_config: Optional[Dict] = None,
-                         c_factor: Optional[float] = None) -> None:
+                         c_factor: Optional[float] = None, attention_mask: Optional[torch.Tensor] = None) -> None:
+        """attention_mask: what attn_forward takes (rank 2..4, broadcastable to [1|B, 1|H, 1|S, S] over [text | image | condition], bool or
+        additive float, on the device), for every attention launch of the forwards of this conditioning. Used under the reference's rules
+        only (user_mask); refused in precise and attn_fp8 modes. A call that raises leaves the engine without a mask and unconditioned."""
         cfg, w, dev = self.cfg, self.w, self.device
         B, T = prompt_embeds.shape[0], prompt_embeds.shape[1]
         N = img_ids.shape[0]
         C = 0 if condition_latents is None else condition_latents.shape[1]
+        self.cond_mask, self.cond_ready = None, False
+        mask = None
+        if attention_mask is not None:
+            mask_argument(attention_mask)
+            refuse_masked_modes(model_config, self.precise_default)
+            mask = self.user_mask(attention_mask, B, T + N + C, C, model_config, c_factor)
         self.setup(B, T, N, C)
         self.gemm_ws()                   # allocated here, outside any stream capture
         self.model_config = dict(model_config or {})
@@ -552,6 +623,9 @@ class DiTEngine:
             self._compute_mods(self.cond_temb, self.cmods, lora=True)
         self.attn_bias = self._attn_bias()
         self._setup_nomax()
+        if mask is not None:
+            self.cond_mask = mask
+            self._prep_cond_mask()
         self.cond_ready = True
         self.cond_cached = False          # a new condition stream: the per-layer key / value images are stale
         self.sched = None
@@ -745,17 +819,20 @@ class DiTEngine:
             okw["qseg_mask"] = 1 << [s for s, _ in streams].index("img")
         if self.f16:
             flags |= ops.ATTN_O_F16
-        if self.attn_mask is not None:
-            # the caller's mask (lx_attn_fwd_masked): always a running maximum -- BOUNDED / INVARIANT do not apply to it
+        # the caller's mask: a block-level call's (prepared inside the call) or the conditioning's (prepared by set_conditioning)
+        mask, mask_ws = (self.attn_mask, None) if self.attn_mask is not None else (self.cond_mask, self._mask_ws)
+        if mask is not None:
+            # lx_attn_fwd_masked: always a running maximum -- BOUNDED / INVARIANT do not apply to it
             if self.model_config.get("attn_fp8", False):
                 raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
-            if cached or img_only:
-                raise NotImplementedError("attention_mask is supported on block-level attention calls only")
+            if cached:        # (unreachable through the public surface: condition caching exists only under rules that replace the mask)
+                raise NotImplementedError("attention_mask is not supported on condition-cached forwards")
             if not prepped:
                 ops.qkv_prep_segs(Y, 2 * D, 0, D, qsegs, B, H, self.VT, in_f16=self.f16)
             mflags = (ops.ATTN_Q_LOG2 if self._layer_nomax(wq) else 0) | (ops.ATTN_O_F16 if self.f16 else 0)
-            ops.attn_fwd_masked(Y, Y, self.VT, Y, self.attn_mask, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
-                                seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, flags=mflags, **({"f16_ovf": self.f16_ovf} if self.f16 else {}))
+            ops.attn_fwd_masked(Y, Y, self.VT, Y, mask, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
+                                seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, flags=mflags, workspace=mask_ws, prepped=mask_ws is not None,
+                                **okw)
             return
         if self.model_config.get("attn_fp8", False):
             # opt-in fp8 (e4m3) attention (BASELINE configs[4]): q / k / v^T go to byte images, both attention products run on
@@ -1234,10 +1311,14 @@ class DiTEngine:
         key = (self.shape, tuple(sorted(self.model_config.items())), self.c_factor, pre, self.pair_plan, self.precise, self.gemm_fp8, self.f16,
                getattr(self.w, "q_log2_version", 0),      # (a weight broadcast refreshes the scaled norm_q tensors and the per-layer bounds)
                getattr(self.w, "weights_version", 0),     # (... and moves this one unconditionally: dist.broadcast_packed_weights)
-               self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, getattr(self, "_w16_gen", 0) if self.f16 else 0)
+               self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, getattr(self, "_w16_gen", 0) if self.f16 else 0,
+               # the masked launches hold the workspace's address and the mask's tile geometry (dtype, broadcast dims), never the mask itself:
+               # a new mask of the same form is a new prep into the same workspace (set_conditioning), which the same graph then reads
+               None if self.cond_mask is None else (self._mask_ws.data_ptr(), self.cond_mask.dtype, tuple(self.cond_mask.shape[:3])))
         g = self.graphs.get(key)
         if g is None:
-            mode = (self.precise, self.gemm_fp8, self.f16, bool(self.model_config.get("attn_fp8", False)), self.latent_lora, self.C > 0, skip)
+            mode = (self.precise, self.gemm_fp8, self.f16, bool(self.model_config.get("attn_fp8", False)), self.latent_lora, self.C > 0, skip,
+                    None if self.cond_mask is None else self.cond_mask.dtype == torch.bool)      # (the bit and the bias form of the masked kernel)
             self.cond_skip = skip
             try:
                 if mode not in self._warmed:                          # lazy code-object loads / buffer allocations must not happen inside capture
@@ -1314,6 +1395,7 @@ class DiTEngine:
         self.setup(B, T, N, C)
         self.gemm_ws()
         self.graphs = {}
+        self.cond_mask = None                                      # (a conditioning's mask does not outlive it; block-level calls bring their own)
         self.cond_cache = self.cond_cached = False                # block-level use: every call computes all three streams
         self.model_config = dict(model_config or {})
         self.c_factor = c_factor

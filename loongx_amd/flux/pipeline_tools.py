@@ -25,3 +25,19 @@ def prepare_text_input(pipeline, prompts, max_sequence_length: int = 512):
     return pipeline.encode_prompt(prompt=prompts, prompt_2=None, prompt_embeds=None, pooled_prompt_embeds=None,
                                   device=pipeline.device, num_images_per_prompt=1, max_sequence_length=max_sequence_length,
                                   lora_scale=None)
+
+
+def text_padding_mask(lengths, T: int, N: int, C: int = 0) -> torch.Tensor:
+    """Key-padding attention_mask for prompts padded to T tokens: bool [B, 1, 1, T + N + C] over the concatenated
+    [text | image | condition] sequence, False on the text keys t >= lengths[b] and True everywhere else (image and condition keys
+    included). Hand it to tranformer_forward / generate as attention_mask (on the transformer's device): the padded keys leave every
+    softmax, and 64-key tiles that hold padding only are never staged or multiplied. Pure torch; the result lives on `lengths`' device
+    (the CPU for a list)."""
+    lengths = torch.as_tensor(lengths, dtype=torch.long).reshape(-1)
+    if T < 0 or N < 0 or C < 0:
+        raise ValueError(f"text_padding_mask: negative length (T={T}, N={N}, C={C})")
+    if lengths.numel() and (int(lengths.min()) < 0 or int(lengths.max()) > T):
+        raise ValueError(f"text_padding_mask: lengths must lie in [0, T={T}]")
+    m = torch.ones(lengths.numel(), 1, 1, T + N + C, dtype=torch.bool, device=lengths.device)
+    m[:, 0, 0, :T] = torch.arange(T, device=lengths.device)[None, :] < lengths[:, None]
+    return m

@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 import torch
 
 from .block import LxBlock
-from .engine import DiTEngine
+from .engine import DiTEngine, mask_argument
 from .weights import FluxConfig, PackedWeights, pack_state_dict, synthetic_weights
 
 
@@ -62,6 +62,7 @@ class LxFluxTransformer:
         """Forget the step-invariant conditioning cache (generate() calls this at the start and end of every image)."""
         self._cond_key = self._cond_refs = None
         self.engine.cond_ready = False
+        self.engine.cond_mask = None
         self.engine.sched = None
 
     @classmethod
@@ -95,12 +96,41 @@ def _tkey(t: Optional[torch.Tensor]):
     return None if t is None else (t.data_ptr(), tuple(t.shape), t.dtype, t._version)
 
 
+def _mkey(m: Optional[torch.Tensor]):
+    """_tkey of an attention mask: its strides too (a transposed view of the same storage is another mask)"""
+    return None if m is None else (id(m),) + _tkey(m) + (tuple(m.stride()),)
+
+
+def _mask_of(joint_attention_kwargs: Optional[Dict[str, Any]], attention_mask):
+    """The one attention_mask of a call: the `attention_mask=` keyword or joint_attention_kwargs["attention_mask"] (diffusers' slot for
+    attention-processor arguments, which the reference threads through to attn_forward), not both."""
+    jm = (joint_attention_kwargs or {}).get("attention_mask")
+    if jm is not None and attention_mask is not None:
+        raise ValueError('attention_mask given twice: as a keyword and in joint_attention_kwargs["attention_mask"]')
+    mask = jm if jm is not None else attention_mask
+    if mask is not None:
+        mask_argument(mask)
+    return mask
+
+
 def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.Tensor, condition_ids: torch.Tensor,
-                       condition_type_ids: torch.Tensor, model_config: Optional[Dict[str, Any]] = {}, c_t=0, **params):
+                       condition_type_ids: torch.Tensor, model_config: Optional[Dict[str, Any]] = {}, c_t=0,
+                       attention_mask: Optional[torch.Tensor] = None, **params):
     """One velocity prediction. Same keyword surface as the reference (prepare_params); `condition_type_ids` is
-    accepted and ignored exactly as in the reference (transformer.py:133 is commented out there)."""
+    accepted and ignored exactly as in the reference (transformer.py:133 is commented out there).
+    attention_mask (or joint_attention_kwargs["attention_mask"]; giving both is a ValueError): what attn_forward takes -- SDPA's attn_mask
+    over the concatenated [text | image | condition] sequence of length S, bool (True = attend) or additive float, broadcastable as
+    [1|B, 1|H, 1|S, S] (rank 2..4), on the device -- applied in all attention launches of the forward. Per image: B is the batch of
+    hidden_states. Used under the reference's rules only (union_cond_attn, no independent_condition, no c_factor: block.py:106-128);
+    otherwise the reference's own mask replaces it. precise and attn_fp8 modes raise NotImplementedError."""
     (hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
      joint_attention_kwargs, controlnet_block_samples, controlnet_single_block_samples, return_dict) = prepare_params(**params)
+    try:
+        attention_mask = _mask_of(joint_attention_kwargs, attention_mask)
+    except (ValueError, NotImplementedError):
+        if transformer is not None:
+            transformer.invalidate_conditioning()          # a refused call leaves no mask (nor the conditioning it belonged to) behind
+        raise
     if controlnet_block_samples is not None or controlnet_single_block_samples is not None:
         raise NotImplementedError("controlnet residuals are not part of the LoongX path (unused hooks at transformer.py:173-181,231-239)")
     eng = transformer.engine
@@ -116,14 +146,17 @@ def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.
     mc = dict(model_config or {})
     key = (_tkey(encoder_hidden_states), _tkey(pooled_projections), _tkey(guidance), _tkey(txt_ids), _tkey(img_ids),
            _tkey(condition_latents), _tkey(condition_ids), float(c_t), tuple(sorted(mc.items())), transformer.c_factor,
-           hidden_states.shape[0], getattr(eng.w, "weights_version", 0), getattr(eng.w, "lora_version", 0))      # (a weight broadcast or a new
-    # adapter after the conditioning: the cached embedder outputs and modulations were computed from the old weights)
+           hidden_states.shape[0], getattr(eng.w, "weights_version", 0), getattr(eng.w, "lora_version", 0),      # (a weight broadcast or a new
+           # adapter after the conditioning: the cached embedder outputs and modulations were computed from the old weights)
+           _mkey(attention_mask))           # (the mask is prepared once per conditioning: a changed mask must never meet a stale prep)
     if key != transformer._cond_key or not eng.cond_ready:
+        transformer._cond_key = transformer._cond_refs = None          # (a conditioning that raises leaves none behind)
         eng.set_conditioning(encoder_hidden_states, pooled_projections, guidance, txt_ids, img_ids,
                              condition_latents if use_condition else None, condition_ids if use_condition else None,
-                             c_t=float(c_t), model_config=mc, c_factor=transformer.c_factor)
+                             c_t=float(c_t), model_config=mc, c_factor=transformer.c_factor, attention_mask=attention_mask)
         transformer._cond_key = key
-        transformer._cond_refs = (encoder_hidden_states, pooled_projections, guidance, txt_ids, img_ids, condition_latents, condition_ids)
+        transformer._cond_refs = (encoder_hidden_states, pooled_projections, guidance, txt_ids, img_ids, condition_latents, condition_ids,
+                                  attention_mask)
     # Extension (the reference swallows unknown kwargs): lx_schedule=(i, timesteps) tells the engine that `timestep` is entry
     # i of a known schedule (same units as `timestep`), so all steps' modulation vectors come from one weight pass.
     step_index = None

@@ -417,12 +417,18 @@ def _seg_desc(B, H, seg_len, seg_vt0, bias) -> AttnDesc:
     return d
 
 
-def attn_mask_workspace(mask, *, B, H, seg_len, seg_vt0, bias=None, device=None) -> torch.Tensor:
-    """A workspace (uint8 tensor) of the size lx_attn_mask_workspace asks for this mask shape / dtype and these segments."""
+def attn_mask_workspace_bytes(mask, *, B, H, seg_len, seg_vt0, bias=None) -> int:
+    """The bytes lx_attn_mask_workspace asks for this mask shape / dtype and these segments."""
     d, m = _seg_desc(B, H, seg_len, seg_vt0, bias), _mask_desc(mask, None)
     n = C.c_size_t(0)
     check(lib.lx_attn_mask_workspace(C.byref(d), C.byref(m), C.byref(n)), "lx_attn_mask_workspace")
-    return torch.empty(max(n.value, 1), dtype=torch.uint8, device=device if device is not None else mask.device)
+    return int(n.value)
+
+
+def attn_mask_workspace(mask, *, B, H, seg_len, seg_vt0, bias=None, device=None) -> torch.Tensor:
+    """A workspace (uint8 tensor) of that size."""
+    n = attn_mask_workspace_bytes(mask, B=B, H=H, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias)
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=device if device is not None else mask.device)
 
 
 def attn_mask_prep(mask, workspace, *, B, H, seg_len, seg_vt0, bias=None) -> None:
@@ -433,20 +439,21 @@ def attn_mask_prep(mask, workspace, *, B, H, seg_len, seg_vt0, bias=None) -> Non
 
 
 def attn_fwd_masked(Q, K, VT, O, mask, *, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias=None, scale=None, flags=0,
-                    f16_ovf=None, workspace=None, prepped=False) -> torch.Tensor:
+                    f16_ovf=None, workspace=None, prepped=False, n_qseg=0, qseg_mask=0) -> torch.Tensor:
     """attn_fwd under a per-(query, key) mask over the concatenated segments (SDPA's attn_mask: bool = attend, float = additive,
-    -inf masks); flags: 0 | ATTN_Q_LOG2 | ATTN_O_F16. Runs lx_attn_mask_prep first unless `prepped` (the workspace then holds what an
-    attn_mask_prep of the same mask wrote). Returns the workspace."""
+    -inf masks); flags: 0 | ATTN_Q_LOG2 | ATTN_O_F16; n_qseg / qseg_mask as in attn_fwd (the mask still spans every segment). Runs
+    lx_attn_mask_prep first unless `prepped` (the workspace then holds what an attn_mask_prep of the same mask wrote). Returns the
+    workspace."""
     if workspace is None:
         workspace = attn_mask_workspace(mask, B=B, H=H, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, device=Q.device)
     d = _attn_desc(Q, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
-    d.flags, d.f16_ovf = flags, _p(f16_ovf)
+    d.flags, d.f16_ovf, d.n_qseg, d.qseg_mask = flags, _p(f16_ovf), n_qseg, qseg_mask
     m = _mask_desc(mask, workspace)
     if not prepped:
         check(lib.lx_attn_mask_prep(C.byref(d), C.byref(m), _stream()), "lx_attn_mask_prep")
     if TIMER is not None and TIMER.active:
         S = sum(seg_len)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * S * S * 128)
+        s, e = TIMER.bracket("attn", 4.0 * B * H * _q_rows(seg_len, n_qseg, qseg_mask) * S * 128)
         s.record()
         check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked")
         e.record()
