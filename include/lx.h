@@ -67,6 +67,7 @@ int lx_device_arch(char* name, size_t n);
  *   acc += sum_r lora_t[m, toff + r] * lora_up[n, r],  toff = lora_r * min(n / lora_mod_cols, lora_toff_max)
  * i.e. y = x W^T + s * (x A^T) B^T evaluated in fp32, with lora_t = x A^T from lx_lora_down and
  * lora_up = s*B.  The image stream passes lora_t = NULL (enable_lora scales the adapter to 0).
+ * 1 <= lora_r <= 64 with bf16 / fp16 operands (<= 16 in the split-bf16 mode, <= 4 with e4m3 operands).
  * ------------------------------------------------------------------------------------------------ */
 enum {
   LX_EPI_STORE_BF16 = 0, /* C(bf16)  = act(acc + bias)                      */
@@ -200,7 +201,8 @@ enum { LX_GEMM_PLAN_NONE = 0, LX_GEMM_PLAN_8WAVE_256 = 1, LX_GEMM_PLAN_8WAVE_128
        LX_GEMM_PLAN_G4 = 5, LX_GEMM_PLAN_G4_SPLIT2 = 6, LX_GEMM_PLAN_G4_SPLIT3 = 7 };
 int lx_gemm_last_plan(void);
 
-/* LoRA down-projection (peft lora_A): T_s[M, R] (fp32, ldt) = X[M, K_s] (bf16, ldx) . Adown[R, K_s]^T (bf16), R <= 16,
+/* LoRA down-projection (peft lora_A): T_s[M, R] (fp32, ldt) = X[M, K_s] (bf16, ldx) . Adown[R, K_s]^T (bf16), R <= 256
+ * (R <= 16: one workgroup per 16 rows and slab; 16 < R <= 256: one per 16 rows, slab and 64 columns of T; same contract),
  * for n_split contiguous K slices s (n_split = 1: the whole K); slab s is written at T + s*split_stride. Splitting K
  * spreads a tall-skinny product over the whole chip without atomics; the consumer (lx_gemm_bf16) adds the slabs. */
 int lx_lora_down(const void* X, int ldx, const void* Adown, float* T, int ldt, int M, int K, int R, int n_split,

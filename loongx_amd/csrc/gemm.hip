@@ -162,7 +162,9 @@ extern "C" int lx_gemm_bf16_ws(const lx_gemm_desc* problems, int n, void* worksp
     if (p.epilogue & LX_W_TILED) LX_CHECK_ARG(p.N % BN == 0 && p.ldw == (segs == 3 ? 2 * p.K : p.K), "lx_gemm_bf16[%d]: LX_W_TILED needs N %% 256 == 0 and ldw == K (2K with k_segs = 3)", i);
     if (p.gate) LX_CHECK_ARG(p.gate_ld >= p.N && p.gate_ld % 4 == 0, "lx_gemm_bf16[%d]: gate_ld=%d", i, p.gate_ld);
     if (p.lora_t) {
-      LX_CHECK_ARG(p.lora_up && p.lora_r >= 1 && p.lora_r <= 16, "lx_gemm_bf16[%d]: LoRA needs lora_up and 1 <= r <= 16", i);
+      LX_CHECK_ARG(p.lora_up && p.lora_r >= 1 && p.lora_r <= 64, "lx_gemm_bf16[%d]: LoRA needs lora_up and 1 <= r <= 64", i);
+      // 16 < r <= 64: the bf16 / fp16 8-wave kernels (their epilogue walks the ranks four at a time); the split-bf16 mode keeps r <= 16
+      LX_CHECK_ARG(p.lora_r <= 16 || !(segs > 1 || (p.epilogue & LX_EPI_SPLIT_BF16)), "lx_gemm_bf16[%d]: the split-bf16 mode applies LoRA of rank <= 16 (r=%d)", i, p.lora_r);
       LX_CHECK_ARG(p.lora_mod_cols <= 0 || p.lora_mod_cols % BN == 0, "lx_gemm_bf16[%d]: lora_mod_cols must be a multiple of %d", i, BN);
     }
     if (p.epilogue & LX_EPI_QKV) {

@@ -501,7 +501,8 @@ __global__ __launch_bounds__(256) void qkv_prep_fp8_kernel(const uint16_t* __res
 }
 
 // ------------------------------------------------------------------------------------------------------
-// LoRA down-projection: T[M,R<=16] = X[M,K] . A[R,K]^T (bf16 in, fp32 out) on v_mfma_f32_16x16x32_bf16.
+// LoRA down-projection: T[M,R] = X[M,K] . A[R,K]^T (bf16 in, fp32 out) on v_mfma_f32_16x16x32_bf16. R <= 16: this kernel;
+// 16 < R <= 256: lora_down_wide_kernel below.
 // Workgroup = 8 waves = 16 rows; the waves split K eight ways and reduce through LDS. A is the MFMA "A"
 // operand (rows = r), X the "B" operand (cols = m): each lane ends with 4 consecutive r of one row m.
 // ------------------------------------------------------------------------------------------------------
@@ -574,6 +575,76 @@ __global__ __launch_bounds__(512) void lora_down_mfma_kernel(const LoraTerms ter
       if (r0 + 4 <= R && (ldt & 3) == 0) *(f32x4*)tp = acc;
       else
         for (int j = 0; j < 4 && r0 + j < R; ++j) tp[j] = acc[j];
+    }
+  }
+}
+
+// Wide form, 16 < R <= 256 (adapters of rank > 4 behind a fused GEMM: up to four modules x rank 64): the same MFMA, operand roles and
+// K-split slab contract, with blockIdx.z = a chunk of 64 r. A wave keeps up to four 16-r accumulators, so an X fragment is loaded
+// once per 64 r, and the eight waves split the slab's K as above. Grid = (M / 16, n_split, R / 64): with the engine's four slabs
+// that is one workgroup per CU at M = 1024, R = 64 (256 workgroups), and R / 64 times as many for the fused single-block adapters.
+// Slabs are plain stores summed by the consumer in slab order; the waves' partial sums are added in wave order: no atomics.
+template <bool F16>
+__global__ __launch_bounds__(512) void lora_down_wide_kernel(const uint16_t* __restrict__ X, int ldx, const uint16_t* __restrict__ A,
+                                                             float* __restrict__ T, int ldt, int M, int K, int R, int Ks, int split_stride) {
+  __shared__ f32x4 red[8][4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m0 = blockIdx.x * 16, rz0 = blockIdx.z * 64;
+  const int nt = min(4, (R - rz0 + 15) / 16);                    // 16-r tiles of this chunk (workgroup-uniform)
+  const int kbeg = blockIdx.y * Ks, kend = min(K, kbeg + Ks);
+  T += (size_t)blockIdx.y * split_stride;
+  const int l15 = lane & 15, kq = lane >> 4;
+  const uint16_t* xp = X + (size_t)min(m0 + l15, M - 1) * ldx + kq * 8;
+  const uint16_t* ap[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) ap[t] = A + (size_t)min(rz0 + t * 16 + l15, R - 1) * K + kq * 8;
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // as in lora_down_mfma_kernel: a batch's loads are all issued before its first MFMA, slots past the end carry zero fragments
+  int k = kbeg + wave * 32;
+  const bf16x8 zero = {};
+  auto batch = [&](auto n_) {
+    constexpr int NS = decltype(n_)::value;
+    bf16x8 af[NS][4], xf[NS];
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+      const bool in = k + u * 256 < kend;
+      xf[u] = in ? *(const bf16x8*)(xp + k + u * 256) : zero;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) af[u][t] = (in && t < nt) ? *(const bf16x8*)(ap[t] + k + u * 256) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (t < nt) {
+          if constexpr (F16) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[u][t]), __builtin_bit_cast(f16x8, xf[u]), acc[t], 0, 0, 0);
+          else acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u][t], xf[u], acc[t], 0, 0, 0);
+        }
+    k += NS * 256;
+  };
+  const int nsteps = k < kend ? (kend - k + 255) / 256 : 0;      // (wave-uniform)
+  if (nsteps <= 4) batch(std::integral_constant<int, 4>{});
+  else
+    while (k < kend) batch(std::integral_constant<int, 8>{});
+#pragma unroll
+  for (int t = 0; t < 4; ++t) red[wave][t][lane] = acc[t];
+  __syncthreads();
+  if (wave < nt) {                                               // wave t finishes tile t
+    f32x4 s = red[0][wave][lane];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) {
+      const f32x4 o = red[w][wave][lane];
+      s[0] += o[0]; s[1] += o[1]; s[2] += o[2]; s[3] += o[3];
+    }
+    // s[j]: r = rz0 + 16*wave + 4*kq + j, m = m0 + l15
+    const int m = m0 + l15, r0 = rz0 + 16 * wave + 4 * kq;
+    if (m < M && r0 < R) {
+      float* tp = T + (size_t)m * ldt + r0;
+      if (r0 + 4 <= R && (ldt & 3) == 0) *(f32x4*)tp = s;
+      else
+        for (int j = 0; j < 4 && r0 + j < R; ++j) tp[j] = s[j];
     }
   }
 }
@@ -883,12 +954,19 @@ extern "C" int lx_qkv_prep_fp8_f16in_segs(const void* QKV, int ld, int q_col, in
 static int lora_down_launch(const char* name, bool f16, const void* X, int ldx, const void* Adown, float* T, int ldt, int M, int K, int R, int n_split,
                             int split_stride, void* stream) {
   LX_CHECK_ARG(X && Adown && T && M > 0, "%s: NULL operand", name);
-  LX_CHECK_ARG(R >= 1 && R <= 16, "%s: R=%d must be in [1,16]", name, R);
+  LX_CHECK_ARG(R >= 1 && R <= 256, "%s: R=%d must be in [1,256]", name, R);
   LX_CHECK_ARG(K % 32 == 0 && ldx % 8 == 0 && ldt >= R, "%s: K %% 32, ldx %% 8 and ldt >= R required (K=%d)", name, K);
   LX_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Adown & 15) == 0 && ((uintptr_t)T & 15) == 0, "%s: operands must be 16-byte aligned", name);
   LX_CHECK_ARG(n_split >= 1 && n_split <= 16 && (n_split == 1 || split_stride >= (M - 1) * ldt + R) && split_stride % 4 == 0,
                "%s: bad n_split=%d / split_stride=%d", name, n_split, split_stride);
   const int Ks = ((K / 32 + n_split - 1) / n_split) * 32;
+  if (R > 16) {                      // the wide form: 64 r per workgroup
+    const dim3 grid((M + 15) / 16, n_split, (R + 63) / 64);
+    if (f16) hipLaunchKernelGGL(lora_down_wide_kernel<true>, grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)X, ldx, (const uint16_t*)Adown, T, ldt, M, K, R, Ks, split_stride);
+    else hipLaunchKernelGGL(lora_down_wide_kernel<false>, grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)X, ldx, (const uint16_t*)Adown, T, ldt, M, K, R, Ks, split_stride);
+    LX_LAUNCH_CHECK(name);
+    return LX_OK;
+  }
   LoraTerms lt = {};
   lt.X[0] = (const uint16_t*)X; lt.A[0] = (const uint16_t*)Adown; lt.ldx[0] = ldx; lt.n = 0;
   if (f16) hipLaunchKernelGGL(lora_down_mfma_kernel<true>, dim3((M + 15) / 16, n_split), dim3(512), 0, (hipStream_t)stream, lt, T, ldt, M, K, R, Ks, split_stride);

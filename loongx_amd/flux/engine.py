@@ -47,6 +47,18 @@ def refuse_masked_modes(model_config: Optional[Dict], precise_default: bool) -> 
         raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
 
 
+def refuse_wide_lora_modes(w: PackedWeights, model_config: Optional[Dict], precise_default: bool) -> None:
+    """The arithmetic modes whose kernels evaluate adapters from one 16-column down-projection slab only."""
+    wide = max([lo.down.shape[0] for lo in w.lora.values()] + [0])
+    if wide <= 16:
+        return
+    mc = model_config or {}
+    for mode, on in (("precise", bool(mc.get("precise", precise_default))), ("gemm_fp8", bool(mc.get("gemm_fp8", False)))):
+        if on:
+            raise ValueError(f"LoRA rank {w.cfg.lora_r} is not supported in {mode} mode ({wide} adapter columns behind one GEMM; that "
+                             "mode takes at most 16): use the bf16 or fp16 operand mode")
+
+
 class DiTEngine:
     def __init__(self, weights: PackedWeights, device="cuda"):
         self.w = weights
@@ -118,9 +130,13 @@ class DiTEngine:
 
     # ------------------------------------------------------------------------------------------ workspace
     def setup(self, B: int, T: int, N: int, C: int) -> None:
-        if self.shape == (B, T, N, C):
-            return
         cfg, dev = self.cfg, self.device
+        # slab width of the LoRA scratch: the widest down-projection of the adapter set (the fused single-block GEMM's four modules x
+        # rank), 16 for the ranks that fit lx_lora_down's narrow form. (A wider adapter set re-allocates even where its installer left
+        # `shape` alone: the slabs are written by kernels.)
+        tl_w = (max([16, cfg.lora_r] + [lo.down.shape[0] for lo in self.w.lora.values()]) + 3) // 4 * 4
+        if self.shape == (B, T, N, C) and self.TLs.shape[2] >= tl_w and self.tmod.shape[1] >= (cfg.num_layers + cfg.num_single_layers) * cfg.lora_r:
+            return
         D, H = cfg.inner_dim, cfg.num_attention_heads
         self.B, self.T, self.N, self.C = B, T, N, C
         self.r_txt, self.r_img, self.r_cond = 0, B * T, B * (T + N)
@@ -137,7 +153,7 @@ class DiTEngine:
         self.TL_SPLIT = 4                 # K-split slabs of the LoRA down-projection: 35.50 ms per step against 35.72 with 2 and 36.12 with 1
                                           # (tools/ab_engine_attr.py TL_SPLIT 4 2, round 5; lx_gemm4_kernel sums at most four slabs)
         # precise mode writes one slab per cross term (up to 3: hi.A, lo.A, hi.A_lo) whatever the K-split of the bf16 path is
-        self.TLs = torch.zeros(max(self.TL_SPLIT, 3), M, 16, dtype=f32, device=dev)
+        self.TLs = torch.zeros(max(self.TL_SPLIT, 3), M, tl_w, dtype=f32, device=dev)
         self.TL = self.TLs[0]
         self.lat16 = torch.zeros(B * N, cfg.in_channels, dtype=bf16, device=dev)
         self.lat16h = self.lat16.view(torch.float16)
@@ -554,6 +570,7 @@ class DiTEngine:
         N = img_ids.shape[0]
         C = 0 if condition_latents is None else condition_latents.shape[1]
         self.cond_mask, self.cond_ready = None, False
+        refuse_wide_lora_modes(w, model_config, self.precise_default)
         mask = None
         if attention_mask is not None:
             mask_argument(attention_mask)

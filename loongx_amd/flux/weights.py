@@ -124,10 +124,15 @@ class PackedWeights:
         return n
 
 
-def _check_lora_ranks(cfg: FluxConfig, ranks: Dict[str, int], group_sizes: Dict[str, int]) -> None:
-    """One rank r for every adapter of a checkpoint, and r * (modules fused into one GEMM) <= 16: lx_lora_down produces at most
-    16 columns per launch (the TL slabs of the engine are 16 columns wide) and the fused single-block GEMM evaluates four
-    adapters (to_k, to_v, to_q, proj_mlp) from one slab. Sets cfg.lora_r, which sizes the engine's modulation scratch."""
+LORA_MAX_RANK = 64                  # per module, bf16 / fp16 operand modes (lx_lora_down's wide form: 4 modules x 64 = 256 columns)
+
+
+def _check_lora_ranks(cfg: FluxConfig, ranks: Dict[str, int], group_sizes: Dict[str, int], precise: bool = False) -> None:
+    """One rank r for every adapter of a checkpoint. Accepted: r * (modules fused into one GEMM) <= 16 (any r: one 16-column slab of
+    lx_lora_down serves the launch, in every mode -- the fused single-block GEMM evaluates four adapters, to_k, to_v, to_q and
+    proj_mlp, from one slab, so r <= 4 there), or an even r <= 64 (the wide down-projection and the 8-wave GEMMs' rank walk, bf16 and
+    fp16 operand modes only: refused for weights packed for precise mode here, and by set_conditioning under gemm_fp8).
+    Sets cfg.lora_r, which sizes the engine's adapter scratch."""
     if not ranks:
         return
     rs = sorted(set(ranks.values()))
@@ -135,10 +140,14 @@ def _check_lora_ranks(cfg: FluxConfig, ranks: Dict[str, int], group_sizes: Dict[
         bad = {k: v for k, v in ranks.items() if v != rs[0]}
         raise ValueError(f"LoRA adapters must share one rank; found ranks {rs} (e.g. {list(bad.items())[:3]})")
     r = rs[0]
-    for name, n in group_sizes.items():
-        if n * r > 16:
-            raise ValueError(f"LoRA rank {r} is too large for the fused GEMM '{name}' ({n} adapters share one down-projection "
-                             f"launch: needs {n} * r <= 16, i.e. r <= {16 // n})")
+    name, n = max(group_sizes.items(), key=lambda kv: kv[1]) if group_sizes else ("", 1)
+    if n * r > 16:                     # more than one 16-column slab
+        if precise:
+            raise ValueError(f"LoRA rank {r} is too large for precise mode: the fused GEMM '{name}' evaluates {n} adapters from one "
+                             f"16-column down-projection there (r <= {16 // n}); pack without precise=True for ranks up to {LORA_MAX_RANK}")
+        if r > LORA_MAX_RANK or r % 2:
+            raise ValueError(f"LoRA rank {r} is not supported: the fused GEMM '{name}' evaluates {n} adapters, which takes "
+                             f"r <= {16 // n} or an even r <= {LORA_MAX_RANK}")
     cfg.lora_r = r
 
 
@@ -263,7 +272,7 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: FluxConfig, device, lora_s
     for e in emb:
         for l in ("linear_1", "linear_2"):
             put(f"tte.{e}.{l}", [f"time_text_embed.{e}.{l}"], [D])
-    _check_lora_ranks(cfg, ranks, groups)
+    _check_lora_ranks(cfg, ranks, groups, precise=bool(precise))
     return pw
 
 
@@ -350,7 +359,7 @@ def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale
         raise KeyError(f"LoRA keys that match no module of this transformer: {unknown[:4]}{' ...' if len(unknown) > 4 else ''}")
     if n == 0:
         raise ValueError("no LoRA adapter found in the state dict")
-    _check_lora_ranks(pw.cfg, ranks, groups)
+    _check_lora_ranks(pw.cfg, ranks, groups, precise=pw.precise_ready)
     pw.lora.clear()
     pw.lora.update(new_lora)
     for k in [k for k in pw.t if k.startswith("mod.lora_")]:
