@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -30,6 +30,44 @@ NEG_INF = float("-inf")
 
 def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+class Stream(NamedTuple):
+    """One token stream of the stream-major layout (DiTEngine.streams, built by setup())."""
+    name: str                # "txt" | "img" | "cond"
+    len: int                 # tokens per sample
+    row0: int                # first row of X / XN / Y
+    vt0: int                 # first slot of a V^T row
+    mods: torch.Tensor       # its modulation vectors: the step's (mods) or the conditioning's (cmods)
+
+
+class HostWord:
+    """One int32 device word watched from the host without a synchronisation: a pinned host word and an event. take() gives the value
+    a previous request() copied, once that copy has landed; request() enqueues the next copy unless one is in flight. So a value
+    surfaces at most one call late."""
+
+    def __init__(self):
+        self.host: Optional[torch.Tensor] = None
+        self.event = None
+
+    def take(self) -> Optional[int]:
+        if self.event is None or not self.event.query():
+            return None
+        self.event = None
+        return int(self.host[0])
+
+    def request(self, word: torch.Tensor) -> None:
+        if self.event is not None:
+            return
+        if self.host is None:
+            self.host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.host.copy_(word, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+
+    def drop(self) -> None:
+        """Forget a copy in flight (what it would report has been reported, or reset, otherwise)."""
+        self.event = None
 
 
 def mask_argument(attention_mask) -> None:
@@ -71,7 +109,6 @@ class DiTEngine:
         self.sched = None
         self.graphs: Dict = {}
         self._warmed = set()             # kernel sets (modes) that have run eagerly once: first launches must not happen inside a capture
-        import os
         self.use_graph = os.environ.get("LX_GRAPH", "1") != "0"
         # The projection launches normalise / rotate k and q and write V^T in their epilogue (LX_EPI_QKV) wherever the shapes allow it
         # (_rope_pairs decides); False forces the separate lx_qkv_prep pass everywhere (tests compare the two).
@@ -81,6 +118,9 @@ class DiTEngine:
         self.ln_lora = True
         self.model_config: Dict = {}
         self.c_factor: Optional[float] = None
+        self.latent_lora = False
+        self.attn_bias: Dict[str, Dict[str, float]] = {}
+        self.cos_main = self.sin_main = self.cos_cond = self.sin_cond = None      # RoPE tables of the conditioning (set_conditioning / configure)
         # A caller's attention_mask, [Bm, Hm, Sq, S] over the concatenated [txt | img | cond] sequence.
         #   attn_mask: block.attn_forward's, set for the duration of one call (the mask is prepared inside every such call);
         #   cond_mask: the conditioning's (set_conditioning(attention_mask=...)): prepared ONCE there into `_mask_ws`, which all 57 attention
@@ -98,7 +138,9 @@ class DiTEngine:
         # fp32 configuration -- split-bf16 MFMA GEMMs (2 or 3 K-segments), fp32 q/k/v, fp32 attention (csrc/precise.hip).
         self.precise_default = False
         self.attn_nomax = False
+        self._nomax_room = 100.0         # what the largest finite attention bias leaves of the bounded kernel's score range (_setup_nomax)
         self.precise = False
+        self.precise_attn_split = False  # decided when the precise buffers are allocated (_setup_precise)
         # fp8 GEMM path (model_config["gemm_fp8"]; BASELINE configs[4]): e4m3 operand images on the 64-deep f8f6f4 MFMA
         self.gemm_fp8 = False
         self.w8: Dict[str, torch.Tensor] = {}          # name -> tiled e4m3 weight / name + ".rs" -> row de-scale, built on first use
@@ -111,8 +153,12 @@ class DiTEngine:
         self.operands_default = "bf16"
         self.f16 = False
         self.w16: Dict[str, torch.Tensor] = {}         # name -> fp16 image of the (tiled) weight / name + ".down" -> fp16 LoRA down-projection
+        self.w16_inexact_share, self.w16_clipped = 0.0, 0
+        self._w16_key, self._w16_gen = None, 0
         self.f16_ovf: Optional[torch.Tensor] = None
+        self._ovf_word, self._ovf_seen = HostWord(), 0         # f16_overflow_poll(sync=False)
         self._gemm_ws: Optional[torch.Tensor] = None
+        self._err_word = HostWord()                            # check_status(sync=False)
         # Step-invariant condition stream (model_config independent_condition / union_cond_attn = False: the condition queries see
         # only condition keys, its timestep c_t is fixed, so its hidden states, keys and values are the same at every denoise step):
         # the first forward after set_conditioning() computes all three streams and leaves the condition keys / V^T of every layer in
@@ -166,6 +212,9 @@ class DiTEngine:
         self.t1000 = torch.zeros(B, dtype=f32, device=dev)
         self.mods = torch.zeros(B, cfg.n_mod, dtype=f32, device=dev)
         self.cmods = torch.zeros(B, cfg.n_mod, dtype=f32, device=dev)
+        self.streams = [Stream("txt", T, self.r_txt, self.vt0["txt"], self.mods), Stream("img", N, self.r_img, self.vt0["img"], self.mods),
+                        Stream("cond", C, self.r_cond, self.vt0["cond"], self.cmods)]
+        self.stream = {s.name: s for s in self.streams}
         nb = cfg.num_layers + cfg.num_single_layers
         self.tmod = torch.zeros(B, max(nb * cfg.lora_r, 4), dtype=f32, device=dev)
         self.X_txt_init = torch.zeros(max(B * T, 1), D, dtype=f32, device=dev)
@@ -232,7 +281,7 @@ class DiTEngine:
         if self.w16 and self._w16_key == key:
             return
         self.w16 = {}
-        self._w16_gen = getattr(self, "_w16_gen", 0) + 1          # part of the step graphs' key: they hold the images' addresses
+        self._w16_gen += 1                                         # part of the step graphs' key: they hold the images' addresses
         stat = torch.zeros(2, dtype=torch.int64, device=self.device)      # [values that lost bits, values clipped]
         total = 0
 
@@ -265,7 +314,8 @@ class DiTEngine:
             return 0
         n = int(self.f16_ovf.item())
         if reset:
-            self._ovf_event, self._ovf_seen = None, 0          # (an asynchronous read still in flight would report what this call reported)
+            self._ovf_word.drop()                              # (an asynchronous read still in flight would report what this call reported)
+            self._ovf_seen = 0
             if n:
                 self.f16_ovf.zero_()
         return n
@@ -281,21 +331,13 @@ class DiTEngine:
         copy, so an event surfaces at most one call late."""
         if not self.f16 or self.f16_ovf is None:
             return 0
-        wclip = int(getattr(self, "w16_clipped", 0))
+        wclip = int(self.w16_clipped)
         if sync:
             return self.f16_overflow_count(reset=True) + wclip
-        if getattr(self, "_ovf_host", None) is None:
-            self._ovf_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._ovf_event, self._ovf_seen = None, 0
-        n = 0
-        if self._ovf_event is not None and self._ovf_event.query():
-            self._ovf_event = None
-            total = int(self._ovf_host[0])
+        n, total = 0, self._ovf_word.take()
+        if total is not None:
             n, self._ovf_seen = max(total - self._ovf_seen, 0), total          # the device counter runs on: nothing is reset behind the kernels' back
-        if self._ovf_event is None:
-            self._ovf_host.copy_(self.f16_ovf, non_blocking=True)
-            self._ovf_event = torch.cuda.Event()
-            self._ovf_event.record()
+        self._ovf_word.request(self.f16_ovf)
         return n + wclip
 
     def set_lora_scale(self, s: float) -> None:
@@ -330,37 +372,36 @@ class DiTEngine:
             try:
                 ops.gemm_workspace_status(self._gemm_ws)      # (resets the flags and the error word when it reports)
             except Exception:
-                self.pair_plan, self.graphs, self._err_event = False, {}, None
+                self.pair_plan, self.graphs = False, {}
+                self._err_word.drop()
                 raise
             return
+        if self._err_word.take():
+            self.check_status(sync=True)              # resets the workspace and raises
         n = self._gemm_ws.numel()
-        if getattr(self, "_err_host", None) is None:
-            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._err_event = None
-        if self._err_event is not None and self._err_event.query():
-            self._err_event = None
-            if int(self._err_host[0]) != 0:
-                self.check_status(sync=True)          # resets the workspace and raises
-        if self._err_event is None:
-            word = self._gemm_ws[n - 64 * 4: n - 63 * 4].view(torch.int32)         # [slots | 256 flags | error word + pad]
-            self._err_host.copy_(word, non_blocking=True)
-            self._err_event = torch.cuda.Event()
-            self._err_event.record()
+        self._err_word.request(self._gemm_ws[n - 64 * 4: n - 63 * 4].view(torch.int32))      # [slots | 256 flags | error word + pad]
 
     # row views ---------------------------------------------------------------------------------------
     def rows(self, buf: torch.Tensor, stream: str) -> torch.Tensor:
-        if stream == "txt":
-            return buf[self.r_txt:self.r_img]
-        if stream == "img":
-            return buf[self.r_img:self.r_cond]
-        return buf[self.r_cond:self.M]
+        s = self.stream[stream]
+        return buf[s.row0:s.row0 + self.B * s.len]
 
-    def _streams(self):
+    def _streams(self) -> List[Stream]:
         """Token streams with rows in this forward (cond_skip: the condition stream's keys / values come from the per-layer cache)."""
-        return [(n, l) for n, l in (("txt", self.T), ("img", self.N), ("cond", 0 if self.cond_skip else self.C)) if l > 0]
+        return [s for s in self.streams if s.len > 0 and not (self.cond_skip and s.name == "cond")]
 
-    def _all_streams(self):
-        return [(n, l) for n, l in (("txt", self.T), ("img", self.N), ("cond", self.C)) if l > 0]
+    def _all_streams(self) -> List[Stream]:
+        return [s for s in self.streams if s.len > 0]
+
+    @staticmethod
+    def _w_rows(W: torch.Tensor, rows: Optional[slice]) -> torch.Tensor:
+        """A row range of a weight image. Row blocks of 256 are contiguous in the tiled image: the slice is a tiled image too."""
+        if rows is None:
+            return W
+        V = W[rows]
+        if getattr(W, "lx_tiled", False):
+            V.lx_tiled = True
+        return V
 
     # ------------------------------------------------------------------------------------------ helpers
     def _lin_skinny(self, x, name, out, act_in=0, act_out=0, accumulate=False):
@@ -460,7 +501,7 @@ class DiTEngine:
         self.attn_nomax = False
         if self.model_config.get("attn_fp8", False) and not self.precise:
             return                                                 # (e4m3 probabilities need the running maximum: their range is 2^17)
-        if (self.precise and not getattr(self, "precise_attn_split", False)) or os.environ.get("LX_ATTN_NOMAX", "1") == "0":
+        if (self.precise and not self.precise_attn_split) or os.environ.get("LX_ATTN_NOMAX", "1") == "0":
             return
         w = self.w
         tab = getattr(w, "q_log2", None)
@@ -539,19 +580,33 @@ class DiTEngine:
                              "over the concatenated [text | image | condition] sequence")
         return m
 
-    def _mask_segments(self):
-        """(seg_len, seg_vt0, bias) of the forward's attention launches, as the mask prep and _attention both describe them"""
-        streams = self._all_streams()
+    def _attn_segments(self, streams: Sequence[Stream], norms=None):
+        """(seg_row0, seg_len, seg_vt0, bias, qsegs) of an attention launch over `streams`, as the mask prep, the q / k / v passes and the
+        attention kernels describe them. bias: the 3x3 (query segment, key segment) table. qsegs, given norms = (wq, wk, wq_txt, wk_txt):
+        per segment (row0, len, vt0, norm_q weight (_qn), norm_k weight, cos, sin), the RoPE tables sliced to the segment's tokens."""
         bias = [[0.0] * 3 for _ in range(3)]
-        for qi, (qs, _) in enumerate(streams):
-            for ki, (ks, _) in enumerate(streams):
-                bias[qi][ki] = self.attn_bias[qs][ks]
-        return [L for _, L in streams], [self.vt0[s] for s, _ in streams], bias
+        for qi, q in enumerate(streams):
+            for ki, k in enumerate(streams):
+                bias[qi][ki] = self.attn_bias[q.name][k.name]
+        return [s.row0 for s in streams], [s.len for s in streams], [s.vt0 for s in streams], bias, self._qsegs(streams, *norms) if norms else []
+
+    def _qsegs(self, streams: Sequence[Stream], wq, wk, wq_txt, wk_txt) -> List:
+        qsegs, off = [], 0
+        for s in streams:
+            if s.name == "cond":
+                cos, sin = self.cos_cond, self.sin_cond
+            elif self.cos_main is None:
+                cos = sin = None
+            else:
+                cos, sin = self.cos_main[off:off + s.len], self.sin_main[off:off + s.len]
+                off += s.len
+            qsegs.append((s.row0, s.len, s.vt0, self._qn(wq_txt if s.name == "txt" else wq, wq), wk_txt if s.name == "txt" else wk, cos, sin))
+        return qsegs
 
     def _prep_cond_mask(self) -> None:
         """ONE lx_attn_mask_prep per conditioning, into an engine-owned workspace (allocated here, outside any stream capture; kept while
         it is large enough, so the step graphs that hold its address stay valid from image to image)."""
-        seg_len, seg_vt0, bias = self._mask_segments()
+        _, seg_len, seg_vt0, bias, _ = self._attn_segments(self._all_streams())
         kw = dict(B=self.B, H=self.cfg.num_attention_heads, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias)
         need = ops.attn_mask_workspace_bytes(self.cond_mask, **kw)
         if self._mask_ws is None or self._mask_ws.numel() < need:
@@ -578,42 +633,15 @@ class DiTEngine:
             mask = self.user_mask(attention_mask, B, T + N + C, C, model_config, c_factor)
         self.setup(B, T, N, C)
         self.gemm_ws()                   # allocated here, outside any stream capture
-        self.model_config = dict(model_config or {})
-        self.c_factor = c_factor
-        self.latent_lora = bool(self.model_config.get("latent_lora", False))
-        self.precise = bool(self.model_config.get("precise", self.precise_default))
-        if self.precise:
-            self._setup_precise()
-        self.gemm_fp8 = bool(self.model_config.get("gemm_fp8", False)) and not self.precise
-        if self.gemm_fp8:
-            self._setup_fp8()
-        self._pick_operands()
-        if self.model_config.get("attn_fp8", False) and not self.precise:
-            self._fp8_images()                                                                    # never first allocated inside a capture
+        self._select_mode(model_config, c_factor)
         if self.model_config.get("add_cond_attn", False) and C and C != N:
             raise ValueError("add_cond_attn adds the condition attention output onto the image stream: needs C == N")
-        f32, bf16 = torch.float32, torch.bfloat16
-        # context_embedder(prompt_embeds) -> cached text rows
-        if self.precise:
-            self._embed_p(prompt_embeds.reshape(B * T, -1), "context_embedder", self.X_txt_init, lora=False)
-            if C:
-                self._embed_p(condition_latents.reshape(B * C, -1), "x_embedder", self.X_cond_init, lora=True)
-        else:
-            pe = prompt_embeds.to(device=dev, dtype=self._op_dtype()).reshape(B * T, -1).contiguous()
-            ops.gemm([ops.gemm_desc(pe, self._W("context_embedder"), self.X_txt_init, bias=w.t["context_embedder.b"],
-                                    epilogue=LX_EPI_STORE_F32, **self._f16_kw())])
-        # x_embedder(condition_latents) with LoRA active -> cached condition rows
-        if C and not self.precise:
-            cl = condition_latents.to(device=dev, dtype=self._op_dtype()).reshape(B * C, -1).contiguous()
-            lo = w.lora.get("x_embedder") if self.lora_scale != 0.0 else None
-            tl = None
-            if lo is not None:
-                tl = self.TL[: B * C, : cfg.lora_r]
-                ops.lora_down(cl, self._down("x_embedder", lo), tl)
-                if self.lora_scale != 1.0:
-                    tl.mul_(self.lora_scale)
-            ops.gemm([ops.gemm_desc(cl, self._W("x_embedder"), self.X_cond_init, bias=w.t["x_embedder.b"], epilogue=LX_EPI_STORE_F32,
-                                    lora_t=tl, lora_up=lo.up if lo is not None else None, **self._f16_kw())])
+        f32 = torch.float32
+        # context_embedder(prompt_embeds) -> cached text rows; x_embedder(condition_latents) with LoRA active -> cached condition rows
+        embed = self._embed_p if self.precise else self._embed
+        embed(prompt_embeds.reshape(B * T, -1), "context_embedder", self.X_txt_init, lora=False)
+        if C:
+            embed(condition_latents.reshape(B * C, -1), "x_embedder", self.X_cond_init, lora=True)
         # RoPE tables: [text; image] and condition (transformer.py:130-134)
         ids = torch.cat([txt_ids.to(dev, f32).reshape(-1, 3), img_ids.to(dev, f32).reshape(-1, 3)], 0)
         # tables live in persistent buffers: the captured step graph holds their addresses
@@ -647,7 +675,24 @@ class DiTEngine:
         self.cond_cached = False          # a new condition stream: the per-layer key / value images are stale
         self.sched = None
 
-    # ------------------------------------------------------------------------------------------ operand format
+    # ------------------------------------------------------------------------------------------ arithmetic mode
+    def _select_mode(self, model_config: Optional[Dict], c_factor: Optional[float], gemm_fp8: bool = True) -> None:
+        """model_config -> latent_lora / precise / gemm_fp8 / the operand format, and the buffers and weight images those modes need: all
+        of them allocated here, by set_conditioning() or configure(), never first inside a capture. gemm_fp8 = False: the caller has no
+        e4m3 GEMM path (the block-level entry points)."""
+        self.model_config = dict(model_config or {})
+        self.c_factor = c_factor
+        self.latent_lora = bool(self.model_config.get("latent_lora", False))
+        self.precise = bool(self.model_config.get("precise", self.precise_default))
+        if self.precise:
+            self._setup_precise()
+        self.gemm_fp8 = gemm_fp8 and bool(self.model_config.get("gemm_fp8", False)) and not self.precise
+        if self.gemm_fp8:
+            self._setup_fp8()
+        self._pick_operands()
+        if self.model_config.get("attn_fp8", False) and not self.precise:
+            self._fp8_images()
+
     def _pick_operands(self) -> None:
         """model_config["operands"]: "bf16" (default) | "fp16" -- the 16-bit format of every GEMM operand image of the forward."""
         fmt = str(self.model_config.get("operands", self.operands_default)).lower()
@@ -676,25 +721,26 @@ class DiTEngine:
         return dict(f16=True, f16_ovf=self.f16_ovf) if self.f16 else {}
 
     # ------------------------------------------------------------------------------------------ building blocks
+    def _ln_segs(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int):
+        """The segment list of an AdaLN LayerNorm + modulation launch over every stream of this forward: per stream (first row, rows, rows per
+        sample, shift vectors, scale vectors), the vectors `shift_off` / `scale_off` past the stream's modulation base."""
+        return [(s.row0, self.B * s.len, s.len, s.mods[:, base_by_stream[s.name] + shift_off:], s.mods[:, base_by_stream[s.name] + scale_off:])
+                for s in self._streams()]
+
     def _ln(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int, lora_for: Optional[str] = None,
             include_txt: bool = False):
         """AdaLN LayerNorm + modulation of every stream of this forward into XN (the 16-bit operand image of this mode).
         lora_for: the Linear that reads XN next (its adapter's down-projection of the adapter rows is computed by the same launch, on the
         matrix pipe, while the normalised rows are at hand: 76 of the 132 lx_lora_down launches of a denoise step sit behind a LayerNorm).
-        Returns what _gemm_streams takes as `lora_ready` ((adapter, first adapter row), or None when there is nothing to hand over)."""
-        row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}
-        segs = []
-        for s, L in self._streams():
-            mods = self.cmods if s == "cond" else self.mods
-            b0 = base_by_stream[s]
-            segs.append((row0[s], self.B * L, L, mods[:, b0 + shift_off:], mods[:, b0 + scale_off:]))
+        Returns what _gemm_streams takes as `lora` ((adapter, 1 slab, first adapter row), or None when there is nothing to hand over)."""
+        segs = self._ln_segs(base_by_stream, shift_off, scale_off)
         lora, ready = None, None
         lo = self.w.lora.get(lora_for) if lora_for is not None else None
-        if (lo is not None and self.ln_lora and (self.C > 0 or self.latent_lora) and self.lora_scale == 1.0 and lo.down.shape[0] <= 16
+        if (lo is not None and self.ln_lora and self.lora_scale == 1.0 and lo.down.shape[0] <= 16
                 and self.cfg.inner_dim in (3072, 256) and self._lora_rows(include_txt) is not None):      # (the widths the kernel is built for)
             r0, n = self._lora_rows(include_txt)
             lora = (self._down(lora_for, lo), self.TL[r0:r0 + n, : lo.down.shape[0]], r0, n)       # slab 0 of TLs: the consumer sums one slab
-            ready = (lo, r0)
+            ready = (lo, 1, r0)
         if self.f16:
             ops.ln_modulate_segs(self.X, segs, self.XN16, self.mods.stride(0), f16_ovf=self.f16_ovf, lora=lora)
         else:
@@ -704,76 +750,94 @@ class DiTEngine:
     def _lora_rows(self, include_txt: bool):
         """(first row, row count) of the rows that run with the adapter on: the condition stream always; with
         model_config["latent_lora"] also the image stream and, where text shares the module (single blocks), text.
-        None: no such rows in this forward (cond_skip without latent_lora)."""
+        None: no such rows in this forward (no condition stream or cond_skip, without latent_lora)."""
         end = self.r_cond if self.cond_skip else self.M
         if self.latent_lora:
             r0 = self.r_txt if include_txt else self.r_img
             return r0, end - r0
-        if self.cond_skip:
+        if self.cond_skip or self.C == 0:
             return None
         return self.r_cond, self.M - self.r_cond
 
+    # An adapter term is handed to a grouped launch as (adapter, slabs of TLs that hold its down-projection, first row they hold), under the
+    # keyword `lora`, in all three modes. (None, 0, 0): nothing to add. The three _lora_t* below compute it from this mode's operand image.
+    NO_LORA = (None, 0, 0)
+
     def _lora_t(self, A: torch.Tensor, name: str, include_txt: bool = False):
         lo = self.w.lora.get(name)
-        if lo is None or (self.C == 0 and not self.latent_lora) or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
-            return None, None
+        if lo is None or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
+            return self.NO_LORA
         r0, n = self._lora_rows(include_txt)
         t = self.TL[r0:r0 + n, : lo.down.shape[0]]
         ops.lora_down(self._op(A[r0:r0 + n]), self._down(name, lo), t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
         if self.lora_scale != 1.0:
             self.TLs[:, r0:r0 + n, : lo.down.shape[0]].mul_(self.lora_scale)
-        return lo, r0
+        return lo, self.TL_SPLIT, r0
 
-    def _gemm_streams(self, A: torch.Tensor, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, epilogue: int,
-                      gate_off: Optional[Dict[str, int]] = None, lora_mod_cols: int = 0, lora_toff_max: int = 0,
-                      gelu_col_start: int = 0, only: Optional[Sequence[str]] = None, ncols: Optional[Dict[str, int]] = None,
-                      qkv=None, lora_ready=None) -> None:
-        """One grouped launch over the token streams. `main` weights serve image+condition rows, `txt` the text rows
-        (None => text rows use `main` too: single blocks). `only` restricts the launch to those streams and `ncols[s]` to the
-        first ncols[s] output columns (a multiple of 256) for stream s: the last block's outputs nobody reads are not computed."""
-        w = self.w
-        lora_needed = only is None or "cond" in only or self.latent_lora
-        nsplit = self.TL_SPLIT
-        if lora_ready is not None:            # the LayerNorm launch that wrote A left this GEMM's adapter term in slab 0 of TL
-            (lo, lr0), nsplit = lora_ready, 1
-        else:
-            lo, lr0 = self._lora_t(A, main, include_txt=txt is None) if lora_needed else (None, None)
+    def _launch_streams(self, desc, workspace, main: str, txt: Optional[str], *, epilogue: int, w_rows: Optional[Dict[str, slice]] = None,
+                        t_col0: int = 0, gate_off: Optional[Dict[str, int]] = None, lora_mod_cols: int = 0, lora_toff_max: int = 0,
+                        only: Optional[Sequence[str]] = None, lora=None) -> None:
+        """One grouped GEMM launch over the token streams, in any operand mode. `main` weights serve image+condition rows, `txt` the text
+        rows (None => text rows use `main` too: single blocks). `only` restricts the launch to those streams, `w_rows[s]` to that range of
+        the weight's rows (= output columns, written to the first columns of the stream's rows of C) for stream s, and `t_col0` names the
+        first column of the adapter slabs that belongs to that range. `gate_off[s]`: the stream's gate vector in its modulation buffer.
+        `lora`: see NO_LORA. The mode supplies desc(stream, weight name, row range, **kw) -> GemmDesc: its operand views of A and C, its
+        weight lookup and its descriptor factory; and the workspace it launches with."""
+        lo, n_slabs, lr0 = lora if lora is not None else self.NO_LORA
         probs = []
-        for s, L in self._streams():
-            if only is not None and s not in only:
+        for s in self._streams():
+            if only is not None and s.name not in only:
                 continue
-            name = txt if (s == "txt" and txt is not None) else main
-            a, c = self._op(self.rows(A, s)), self.rows(Cbuf, s)
-            W, bias = self._W(name), w.t[name + ".b"]
+            name = txt if (s.name == "txt" and txt is not None) else main
+            rows = w_rows.get(s.name) if w_rows else None
+            bias = self.w.t[name + ".b"]
+            kw = dict(bias=bias if rows is None else bias[rows], epilogue=epilogue, rows_per_batch=s.len)
+            if gate_off is not None:
+                kw["gate"] = s.mods[:, gate_off[s.name]:]
+            if lo is not None and name == main and s.row0 >= lr0 and (s.name == "cond" or (s.name == "img" and self.latent_lora) or
+                                                                       (s.name == "txt" and self.latent_lora and txt is None)):
+                kw.update(lora_t=self.TL[s.row0:s.row0 + self.B * s.len, t_col0:], lora_up=lo.up if rows is None else lo.up[rows],
+                          lora_mod_cols=lora_mod_cols, lora_toff_max=lora_toff_max, lora_nsplit=n_slabs, lora_split_stride=self.TLs.stride(0))
+            probs.append(desc(s, name, rows, **kw))
+        ops.gemm(probs, workspace)
+
+    @staticmethod
+    def _every_stream(rows: slice) -> Dict[str, slice]:
+        return {"txt": rows, "img": rows, "cond": rows}
+
+    def _lora_wanted(self, only: Optional[Sequence[str]]) -> bool:
+        """Can a launch over `only` have adapter rows at all? (Which rows: _lora_rows.)"""
+        return only is None or "cond" in only or self.latent_lora
+
+    def _gemm_streams(self, A: torch.Tensor, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, epilogue: int, gelu_col_start: int = 0,
+                      qkv=None, only: Optional[Sequence[str]] = None, lora=None, **kw) -> None:
+        """The grouped launch (_launch_streams) on the 16-bit operand images of this mode (bf16 or fp16). lora = None: the adapter's
+        down-projection is computed here, from A. qkv = (wq, wk, wq_txt, wk_txt[, layer]): RMSNorm + RoPE + V^T in the launch's epilogue."""
+        if lora is None:
+            lora = self._lora_t(A, main, include_txt=txt is None) if self._lora_wanted(only) else self.NO_LORA
+
+        def desc(s: Stream, name: str, rows: Optional[slice], **k):
+            a, c = self._op(self.rows(A, s.name)), self.rows(Cbuf, s.name)
             if self.f16 and (epilogue & 0xff) == LX_EPI_STORE_BF16 and qkv is None:
                 c = c.view(torch.float16)               # a 16-bit store of this mode is the next GEMM's fp16 operand
-            n_out = ncols.get(s) if ncols else None
-            if n_out is not None and n_out < W.shape[0]:
-                tiled = getattr(W, "lx_tiled", False)
-                W, bias, c = W[:n_out], bias[:n_out], c[:, :n_out]
-                if tiled:
-                    W.lx_tiled = True          # row blocks of 256 are contiguous in the tiled image
-            kw = dict(bias=bias, epilogue=epilogue, rows_per_batch=L, gelu_col_start=gelu_col_start, **self._f16_kw())
-            if qkv is not None:                # (wq, wk, wq_txt, wk_txt[, layer]): RMSNorm + RoPE + V^T in this launch's epilogue
-                rope = self.rope_cs_cond if s == "cond" else (self.rope_cs_main[: self.T] if s == "txt" else self.rope_cs_main[self.T:])
-                kw["qkv"] = dict(norm_q=self._qn(qkv[2] if s == "txt" else qkv[0], qkv[0]), norm_k=qkv[3] if s == "txt" else qkv[1], rope=rope,
-                                 vt=self.VT, vt_pos0=self.vt0[s], d=self.cfg.inner_dim)
-                if self.model_config.get("attn_fp8", False):      # e4m3 q / k / V^T images straight from the accumulators
-                    self._fp8_images()
-                    kw["qkv"].update(q8=self.rows(self.Q8, s), k8=self.rows(self.K8, s), vt=self.VT8)
-                elif self.cond_cache and len(qkv) > 4:      # per-layer key / V^T images: the condition rows' entries outlive the step
-                    kw["qkv"].update(k=self.rows(self.KC[qkv[4]], s), vt=self.VTC[qkv[4]])
-            if gate_off is not None:
-                mods = self.cmods if s == "cond" else self.mods
-                kw["gate"] = mods[:, gate_off[s]:]
-            if lo is not None and name == main and (s == "cond" or (s == "img" and self.latent_lora) or
-                                                    (s == "txt" and self.latent_lora and txt is None)):
-                row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}[s]
-                if row0 >= lr0:
-                    kw.update(lora_t=self.TL[row0:row0 + a.shape[0]], lora_up=lo.up[: W.shape[0]], lora_mod_cols=lora_mod_cols,
-                              lora_toff_max=lora_toff_max, lora_nsplit=nsplit, lora_split_stride=self.TLs.stride(0))
-            probs.append(ops.gemm_desc(a, W, c, **kw))
-        ops.gemm(probs, self.gemm_ws())
+            if qkv is not None:
+                k["qkv"] = self._qkv_kw(s, qkv)
+            return ops.gemm_desc(a, self._w_rows(self._W(name), rows), c, gelu_col_start=gelu_col_start, **k, **self._f16_kw())
+
+        self._launch_streams(desc, self.gemm_ws(), main, txt, epilogue=epilogue, only=only, lora=lora, **kw)
+
+    def _qkv_kw(self, s: Stream, qkv) -> Dict:
+        """What the projection launch's fused epilogue (LX_EPI_QKV) needs for stream s: norm weights, the stream's (cos, sin) pairs and
+        where k, q and V^T go."""
+        rope = self.rope_cs_cond if s.name == "cond" else (self.rope_cs_main[: self.T] if s.name == "txt" else self.rope_cs_main[self.T:])
+        kw = dict(norm_q=self._qn(qkv[2] if s.name == "txt" else qkv[0], qkv[0]), norm_k=qkv[3] if s.name == "txt" else qkv[1], rope=rope,
+                  vt=self.VT, vt_pos0=s.vt0, d=self.cfg.inner_dim)
+        if self.model_config.get("attn_fp8", False):      # e4m3 q / k / V^T images straight from the accumulators
+            self._fp8_images()
+            kw.update(q8=self.rows(self.Q8, s.name), k8=self.rows(self.K8, s.name), vt=self.VT8)
+        elif self.cond_cache and len(qkv) > 4:      # per-layer key / V^T images: the condition rows' entries outlive the step
+            kw.update(k=self.rows(self.KC[qkv[4]], s.name), vt=self.VTC[qkv[4]])
+        return kw
 
     def _rope_pairs(self, check: bool) -> None:
         """(cos, sin) per rotary pair, [L, 128], for LX_EPI_QKV, and the decision whether the projections of this configuration
@@ -781,7 +845,7 @@ class DiTEngine:
         entries of a pair agree (FluxPosEmbed's repeat_interleave; `check`: tables handed in by a caller are verified)."""
         D, rd = self.cfg.inner_dim, sum(self.cfg.axes_dims_rope)
         ok = (self.qkv_epilogue and D % 256 == 0 and rd == 128 and self.cos_main is not None
-              and all(L % 32 == 0 for _, L in self._all_streams()) and (self.C == 0 or self.cos_cond is not None)
+              and all(s.len % 32 == 0 for s in self._all_streams()) and (self.C == 0 or self.cos_cond is not None)
               and self.cos_main.shape[0] == self.T + self.N)
         if ok:
             pairs = [(self.rope_cs_main, self.cos_main, self.sin_main)]
@@ -809,31 +873,15 @@ class DiTEngine:
         cfg = self.cfg
         D, H, B = cfg.inner_dim, cfg.num_attention_heads, self.B
         Y = self.Y
-        seg_row0, seg_len, seg_vt0, qsegs = [], [], [], []
-        off = 0
         cached = self.cond_cache and layer is not None and prepped
         streams = self._all_streams() if cached else self._streams()      # key / value segments (queries: the streams of this forward)
-        bias = [[0.0] * 3 for _ in range(3)]
-        for qi, (qs, _) in enumerate(streams):
-            for ki, (ks, _) in enumerate(streams):
-                bias[qi][ki] = self.attn_bias[qs][ks]
-        for s, L in streams:
-            row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}[s]
-            if s == "cond":
-                cos, sin = self.cos_cond, self.sin_cond
-            elif self.cos_main is None:
-                cos = sin = None
-            else:
-                cos, sin = self.cos_main[off:off + L], self.sin_main[off:off + L]
-                off += L
-            qsegs.append((row0, L, self.vt0[s], self._qn(wq_txt if s == "txt" else wq, wq), wk_txt if s == "txt" else wk, cos, sin))
-            seg_row0.append(row0); seg_len.append(L); seg_vt0.append(self.vt0[s])
+        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(streams, (wq, wk, wq_txt, wk_txt))
         flags = (ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0
         if not self.pair_plan:             # the batch-size-invariant plans: the attention kernel must not depend on the batch size either
             flags |= ops.ATTN_INVARIANT
         okw = dict(f16_ovf=self.f16_ovf) if self.f16 else {}      # O is the output projection's A operand: fp16 in the fp16 operand mode
         if img_only:
-            okw["qseg_mask"] = 1 << [s for s, _ in streams].index("img")
+            okw["qseg_mask"] = 1 << [s.name for s in streams].index("img")
         if self.f16:
             flags |= ops.ATTN_O_F16
         # the caller's mask: a block-level call's (prepared inside the call) or the conditioning's (prepared by set_conditioning)
@@ -890,7 +938,7 @@ class DiTEngine:
         nw = (w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
         fused = self._qkv_epilogue()
         self._gemm_streams(self.XN, Yq, p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_BF16, lora_mod_cols=D, lora_toff_max=2,
-                           qkv=nw + (i,) if fused else None, lora_ready=ready)
+                           qkv=nw + (i,) if fused else None, lora=ready)
         self._attention(*nw, prepped=fused, layer=i)
         gate = {s: base[s] + 2 * D for s in base}
         self._gemm_streams(Ya, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
@@ -902,7 +950,7 @@ class DiTEngine:
             ops.gemm([ops.gemm_desc(self._op(a), self._W(p + ".out"), self.rows(self.X, "img"), bias=w.t[p + ".out.b"], epilogue=LX_EPI_RESID_F32,
                                     rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw, **self._f16_kw())])
         ready = self._ln(base, 3 * D, 4 * D, lora_for=p + ".ff1")                           # norm2 + (scale_mlp, shift_mlp)
-        self._gemm_streams(self.XN, Yf, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, lora_ready=ready)
+        self._gemm_streams(self.XN, Yf, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, lora=ready)
         gate = {s: base[s] + 5 * D for s in base}
         self._gemm_streams(Yf, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
 
@@ -921,12 +969,12 @@ class DiTEngine:
         base = {"img": b, "cond": b, "txt": b}
         p = f"s{j}"
         ready = self._ln(base, 0, D, lora_for=p + ".fused", include_txt=True)
-        kv_only = {"txt": 2 * D, "cond": 2 * D} if image_out_only else None          # fused columns are [k | v | q | mlp]
+        kv_only = {"txt": slice(0, 2 * D), "cond": slice(0, 2 * D)} if image_out_only else None      # fused columns are [k | v | q | mlp]
         nw = (w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
         fused = self._qkv_epilogue()
         self._gemm_streams(self.XN, self.Y, p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, gelu_col_start=3 * D,
-                           lora_mod_cols=D, lora_toff_max=3, ncols=kv_only, qkv=nw + (cfg.num_layers + j,) if fused else None,
-                           lora_ready=ready)
+                           lora_mod_cols=D, lora_toff_max=3, w_rows=kv_only, qkv=nw + (cfg.num_layers + j,) if fused else None,
+                           lora=ready)
         self._attention(*nw, prepped=fused, layer=cfg.num_layers + j, img_only=image_out_only)
         gate = {s: b + 2 * D for s in base}
         self._gemm_streams(self.Y[:, 2 * D:], self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate,
@@ -965,61 +1013,29 @@ class DiTEngine:
             t = self.w8[key] = (self.w8[name + ".rs"] / act_scale).contiguous()
         return t if rows is None else t[rows]
 
-    def _gemm_streams_8(self, A8: torch.Tensor, act_scale: float, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, epilogue: int,
-                        w_rows: Optional[slice] = None, t_col0: int = 0, gate_off: Optional[Dict[str, int]] = None, lora_mod_cols: int = 0,
-                        lora_toff_max: int = 0, gelu: bool = False, only: Optional[Sequence[str]] = None, lora=None, out_scale: float = 0.0):
-        """One grouped fp8 launch over the token streams (the fp8 twin of _gemm_streams). `lora` = (Lora, first row) of a
-        down-projection already in the TL slabs (computed by the caller from whichever image of the operand it has)."""
-        w = self.w
-        row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}
-        lo, lr0 = lora if lora is not None else (None, 0)
-        probs = []
-        for s_, L in self._streams():
-            if only is not None and s_ not in only:
-                continue
-            name = txt if (s_ == "txt" and txt is not None) else main
-            a, c = self.rows(A8, s_), self.rows(Cbuf, s_)
-            W8, bias = self.w8[name], w.t[name + ".b"]
-            if w_rows is not None:
-                tiled = getattr(W8, "lx_tiled", False)
-                W8, bias = W8[w_rows], bias[w_rows]
-                if tiled:
-                    W8.lx_tiled = True
-            kw = dict(bias=bias, epilogue=epilogue | (LX_EPI_GELU if gelu else 0), rows_per_batch=L, fp8=True, col_scale=self._cs(name, act_scale, w_rows),
-                      out_scale=out_scale)
-            if gate_off is not None:
-                mods = self.cmods if s_ == "cond" else self.mods
-                kw["gate"] = mods[:, gate_off[s_]:]
-            if lo is not None and name == main and row0[s_] >= lr0 and (s_ == "cond" or (s_ == "img" and self.latent_lora) or
-                                                                         (s_ == "txt" and self.latent_lora and txt is None)):
-                up = lo.up[w_rows] if w_rows is not None else lo.up
-                kw.update(lora_t=self.TL[row0[s_]:row0[s_] + a.shape[0], t_col0:], lora_up=up, lora_mod_cols=lora_mod_cols,
-                          lora_toff_max=lora_toff_max, lora_nsplit=self.TL_SPLIT, lora_split_stride=self.TLs.stride(0))
-            probs.append(ops.gemm_desc(a, W8, c, **kw))
-        ops.gemm(probs)
+    def _gemm_streams_8(self, A8: torch.Tensor, act_scale: float, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, out_scale: float = 0.0,
+                        **kw) -> None:
+        """The grouped launch (_launch_streams) on e4m3 operand images: A8 = e4m3(activation * act_scale), per-output-row weight scales.
+        The caller brings the adapter's down-projection (`lora`), computed from whichever image of the operand it has. No workspace:
+        lx_gemm_fp8_kernel has no pair plan."""
+        def desc(s: Stream, name: str, rows: Optional[slice], **k):
+            return ops.gemm_desc(self.rows(A8, s.name), self._w_rows(self.w8[name], rows), self.rows(Cbuf, s.name), fp8=True,
+                                 col_scale=self._cs(name, act_scale, rows), out_scale=out_scale, **k)
+
+        self._launch_streams(desc, None, main, txt, **kw)
 
     def _lora_t8(self, X8: torch.Tensor, act_scale: float, name: str, include_txt: bool = False):
         """LoRA down-projection from an e4m3 operand image (the MLP hidden / [attn | mlp] exist only as fp8 in this mode)."""
         lo = self.w.lora.get(name)
-        if lo is None or (self.C == 0 and not self.latent_lora) or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
-            return None
+        if lo is None or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
+            return self.NO_LORA
         r0, n = self._lora_rows(include_txt)
         t = self.TL[r0:r0 + n, : lo.down.shape[0]]
         ops.lora_down_fp8(X8[r0:r0 + n], self.lora_scale / act_scale, lo.down, t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
-        return lo, r0
+        return lo, self.TL_SPLIT, r0
 
     def _ln8(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
-        row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}
-        segs = []
-        for s_, L in self._streams():
-            mods = self.cmods if s_ == "cond" else self.mods
-            b0 = base_by_stream[s_]
-            segs.append((row0[s_], self.B * L, L, mods[:, b0 + shift_off:], mods[:, b0 + scale_off:]))
-        ops.ln_modulate_fp8_segs(self.X, segs, self.XN, self.XN8, self.mods.stride(0), self.S_X8)
-
-    def _lora_pair(self, A: torch.Tensor, name: str, include_txt: bool = False):
-        lo, r0 = self._lora_t(A, name, include_txt=include_txt)
-        return None if lo is None else (lo, r0)
+        ops.ln_modulate_fp8_segs(self.X, self._ln_segs(base_by_stream, shift_off, scale_off), self.XN, self.XN8, self.mods.stride(0), self.S_X8)
 
     def _double_block_8(self, i: int) -> None:
         cfg, w = self.cfg, self.w
@@ -1030,17 +1046,17 @@ class DiTEngine:
         Y, Y8 = self.Y, self.Y8
         self._ln8(base, 0, D)                                                             # XN (bf16, for the LoRA down) + XN8
         self._gemm_streams_8(self.XN8, self.S_X8, Y[:, : 3 * D], p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_BF16, lora_mod_cols=D,
-                             lora_toff_max=2, lora=self._lora_pair(self.XN, p + ".qkv"))
+                             lora_toff_max=2, lora=self._lora_t(self.XN, p + ".qkv"))
         self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
         Ya = Y[:, 2 * D: 3 * D]
         ops.convert_fp8(Ya, Y8[:, :D], self.S_Y8)                                          # attention output -> e4m3 image
         gate = {s_: base[s_] + 2 * D for s_ in base}
         self._gemm_streams_8(Y8[:, :D], self.S_Y8, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate,
-                             lora=self._lora_pair(Ya, p + ".out"))
+                             lora=self._lora_t(Ya, p + ".out"))
         if self.C and self.model_config.get("add_cond_attn", False):
             raise NotImplementedError("add_cond_attn is not wired into the fp8 GEMM path (use the bf16 or the precise mode)")
         self._ln8(base, 3 * D, 4 * D)
-        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".ff1", p + ".ff1_txt", epilogue=ops.LX_EPI_STORE_FP8, gelu=True, out_scale=self.S_Y8)
+        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".ff1", p + ".ff1_txt", epilogue=ops.LX_EPI_STORE_FP8 | LX_EPI_GELU, out_scale=self.S_Y8)
         gate = {s_: base[s_] + 5 * D for s_ in base}
         self._gemm_streams_8(Y8[:, D:], self.S_Y8, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate,
                              lora=self._lora_t8(Y8[:, D:], self.S_Y8, p + ".ff2"))
@@ -1053,13 +1069,13 @@ class DiTEngine:
         p = f"s{j}"
         Y, Y8 = self.Y, self.Y8
         self._ln8(base, 0, D)
-        lora = self._lora_pair(self.XN, p + ".fused", include_txt=True)
+        lora = self._lora_t(self.XN, p + ".fused", include_txt=True)
         only = ("img",) if image_out_only else None
         # the fused [k | v | q | mlp] weight in two launches: q/k/v as bf16 for the attention prep, the MLP hidden straight to e4m3
-        self._gemm_streams_8(self.XN8, self.S_X8, Y[:, : 3 * D], p + ".fused", None, epilogue=LX_EPI_STORE_BF16, w_rows=slice(0, 3 * D),
-                             lora_mod_cols=D, lora_toff_max=2, lora=lora)
-        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".fused", None, epilogue=ops.LX_EPI_STORE_FP8, gelu=True, out_scale=self.S_Y8,
-                             w_rows=slice(3 * D, 7 * D), t_col0=3 * r, only=only, lora=lora)
+        self._gemm_streams_8(self.XN8, self.S_X8, Y[:, : 3 * D], p + ".fused", None, epilogue=LX_EPI_STORE_BF16,
+                             w_rows=self._every_stream(slice(0, 3 * D)), lora_mod_cols=D, lora_toff_max=2, lora=lora)
+        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".fused", None, epilogue=ops.LX_EPI_STORE_FP8 | LX_EPI_GELU,
+                             out_scale=self.S_Y8, w_rows=self._every_stream(slice(3 * D, 7 * D)), t_col0=3 * r, only=only, lora=lora)
         self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
         ops.convert_fp8(Y[:, 2 * D: 3 * D], Y8[:, :D], self.S_Y8)
         gate = {s_: b + 2 * D for s_ in base}
@@ -1071,20 +1087,15 @@ class DiTEngine:
         """GEMM descriptor of a split-bf16 launch: A2 holds the hi image in columns [0, K) and the lo image a_lo_off columns
         further; the weight is [W_hi | W_lo] (3 K-segments) when it has a rounding residual, else W (2 segments)."""
         w2 = self.w.t.get(name + ".w2")
-        W = w2 if w2 is not None else self.w.t[name + ".w"]
-        if w_rows is not None:
-            tiled = getattr(W, "lx_tiled", False)
-            W = W[w_rows]
-            if tiled:
-                W.lx_tiled = True            # row blocks of 256 are contiguous in the tiled image
+        W = self._w_rows(w2 if w2 is not None else self.w.t[name + ".w"], w_rows)
         return ops.gemm_desc(A2, W, Cbuf, K=K, N=W.shape[0], k_segs=3 if w2 is not None else 2, a_lo_off=a_lo_off, **kw)
 
     def _lora_t_p(self, A2: torch.Tensor, name: str, K: int, a_lo_off: int, r0: int, n: int):
         """t = x A_down^T for rows [r0, r0+n) with x = hi + lo: one slab per cross term (the consumer GEMM adds them).
-        Returns (Lora, number of slabs) or (None, 0)."""
+        Returns the `lora` of the launch that consumes them (NO_LORA: no adapter on this Linear)."""
         lo = self.w.lora.get(name)
         if lo is None or self.lora_scale == 0.0:
-            return None, 0
+            return self.NO_LORA
         R = lo.down.shape[0]
         terms = [(A2[r0:r0 + n, :K], lo.down), (A2[r0:r0 + n, a_lo_off:a_lo_off + K], lo.down)]
         if lo.down_lo is not None:
@@ -1093,7 +1104,7 @@ class DiTEngine:
         ops.lora_down_terms(terms, self.TLs[0, r0:r0 + n, :R], self.TLs.stride(0))
         if self.lora_scale != 1.0:
             self.TLs[: len(terms), r0:r0 + n, :R].mul_(self.lora_scale)
-        return lo, len(terms)
+        return lo, len(terms), r0
 
     def _embed_p(self, x32: torch.Tensor, name: str, out: torch.Tensor, lora: bool, pair: Optional[torch.Tensor] = None) -> None:
         """out(fp32) = Linear_name(x32) with x as a hi/lo pair (context_embedder / x_embedder)."""
@@ -1104,84 +1115,54 @@ class DiTEngine:
         ops.split_bf16(x32, pair, K)
         kw = {}
         if lora:
-            lo, ns = self._lora_t_p(pair, name, K, K, 0, rows) if rows <= self.TLs.shape[1] else (None, 0)
+            lo, ns, _ = self._lora_t_p(pair, name, K, K, 0, rows) if rows <= self.TLs.shape[1] else self.NO_LORA
             if lo is not None:
                 kw = dict(lora_t=self.TL[:rows], lora_up=lo.up, lora_nsplit=ns, lora_split_stride=self.TLs.stride(0))
         ops.gemm([self._desc_p(pair, name, out, K=K, a_lo_off=K, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, **kw)], self.gemm_ws())
 
-    def _ln_p(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
-        row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}
-        segs = []
-        for s_, L in self._streams():
-            mods = self.cmods if s_ == "cond" else self.mods
-            b0 = base_by_stream[s_]
-            segs.append((row0[s_], self.B * L, L, mods[:, b0 + shift_off:], mods[:, b0 + scale_off:]))
-        ops.ln_modulate_split_segs(self.X, segs, self.XN2, self.mods.stride(0), self.cfg.inner_dim)
+    def _embed(self, x: torch.Tensor, name: str, out: torch.Tensor, lora: bool) -> None:
+        """out(fp32) = Linear_name(x) on the 16-bit operand image of x in this mode (context_embedder / x_embedder): _embed_p's twin for
+        the bf16 / fp16 / e4m3 modes (whose embedders run on 16-bit operands alike)."""
+        x = x.to(device=self.device, dtype=self._op_dtype()).contiguous()
+        lo = self.w.lora.get(name) if (lora and self.lora_scale != 0.0) else None
+        tl = None
+        if lo is not None:
+            tl = self.TL[: x.shape[0], : self.cfg.lora_r]
+            ops.lora_down(x, self._down(name, lo), tl)
+            if self.lora_scale != 1.0:
+                tl.mul_(self.lora_scale)
+        ops.gemm([ops.gemm_desc(x, self._W(name), out, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, lora_t=tl,
+                                lora_up=lo.up if lo is not None else None, **self._f16_kw())])
 
-    def _gemm_streams_p(self, A2: torch.Tensor, K: int, a_lo_off: int, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, epilogue: int,
-                        c_lo_off: int = 0, w_rows: Optional[slice] = None, t_col0: int = 0, gate_off: Optional[Dict[str, int]] = None,
-                        lora_mod_cols: int = 0, lora_toff_max: int = 0, gelu: bool = False, only: Optional[Sequence[str]] = None,
-                        lora_done=None):
-        """The precise twin of _gemm_streams: one grouped split-bf16 launch over the token streams. `w_rows`: row range of the
-        (fused) weight this launch evaluates, `t_col0`: first column of the LoRA slab that belongs to it. Returns the
-        (Lora, slabs, first row) of the LoRA down-projection it computed (or was handed in `lora_done`) for a sibling launch."""
-        w = self.w
-        row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}
-        if lora_done is not None:
-            lo, ns, lr0 = lora_done
-        elif ((self.C == 0 and not self.latent_lora) or (only is not None and "cond" not in only and not self.latent_lora)
-              or self._lora_rows(txt is None) is None):
-            lo, ns, lr0 = None, 0, 0
-        else:
-            lr0, n = self._lora_rows(txt is None)
-            lo, ns = self._lora_t_p(A2, main, K, a_lo_off, lr0, n)
-        probs = []
-        for s_, L in self._streams():
-            if only is not None and s_ not in only:
-                continue
-            name = txt if (s_ == "txt" and txt is not None) else main
-            a, c = self.rows(A2, s_), self.rows(Cbuf, s_)
-            bias = w.t[name + ".b"]
-            kw = dict(bias=bias[w_rows] if w_rows is not None else bias, epilogue=epilogue | (LX_EPI_GELU if gelu else 0), rows_per_batch=L,
-                      c_lo_off=c_lo_off)
-            if gate_off is not None:
-                mods = self.cmods if s_ == "cond" else self.mods
-                kw["gate"] = mods[:, gate_off[s_]:]
-            if lo is not None and name == main and row0[s_] >= lr0 and (s_ == "cond" or (s_ == "img" and self.latent_lora) or
-                                                                         (s_ == "txt" and self.latent_lora and txt is None)):
-                up = lo.up[w_rows] if w_rows is not None else lo.up
-                kw.update(lora_t=self.TL[row0[s_]:row0[s_] + a.shape[0], t_col0:], lora_up=up, lora_mod_cols=lora_mod_cols,
-                          lora_toff_max=lora_toff_max, lora_nsplit=ns, lora_split_stride=self.TLs.stride(0))
-            probs.append(self._desc_p(a, name, c, K=K, a_lo_off=a_lo_off, w_rows=w_rows, **kw))
-        ops.gemm(probs, self.gemm_ws())       # (the workspace admits lx_gemm4_kernel<true> and its split form; None under LX_PAIR_PLAN=0)
-        return lo, ns, lr0
+    def _ln_p(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
+        ops.ln_modulate_split_segs(self.X, self._ln_segs(base_by_stream, shift_off, scale_off), self.XN2, self.mods.stride(0), self.cfg.inner_dim)
+
+    def _gemm_streams_p(self, A2: torch.Tensor, K: int, a_lo_off: int, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, c_lo_off: int = 0,
+                        only: Optional[Sequence[str]] = None, lora=None, **kw):
+        """The grouped launch (_launch_streams) on split-bf16 operands (_desc_p). lora = None: the adapter's down-projection is computed
+        here, from A2. Returns the `lora` it launched with, for a sibling launch over the same operand (the two halves of the single
+        blocks' fused weight) or the add_cond_attn launch."""
+        if lora is None:
+            lora = self.NO_LORA
+            if self._lora_wanted(only) and self._lora_rows(txt is None) is not None:
+                lora = self._lora_t_p(A2, main, K, a_lo_off, *self._lora_rows(txt is None))
+
+        def desc(s: Stream, name: str, rows: Optional[slice], **k):
+            return self._desc_p(self.rows(A2, s.name), name, self.rows(Cbuf, s.name), K=K, a_lo_off=a_lo_off, w_rows=rows, c_lo_off=c_lo_off, **k)
+
+        # (the workspace admits lx_gemm4_kernel<true> and its split form; None under LX_PAIR_PLAN=0)
+        self._launch_streams(desc, self.gemm_ws(), main, txt, only=only, lora=lora, **kw)
+        return lora
 
     def _attention_p(self, wq, wk, wq_txt, wk_txt) -> None:
         """fp32 q / k / v in Y32 = [k | v | q]: per-head RMSNorm + RoPE in fp32, fp32 attention, output pair into YA's attn columns."""
         D, H, B = self.cfg.inner_dim, self.cfg.num_attention_heads, self.B
-        seg_row0, seg_len, qsegs = [], [], []
-        off = 0
-        streams = self._streams()
-        bias = [[0.0] * 3 for _ in range(3)]
-        for qi, (qs, _) in enumerate(streams):
-            for ki, (ks, _) in enumerate(streams):
-                bias[qi][ki] = self.attn_bias[qs][ks]
-        for s_, L in streams:
-            row0 = {"txt": self.r_txt, "img": self.r_img, "cond": self.r_cond}[s_]
-            if s_ == "cond":
-                cos, sin = self.cos_cond, self.sin_cond
-            elif self.cos_main is None:
-                cos = sin = None
-            else:
-                cos, sin = self.cos_main[off:off + L], self.sin_main[off:off + L]
-                off += L
-            qsegs.append((row0, L, self.vt0[s_], self._qn(wq_txt if s_ == "txt" else wq, wq), wk_txt if s_ == "txt" else wk, cos, sin))
-            seg_row0.append(row0); seg_len.append(L)
+        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(self._streams(), (wq, wk, wq_txt, wk_txt))
         if self.precise_attn_split:
             # split-bf16 attention: hi.hi + hi.lo + lo.hi on the bf16 MFMA (3/16 of the fp32-MFMA cost), fp32 softmax
             ops.qkv_prep_split_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, q2_col=2 * D, k2_col=0, lo_off=D, VT2=self.VT2)
             ops.attn_fwd_split(self.QK2, self.VT2, self.YA, q_col=2 * D, k_col=0, qk_lo_off=D, o_col=0, o_lo_off=5 * D, B=B, H=H,
-                               seg_row0=seg_row0, seg_len=seg_len, seg_vt0=[q[2] for q in qsegs], bias=bias,
+                               seg_row0=seg_row0, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias,
                                flags=(ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0)
             return
         ops.qkv_prep_f32_segs(self.Y32, 2 * D, 0, qsegs, B, H)
@@ -1207,7 +1188,7 @@ class DiTEngine:
                                    epilogue=LX_EPI_RESID_F32, rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw)], self.gemm_ws())
         self._ln_p(base, 3 * D, 4 * D)
         Ym = self.YA[:, D:]                                                                   # mlp hidden pair: hi at [D, 5D), lo 5D further
-        self._gemm_streams_p(self.XN2, D, D, Ym, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16, c_lo_off=5 * D, gelu=True)
+        self._gemm_streams_p(self.XN2, D, D, Ym, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, c_lo_off=5 * D)
         gate = {s_: base[s_] + 5 * D for s_ in base}
         self._gemm_streams_p(Ym, 4 * D, 5 * D, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
 
@@ -1219,11 +1200,11 @@ class DiTEngine:
         p = f"s{j}"
         self._ln_p(base, 0, D)
         # the fused [k | v | q | mlp] weight in two launches: q/k/v stay fp32 (Y32), the MLP hidden becomes a GELU'd bf16 pair
-        lora = self._gemm_streams_p(self.XN2, D, D, self.Y32, p + ".fused", None, epilogue=LX_EPI_STORE_F32, w_rows=slice(0, 3 * D),
-                                    lora_mod_cols=D, lora_toff_max=2)
+        lora = self._gemm_streams_p(self.XN2, D, D, self.Y32, p + ".fused", None, epilogue=LX_EPI_STORE_F32,
+                                    w_rows=self._every_stream(slice(0, 3 * D)), lora_mod_cols=D, lora_toff_max=2)
         only = ("img",) if image_out_only else None
-        self._gemm_streams_p(self.XN2, D, D, self.YA[:, D:], p + ".fused", None, epilogue=LX_EPI_STORE_BF16, c_lo_off=5 * D, gelu=True,
-                             w_rows=slice(3 * D, 7 * D), t_col0=3 * r, only=only, lora_done=lora)
+        self._gemm_streams_p(self.XN2, D, D, self.YA[:, D:], p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, c_lo_off=5 * D,
+                             w_rows=self._every_stream(slice(3 * D, 7 * D)), t_col0=3 * r, only=only, lora=lora)
         self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
         gate = {s_: b + 2 * D for s_ in base}
         self._gemm_streams_p(self.YA, 5 * D, 5 * D, self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate, only=only)
@@ -1231,29 +1212,14 @@ class DiTEngine:
     # ------------------------------------------------------------------------------------------ one step
     def embed_step_inputs(self, latents: torch.Tensor, timestep: torch.Tensor, mods_ready: bool = False) -> None:
         """x_embedder(latents), reset text/condition rows, temb(t) and every image/text modulation vector."""
-        w, cfg = self.w, self.cfg
         if self.precise:
             self._embed_p(latents.reshape(self.B * self.N, -1), "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora, pair=self.lat2)
-            self.rows(self.X, "txt").copy_(self.X_txt_init)
-            if self.C:
-                self.rows(self.X, "cond").copy_(self.X_cond_init)
-            if not mods_ready:
-                torch.mul(timestep.to(device=self.device, dtype=torch.float32), 1000.0, out=self.t1000)
-                self._time_text_embed(self.t1000, self.temb, self.temb_base)
-                self._compute_mods(self.temb, self.mods, lora=self.latent_lora)
-            return
-        lat = self._op(self.lat16)
-        ops.convert(lat, latents.reshape(self.B * self.N, -1).contiguous())
-        lo = w.lora.get("x_embedder") if (self.latent_lora and self.lora_scale != 0.0) else None
-        tl = None
-        if lo is not None:
-            tl = self.TL[: self.B * self.N, : cfg.lora_r]
-            ops.lora_down(lat, self._down("x_embedder", lo), tl)
-            if self.lora_scale != 1.0:
-                tl.mul_(self.lora_scale)
-        ops.gemm([ops.gemm_desc(lat, self._W("x_embedder"), self.rows(self.X, "img"), bias=w.t["x_embedder.b"],
-                                epilogue=LX_EPI_STORE_F32, lora_t=tl, lora_up=lo.up if lo is not None else None, **self._f16_kw())])
+        else:
+            lat = self._op(self.lat16)
+            ops.convert(lat, latents.reshape(self.B * self.N, -1).contiguous())
+            self._embed(lat, "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora)
         self.rows(self.X, "txt").copy_(self.X_txt_init)
+        # (cond_skip is never set in precise mode: _qkv_epilogue() is False there, so _cond_cache_ok() is)
         if self.C and not self.cond_skip:
             self.rows(self.X, "cond").copy_(self.X_cond_init)
         if mods_ready:                      # self.mods already holds this step's row of the prepare_schedule() table
@@ -1328,7 +1294,7 @@ class DiTEngine:
         key = (self.shape, tuple(sorted(self.model_config.items())), self.c_factor, pre, self.pair_plan, self.precise, self.gemm_fp8, self.f16,
                getattr(self.w, "q_log2_version", 0),      # (a weight broadcast refreshes the scaled norm_q tensors and the per-layer bounds)
                getattr(self.w, "weights_version", 0),     # (... and moves this one unconditionally: dist.broadcast_packed_weights)
-               self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, getattr(self, "_w16_gen", 0) if self.f16 else 0,
+               self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, self._w16_gen if self.f16 else 0,
                # the masked launches hold the workspace's address and the mask's tile geometry (dtype, broadcast dims), never the mask itself:
                # a new mask of the same form is a new prep into the same workspace (set_conditioning), which the same graph then reads
                None if self.cond_mask is None else (self._mask_ws.data_ptr(), self.cond_mask.dtype, tuple(self.cond_mask.shape[:3])))
@@ -1414,16 +1380,7 @@ class DiTEngine:
         self.graphs = {}
         self.cond_mask = None                                      # (a conditioning's mask does not outlive it; block-level calls bring their own)
         self.cond_cache = self.cond_cached = False                # block-level use: every call computes all three streams
-        self.model_config = dict(model_config or {})
-        self.c_factor = c_factor
-        self.latent_lora = bool(self.model_config.get("latent_lora", False))
-        self.precise = bool(self.model_config.get("precise", self.precise_default))
-        if self.precise:
-            self._setup_precise()
-        elif self.model_config.get("attn_fp8", False):
-            self._fp8_images()
-        self.gemm_fp8 = False
-        self._pick_operands()
+        self._select_mode(model_config, c_factor, gemm_fp8=False)
         self.attn_bias = self._attn_bias()
         self._setup_nomax()
         f32 = torch.float32

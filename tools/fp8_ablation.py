@@ -103,10 +103,8 @@ class Hooks:
         if kind_of(main) not in self.kinds:
             return self._orig_gemm_streams(A, Cbuf, main, txt, **kw)
         eng = self.eng
-        if kw.get("lora") is None:               # the adapters' down-projection reads the unquantised operand, as the fp8 engine path does for q/k/v
-            lo, r0 = eng._lora_t(A, main, include_txt=txt is None)
-            if lo is not None:
-                kw["lora"] = (lo, r0)
+        if kw.get("lora") is None and eng._lora_wanted(kw.get("only")):      # the adapters' down-projection reads the unquantised operand, as the fp8 engine path does for q/k/v
+            kw["lora"] = eng._lora_t(A, main, include_txt=txt is None)
         Aq = ACT[self.recipe](A.float()).to(torch.bfloat16)
         names = [main] + ([txt] if txt is not None else [])
         saved = {n: eng.w.t[n + ".w"] for n in names}
