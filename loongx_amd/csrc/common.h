@@ -141,3 +141,60 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// ---- token-stream segment lists: lx_ln_seg[] / lx_qkv_seg[] (include/lx.h) -> the by-value kernel arguments ---------------------------
+// The helpers are the entry points' segment checks, in their order within a segment; each returns the launch's extent (> 0) or the
+// negative lx_status it has set the error text for. `name` is the entry point the messages speak of.
+namespace {   // (kernel-argument types stay local to their translation unit, like the kernels that take them)
+
+struct LnSegs {   // up to 3 row segments (token streams), each with its own modulation table
+  int n;
+  int row0[3], n_rows[3], rows_per_batch[3];
+  const float* shift[3];
+  const float* scale[3];
+};
+
+// -> M, the rows of all segments together
+inline int lx_ln_segs(const char* name, const lx_ln_seg* seg, int n_seg, LnSegs& segs) {
+  segs.n = n_seg;
+  int M = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    LX_CHECK_ARG(seg[i].shift && seg[i].scale && seg[i].n_rows > 0 && seg[i].rows_per_batch > 0, "%s: bad segment %d", name, i);
+    LX_CHECK_ARG((((uintptr_t)seg[i].shift | (uintptr_t)seg[i].scale) & 15) == 0, "%s: misaligned modulation table", name);
+    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
+    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
+    M += seg[i].n_rows;
+  }
+  return M;
+}
+
+// what an entry point asks of a segment's vt_pos0 (the first slot of the stream in a V^T row)
+enum LxVtPos0 {
+  LX_VT_POS0_ANY,              // no V^T image is written
+  LX_VT_POS0_MULT64,           // a multiple of 64, of either sign
+  LX_VT_POS0_MULT64_NONNEG     // a multiple of 64, >= 0
+};
+
+// Segs: QkvSegs (rowops.hip) | QkvSegsP (precise.hip, which has no vt_pos0 member): the members they share are filled here, tile0[]
+// (the prefix sum of the segments' 64-row tiles) included; vt_pos0[] (NULL: not wanted) is wherever the caller's kernel reads it.
+// -> the tiles of all segments together
+template <class Segs>
+inline int lx_qkv_segs(const char* name, const lx_qkv_seg* seg, int n_seg, LxVtPos0 vt_rule, Segs& segs, int* vt_pos0) {
+  segs.n = n_seg;
+  int t = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    LX_CHECK_ARG(seg[i].rows_per_batch > 0, "%s: empty segment %d", name, i);
+    LX_CHECK_ARG((seg[i].cos_tab == nullptr) == (seg[i].sin_tab == nullptr), "%s: cos/sin tables must come together", name);
+    LX_CHECK_ARG(vt_rule == LX_VT_POS0_ANY || (seg[i].vt_pos0 % 64 == 0 && (vt_rule == LX_VT_POS0_MULT64 || seg[i].vt_pos0 >= 0)),
+                 "%s: vt_pos0 must be a multiple of 64", name);
+    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch;
+    segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
+    if (vt_pos0) vt_pos0[i] = seg[i].vt_pos0;
+    segs.tile0[i] = t;
+    t += (seg[i].rows_per_batch + 63) / 64;
+  }
+  segs.tile0[n_seg] = t;
+  return t;
+}
+
+}  // namespace

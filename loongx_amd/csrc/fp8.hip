@@ -15,15 +15,8 @@ __device__ __forceinline__ uint32_t pk8(float a, float b, float c, float d) {
   return (uint32_t)w;
 }
 
-struct LnSegs8 {
-  int n;
-  int row0[3], n_rows[3], rows_per_batch[3];
-  const float* shift[3];
-  const float* scale[3];
-};
-
 // one wave per row, three passes over the (L2-resident) row; Y (bf16) may be NULL
-__global__ __launch_bounds__(256) void ln_modulate_fp8_kernel(const float* __restrict__ X, int ldx, const LnSegs8 segs, int mod_ld, uint16_t* __restrict__ Y,
+__global__ __launch_bounds__(256) void ln_modulate_fp8_kernel(const float* __restrict__ X, int ldx, const LnSegs segs, int mod_ld, uint16_t* __restrict__ Y,
                                                               int ldy, uint8_t* __restrict__ Y8, int ldy8, float s8, int M, int D, float eps) {
   int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -131,16 +124,9 @@ extern "C" int lx_ln_modulate_fp8_segs(const float* X, int ldx, const lx_ln_seg*
   LX_CHECK_ARG(X && Y8 && D > 0 && D % 4 == 0 && y8_scale > 0.f, "lx_ln_modulate_fp8_segs: bad arguments");
   LX_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ldy8 % 4 == 0 && mod_ld % 4 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 7) == 0 && ((uintptr_t)Y8 & 3) == 0,
                "lx_ln_modulate_fp8_segs: leading dimensions must be multiples of 4, operands aligned");
-  LnSegs8 segs;
-  segs.n = n_seg;
-  int M = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    LX_CHECK_ARG(seg[i].shift && seg[i].scale && seg[i].n_rows > 0 && seg[i].rows_per_batch > 0, "lx_ln_modulate_fp8_segs: bad segment %d", i);
-    LX_CHECK_ARG((((uintptr_t)seg[i].shift | (uintptr_t)seg[i].scale) & 15) == 0, "lx_ln_modulate_fp8_segs: misaligned modulation table");
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-    M += seg[i].n_rows;
-  }
+  LnSegs segs;
+  const int M = lx_ln_segs("lx_ln_modulate_fp8_segs", seg, n_seg, segs);
+  if (M < 0) return M;
   hipLaunchKernelGGL(ln_modulate_fp8_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, segs, mod_ld, (uint16_t*)Y, ldy, (uint8_t*)Y8, ldy8,
                      y8_scale, M, D, eps);
   LX_LAUNCH_CHECK("lx_ln_modulate_fp8_segs");

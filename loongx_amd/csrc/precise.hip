@@ -35,14 +35,7 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict
 }
 
 // ---- LayerNorm (no affine) + AdaLN modulation, fp32 in -> bf16 hi/lo pair out. One wave per row. --------------------------------
-struct LnSegsP {
-  int n;
-  int row0[3], n_rows[3], rows_per_batch[3];
-  const float* shift[3];
-  const float* scale[3];
-};
-
-__global__ __launch_bounds__(256) void ln_modulate_split_kernel(const float* __restrict__ X, int ldx, const LnSegsP segs, int mod_ld,
+__global__ __launch_bounds__(256) void ln_modulate_split_kernel(const float* __restrict__ X, int ldx, const LnSegs segs, int mod_ld,
                                                                 uint16_t* __restrict__ Y, int ldy, int lo_off, int M, int D, float eps) {
   int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -619,16 +612,9 @@ extern "C" int lx_ln_modulate_split_segs(const float* X, int ldx, const lx_ln_se
   LX_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && mod_ld % 4 == 0 && y_lo_off % 4 == 0 && y_lo_off >= D && ldy >= y_lo_off + D,
                "lx_ln_modulate_split_segs: ldx/ldy/mod_ld/y_lo_off must be multiples of 4 and D <= y_lo_off, y_lo_off + D <= ldy");
   LX_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 7) == 0, "lx_ln_modulate_split_segs: misaligned operand");
-  LnSegsP segs;
-  segs.n = n_seg;
-  int M = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    LX_CHECK_ARG(seg[i].shift && seg[i].scale && seg[i].n_rows > 0 && seg[i].rows_per_batch > 0, "lx_ln_modulate_split_segs: bad segment %d", i);
-    LX_CHECK_ARG((((uintptr_t)seg[i].shift | (uintptr_t)seg[i].scale) & 15) == 0, "lx_ln_modulate_split_segs: misaligned modulation table");
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-    M += seg[i].n_rows;
-  }
+  LnSegs segs;
+  const int M = lx_ln_segs("lx_ln_modulate_split_segs", seg, n_seg, segs);
+  if (M < 0) return M;
   hipLaunchKernelGGL(ln_modulate_split_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, segs, mod_ld, (uint16_t*)Y, ldy,
                      y_lo_off, M, D, eps);
   LX_LAUNCH_CHECK("lx_ln_modulate_split_segs");
@@ -641,17 +627,8 @@ extern "C" int lx_qkv_prep_f32_segs(float* QKV, int ld, int q_col, int k_col, co
   LX_CHECK_ARG(QKV && n_batches > 0 && H > 0, "lx_qkv_prep_f32_segs: bad arguments");
   LX_CHECK_ARG(ld % 4 == 0 && q_col % 4 == 0 && k_col % 4 == 0 && ((uintptr_t)QKV & 15) == 0, "lx_qkv_prep_f32_segs: ld / column offsets must be multiples of 4, QKV 16-byte aligned");
   QkvSegsP segs;
-  segs.n = n_seg;
-  int t = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    LX_CHECK_ARG(seg[i].rows_per_batch > 0, "lx_qkv_prep_f32_segs: empty segment %d", i);
-    LX_CHECK_ARG((seg[i].cos_tab == nullptr) == (seg[i].sin_tab == nullptr), "lx_qkv_prep_f32_segs: cos/sin tables must come together");
-    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
-    segs.tile0[i] = t;
-    t += (seg[i].rows_per_batch + 63) / 64;
-  }
-  segs.tile0[n_seg] = t;
+  const int t = lx_qkv_segs("lx_qkv_prep_f32_segs", seg, n_seg, LX_VT_POS0_ANY, segs, nullptr);
+  if (t < 0) return t;
   hipLaunchKernelGGL(qkv_prep_f32_kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, QKV, ld, q_col, k_col, segs, eps);
   LX_LAUNCH_CHECK("lx_qkv_prep_f32_segs");
   return LX_OK;
@@ -698,19 +675,8 @@ extern "C" int lx_qkv_prep_split_segs(const float* QKV, int ld, int q_col, int k
                "lx_qkv_prep_split_segs: vt_ld %% 64, vt_lo_off %% 8 and the lo V^T image behind the hi image required");
   QkvSegsP segs;
   QkvSplitArgs a;
-  segs.n = n_seg;
-  int t = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    LX_CHECK_ARG(seg[i].rows_per_batch > 0, "lx_qkv_prep_split_segs: empty segment %d", i);
-    LX_CHECK_ARG((seg[i].cos_tab == nullptr) == (seg[i].sin_tab == nullptr), "lx_qkv_prep_split_segs: cos/sin tables must come together");
-    LX_CHECK_ARG(seg[i].vt_pos0 % 64 == 0 && seg[i].vt_pos0 >= 0, "lx_qkv_prep_split_segs: vt_pos0 must be a multiple of 64");
-    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
-    a.vt_pos0[i] = seg[i].vt_pos0;
-    segs.tile0[i] = t;
-    t += (seg[i].rows_per_batch + 63) / 64;
-  }
-  segs.tile0[n_seg] = t;
+  const int t = lx_qkv_segs("lx_qkv_prep_split_segs", seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, a.vt_pos0);
+  if (t < 0) return t;
   a.QKV = QKV; a.ld = ld; a.q_col = q_col; a.k_col = k_col; a.v_col = v_col;
   a.QK2 = (uint16_t*)QK2; a.ld2 = ld2; a.q2_col = q2_col; a.k2_col = k2_col; a.lo_off = lo_off;
   a.VT2 = (uint16_t*)VT2; a.vt_ld = vt_ld; a.vt_lo_off = vt_lo_off; a.H = H; a.eps = eps;

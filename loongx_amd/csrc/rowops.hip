@@ -10,13 +10,6 @@ namespace {
 // LayerNorm(no affine) + (1+scale)*x + shift, fp32 in -> bf16 out. One wave per row, row kept in VGPRs.
 // Reference: AdaLayerNormZero/ZeroSingle/Continuous + norm2 modulation (block.py:192-207,238-253,301,305).
 // ------------------------------------------------------------------------------------------------------
-struct LnSegs {   // up to 3 row segments (token streams), each with its own modulation table
-  int n;
-  int row0[3], n_rows[3], rows_per_batch[3];
-  const float* shift[3];
-  const float* scale[3];
-};
-
 // LM (round 5): the rows [lora_row0, lora_row0 + lora_rows) (the streams that run with the adapter on) also get their LoRA down-projection
 // T[row - lora_row0, 0..R) = Y_row . Adown[R, D]^T (R <= 16) on the matrix pipe while the workgroup's four normalised rows are at hand:
 // the rows go to LDS as the 16-bit operand images they are stored as, Adown is the MFMA "A" operand (rows = r), the four rows the "B"
@@ -743,134 +736,93 @@ __global__ void convert_kernel(void* __restrict__ dst, int dst_bf16, const void*
 
 }  // namespace
 
-static int ln_launch(const float* X, int ldx, const LnSegs& segs, int mod_ld, void* Y, int ldy, int D, float eps, void* stream,
-                     const LnLora* lora = nullptr, bool f16 = false, int* f16_ovf = nullptr) {
-  int M = 0;
-  for (int i = 0; i < segs.n; ++i) {
-    LX_CHECK_ARG(segs.shift[i] && segs.scale[i] && segs.n_rows[i] > 0 && segs.rows_per_batch[i] > 0, "lx_ln_modulate: bad segment %d", i);
-    LX_CHECK_ARG((((uintptr_t)segs.shift[i] | (uintptr_t)segs.scale[i]) & 15) == 0, "lx_ln_modulate: misaligned modulation table");
-    M += segs.n_rows[i];
-  }
+// The five lx_ln_modulate* entry points. `name` is the one that was called: it reports the segment count and f16_ovf; everything else
+// reports as lx_ln_modulate (the operands) or lx_ln_modulate_lora_segs (the adapter), whichever form was called.
+static int ln_launch(const char* name, const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D, float eps,
+                     void* stream, const LnLora* lora = nullptr, bool f16 = false, int* f16_ovf = nullptr) {
+  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "%s: 1..3 segments", name);
+  if (f16) LX_CHECK_ARG(((uintptr_t)f16_ovf & 3) == 0, "%s: f16_ovf must be 4-byte aligned", name);
+  LnSegs segs;
+  const int M = lx_ln_segs("lx_ln_modulate", seg, n_seg, segs);
+  if (M < 0) return M;
   LX_CHECK_ARG(X && Y, "lx_ln_modulate: NULL operand");
   LX_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 16384, "lx_ln_modulate: D=%d must be a multiple of 4 and <= 16384", D);
   LX_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && mod_ld % 4 == 0, "lx_ln_modulate: ldx/ldy/mod_ld must be multiples of 4");
   LX_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 7) == 0, "lx_ln_modulate: misaligned operand");
-  const dim3 grid((M + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  uint16_t* y = (uint16_t*)Y;
   if (lora) {
     LX_CHECK_ARG(D == 3072 || D == 256, "lx_ln_modulate_lora_segs: the fused down-projection exists for D = 3072 and 256 (D=%d): use lx_lora_down", D);
     LX_CHECK_ARG(lora->A && lora->T && lora->R >= 1 && lora->R <= 16 && lora->ldt >= lora->R && lora->rows > 0 && lora->row0 >= 0,
                  "lx_ln_modulate_lora_segs: bad adapter arguments (R=%d)", lora->R);
     LX_CHECK_ARG(((uintptr_t)lora->A & 15) == 0, "lx_ln_modulate_lora_segs: Adown must be 16-byte aligned");
-    if (D == 3072) {
-      if (f16) hipLaunchKernelGGL((ln_modulate_kernel<12, true, true>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, *lora, f16_ovf);
-      else hipLaunchKernelGGL((ln_modulate_kernel<12, true, false>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, *lora, (int*)nullptr);
-    } else {
-      if (f16) hipLaunchKernelGGL((ln_modulate_kernel<1, true, true>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, *lora, f16_ovf);
-      else hipLaunchKernelGGL((ln_modulate_kernel<1, true, false>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, *lora, (int*)nullptr);
-    }
-    LX_LAUNCH_CHECK("lx_ln_modulate_lora_segs");
-    return LX_OK;
   }
-  if (f16) {
-    if (D == 3072) hipLaunchKernelGGL((ln_modulate_kernel<12, false, true>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, LnLora{}, f16_ovf);
-    else if (D == 256) hipLaunchKernelGGL((ln_modulate_kernel<1, false, true>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, LnLora{}, f16_ovf);
-    else hipLaunchKernelGGL(ln_modulate_generic<true>, grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, f16_ovf);
-    LX_LAUNCH_CHECK("lx_ln_modulate_f16_segs");
-    return LX_OK;
-  }
-  if (D == 3072) hipLaunchKernelGGL((ln_modulate_kernel<12>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, LnLora{}, (int*)nullptr);
-  else if (D == 256) hipLaunchKernelGGL((ln_modulate_kernel<1>), grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, LnLora{}, (int*)nullptr);
-  else hipLaunchKernelGGL(ln_modulate_generic<false>, grid, block, 0, s, X, ldx, segs, mod_ld, y, ldy, M, D, eps, (int*)nullptr);
-  LX_LAUNCH_CHECK("lx_ln_modulate");
+  const LnLora lo = lora ? *lora : LnLora{};
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, segs, mod_ld, (uint16_t*)Y, ldy, M, D, eps, tail...);
+  };
+  auto dispatch = [&](auto lm, auto h) {      // (LM, F16) -> the kernel for this D
+    constexpr bool LM = decltype(lm)::value, F16 = decltype(h)::value;
+    if (D == 3072) launch(ln_modulate_kernel<12, LM, F16>, lo, f16_ovf);
+    else if (D == 256) launch(ln_modulate_kernel<1, LM, F16>, lo, f16_ovf);
+    else if constexpr (!LM) launch(ln_modulate_generic<F16>, f16_ovf);
+  };
+  if (lora && f16) dispatch(std::true_type{}, std::true_type{});
+  else if (lora) dispatch(std::true_type{}, std::false_type{});
+  else if (f16) dispatch(std::false_type{}, std::true_type{});
+  else dispatch(std::false_type{}, std::false_type{});
+  LX_LAUNCH_CHECK(lora ? "lx_ln_modulate_lora_segs" : f16 ? "lx_ln_modulate_f16_segs" : "lx_ln_modulate");
   return LX_OK;
 }
 
 extern "C" int lx_ln_modulate(const float* X, int ldx, const float* shift, const float* scale, int mod_ld, void* Y, int ldy,
                               int M, int D, int rows_per_batch, float eps, void* stream) {
   LX_CHECK_ARG(M > 0, "lx_ln_modulate: M must be > 0");
-  LnSegs segs;
-  segs.n = 1;
-  segs.row0[0] = 0; segs.n_rows[0] = M; segs.rows_per_batch[0] = rows_per_batch; segs.shift[0] = shift; segs.scale[0] = scale;
-  return ln_launch(X, ldx, segs, mod_ld, Y, ldy, D, eps, stream);
+  const lx_ln_seg one = {0, M, rows_per_batch, 0, shift, scale};
+  return ln_launch("lx_ln_modulate", X, ldx, &one, 1, mod_ld, Y, ldy, D, eps, stream);
 }
 
 extern "C" int lx_ln_modulate_segs(const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D,
                                    float eps, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_ln_modulate_segs: 1..3 segments");
-  LnSegs segs;
-  segs.n = n_seg;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-  }
-  return ln_launch(X, ldx, segs, mod_ld, Y, ldy, D, eps, stream);
+  return ln_launch("lx_ln_modulate_segs", X, ldx, seg, n_seg, mod_ld, Y, ldy, D, eps, stream);
 }
 
 extern "C" int lx_ln_modulate_f16_segs(const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D,
                                        float eps, int32_t* f16_ovf, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_ln_modulate_f16_segs: 1..3 segments");
-  LX_CHECK_ARG(((uintptr_t)f16_ovf & 3) == 0, "lx_ln_modulate_f16_segs: f16_ovf must be 4-byte aligned");
-  LnSegs segs;
-  segs.n = n_seg;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-  }
-  return ln_launch(X, ldx, segs, mod_ld, Y, ldy, D, eps, stream, nullptr, true, (int*)f16_ovf);
+  return ln_launch("lx_ln_modulate_f16_segs", X, ldx, seg, n_seg, mod_ld, Y, ldy, D, eps, stream, nullptr, true, (int*)f16_ovf);
 }
 
 extern "C" int lx_ln_modulate_lora_f16_segs(const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D,
                                             float eps, const void* Adown, int R, float* T, int ldt, int lora_row0, int lora_rows,
                                             int32_t* f16_ovf, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_ln_modulate_lora_f16_segs: 1..3 segments");
-  LX_CHECK_ARG(((uintptr_t)f16_ovf & 3) == 0, "lx_ln_modulate_lora_f16_segs: f16_ovf must be 4-byte aligned");
-  LnSegs segs;
-  segs.n = n_seg;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-  }
   const LnLora lo{(const uint16_t*)Adown, T, R, ldt, lora_row0, lora_rows};
-  return ln_launch(X, ldx, segs, mod_ld, Y, ldy, D, eps, stream, &lo, true, (int*)f16_ovf);
+  return ln_launch("lx_ln_modulate_lora_f16_segs", X, ldx, seg, n_seg, mod_ld, Y, ldy, D, eps, stream, &lo, true, (int*)f16_ovf);
 }
 
 extern "C" int lx_ln_modulate_lora_segs(const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D,
                                         float eps, const void* Adown, int R, float* T, int ldt, int lora_row0, int lora_rows, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_ln_modulate_lora_segs: 1..3 segments");
-  LnSegs segs;
-  segs.n = n_seg;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
-    segs.shift[i] = seg[i].shift; segs.scale[i] = seg[i].scale;
-  }
   const LnLora lo{(const uint16_t*)Adown, T, R, ldt, lora_row0, lora_rows};
-  return ln_launch(X, ldx, segs, mod_ld, Y, ldy, D, eps, stream, &lo);
+  return ln_launch("lx_ln_modulate_lora_segs", X, ldx, seg, n_seg, mod_ld, Y, ldy, D, eps, stream, &lo);
 }
 
-static int qkv_launch(void* QKV, int ld, int q_col, int k_col, int v_col, QkvSegs& segs, int n_batches, int H, float eps, void* VT,
-                      int vt_ld, void* stream, bool in_f16 = false) {
+// lx_qkv_prep and its two _segs forms: all report as lx_qkv_prep, the segment count as lx_qkv_prep_segs. vt_pos0 is looked at only when
+// a V^T image is written.
+static int qkv_launch(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches, int H, float eps,
+                      void* VT, int vt_ld, void* stream, bool in_f16 = false) {
+  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_qkv_prep_segs: 1..3 segments");
   LX_CHECK_ARG(QKV && n_batches > 0 && H > 0, "lx_qkv_prep: bad arguments");
   LX_CHECK_ARG(ld % 8 == 0 && q_col % 8 == 0 && k_col % 8 == 0 && v_col % 8 == 0, "lx_qkv_prep: ld and column offsets must be multiples of 8");
   if (VT) LX_CHECK_ARG(vt_ld % 64 == 0, "lx_qkv_prep: vt_ld must be a multiple of 64");
-  int t = 0;
-  for (int i = 0; i < segs.n; ++i) {
-    LX_CHECK_ARG(segs.rows_per_batch[i] > 0, "lx_qkv_prep: empty segment %d", i);
-    LX_CHECK_ARG((segs.cos_tab[i] == nullptr) == (segs.sin_tab[i] == nullptr), "lx_qkv_prep: cos/sin tables must come together");
-    if (VT) LX_CHECK_ARG(segs.vt_pos0[i] % 64 == 0, "lx_qkv_prep: vt_pos0 must be a multiple of 64");
-    segs.tile0[i] = t;
-    t += (segs.rows_per_batch[i] + 63) / 64;
-  }
-  segs.tile0[segs.n] = t;
+  QkvSegs segs;
+  const int t = lx_qkv_segs("lx_qkv_prep", seg, n_seg, VT ? LX_VT_POS0_MULT64 : LX_VT_POS0_ANY, segs, segs.vt_pos0);
+  if (t < 0) return t;
   bool fast = true;
   for (int i = 0; i < segs.n; ++i) fast = fast && segs.wq[i] && segs.wk[i] && segs.cos_tab[i];
-  if (in_f16) hipLaunchKernelGGL((qkv_prep_kernel<false, true>), dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col,
-                                 k_col, v_col, segs, eps, (uint16_t*)VT, vt_ld, H);
-  else if (fast) hipLaunchKernelGGL(qkv_prep_kernel<true>, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col, k_col,
-                               v_col, segs, eps, (uint16_t*)VT, vt_ld, H);
-  else hipLaunchKernelGGL(qkv_prep_kernel<false>, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col, k_col,
-                          v_col, segs, eps, (uint16_t*)VT, vt_ld, H);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col, k_col, v_col, segs, eps,
+                       (uint16_t*)VT, vt_ld, H);
+  };
+  if (in_f16) launch(qkv_prep_kernel<false, true>);
+  else if (fast) launch(qkv_prep_kernel<true>);
+  else launch(qkv_prep_kernel<false>);
   LX_LAUNCH_CHECK("lx_qkv_prep");
   return LX_OK;
 }
@@ -879,33 +831,18 @@ extern "C" int lx_qkv_prep(void* QKV, int ld, int q_col, int k_col, int v_col, i
                            const float* wq, const float* wk, float eps, const float* cos_tab, const float* sin_tab, void* VT,
                            int vt_ld, int vt_pos0, void* stream) {
   LX_CHECK_ARG(n_rows > 0 && rows_per_batch > 0 && n_rows % rows_per_batch == 0, "lx_qkv_prep: n_rows=%d must be a multiple of rows_per_batch=%d", n_rows, rows_per_batch);
-  QkvSegs segs;
-  segs.n = 1;
-  segs.row0[0] = row0; segs.rows_per_batch[0] = rows_per_batch; segs.vt_pos0[0] = vt_pos0;
-  segs.wq[0] = wq; segs.wk[0] = wk; segs.cos_tab[0] = cos_tab; segs.sin_tab[0] = sin_tab;
-  return qkv_launch(QKV, ld, q_col, k_col, v_col, segs, n_rows / rows_per_batch, H, eps, VT, vt_ld, stream);
-}
-
-static int qkv_segs_launch(bool in_f16, void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
-                           int H, float eps, void* VT, int vt_ld, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_qkv_prep_segs: 1..3 segments");
-  QkvSegs segs;
-  segs.n = n_seg;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch; segs.vt_pos0[i] = seg[i].vt_pos0;
-    segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
-  }
-  return qkv_launch(QKV, ld, q_col, k_col, v_col, segs, n_batches, H, eps, VT, vt_ld, stream, in_f16);
+  const lx_qkv_seg one = {row0, rows_per_batch, vt_pos0, 0, wq, wk, cos_tab, sin_tab};
+  return qkv_launch(QKV, ld, q_col, k_col, v_col, &one, 1, n_rows / rows_per_batch, H, eps, VT, vt_ld, stream);
 }
 
 extern "C" int lx_qkv_prep_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
                                 int H, float eps, void* VT, int vt_ld, void* stream) {
-  return qkv_segs_launch(false, QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, VT, vt_ld, stream);
+  return qkv_launch(QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, VT, vt_ld, stream);
 }
 
 extern "C" int lx_qkv_prep_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
                                       int H, float eps, void* VT, int vt_ld, void* stream) {
-  return qkv_segs_launch(true, QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, VT, vt_ld, stream);
+  return qkv_launch(QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, VT, vt_ld, stream, true);
 }
 
 static int qkv_fp8_segs_launch(bool in_f16, const void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg,
@@ -917,22 +854,14 @@ static int qkv_fp8_segs_launch(bool in_f16, const void* QKV, int ld, int q_col, 
   LX_CHECK_ARG(ld8 % 16 == 0 && vt8_ld % 64 == 0, "lx_qkv_prep_fp8_segs: ld8 %% 16 and vt8_ld %% 64 required");
   LX_CHECK_ARG(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "lx_qkv_prep_fp8_segs: scales must be positive");
   QkvSegs segs;
-  segs.n = n_seg;
-  int t = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch; segs.vt_pos0[i] = seg[i].vt_pos0;
-    segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
-    LX_CHECK_ARG(segs.rows_per_batch[i] > 0, "lx_qkv_prep_fp8_segs: empty segment %d", i);
-    LX_CHECK_ARG((segs.cos_tab[i] == nullptr) == (segs.sin_tab[i] == nullptr), "lx_qkv_prep_fp8_segs: cos/sin tables must come together");
-    LX_CHECK_ARG(segs.vt_pos0[i] % 64 == 0, "lx_qkv_prep_fp8_segs: vt_pos0 must be a multiple of 64");
-    segs.tile0[i] = t;
-    t += (segs.rows_per_batch[i] + 63) / 64;
-  }
-  segs.tile0[n_seg] = t;
-  if (in_f16) hipLaunchKernelGGL(qkv_prep_fp8_kernel<true>, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld, q_col,
-                                 k_col, v_col, segs, eps, (uint8_t*)Q8, (uint8_t*)K8, ld8, (uint8_t*)VT8, vt8_ld, H, q_scale, k_scale, v_scale);
-  else hipLaunchKernelGGL(qkv_prep_fp8_kernel<false>, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld, q_col,
-                          k_col, v_col, segs, eps, (uint8_t*)Q8, (uint8_t*)K8, ld8, (uint8_t*)VT8, vt8_ld, H, q_scale, k_scale, v_scale);
+  const int t = lx_qkv_segs("lx_qkv_prep_fp8_segs", seg, n_seg, LX_VT_POS0_MULT64, segs, segs.vt_pos0);
+  if (t < 0) return t;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld, q_col, k_col, v_col, segs, eps,
+                       (uint8_t*)Q8, (uint8_t*)K8, ld8, (uint8_t*)VT8, vt8_ld, H, q_scale, k_scale, v_scale);
+  };
+  if (in_f16) launch(qkv_prep_fp8_kernel<true>);
+  else launch(qkv_prep_fp8_kernel<false>);
   LX_LAUNCH_CHECK("lx_qkv_prep_fp8_segs");
   return LX_OK;
 }

@@ -183,6 +183,21 @@ class LaunchTimer:
 TIMER: Optional[LaunchTimer] = None
 
 
+def _timed(kind: str, cost, call) -> None:
+    """Run `call` (one launch), between two events when a timer is installed and active for this forward call.
+    cost() -> (algorithmic flops, operand + output bytes): worked out only for a bracketed launch."""
+    if TIMER is None or not TIMER.active:
+        return call()
+    s, e = TIMER.bracket(kind, *cost())
+    s.record()
+    call()
+    e.record()
+
+
+def _attn_cost(B, H, q_rows, S):
+    return lambda: (4.0 * B * H * q_rows * S * 128, 0.0)
+
+
 def gemm_workspace(device) -> torch.Tensor:
     """Zero-filled scratch for lx_gemm_bf16_ws (split-K pair plan): one per stream / engine, owned by the caller."""
     return torch.zeros(lib.lx_gemm_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -200,17 +215,12 @@ def gemm(problems: Sequence[GemmDesc], workspace: Optional[torch.Tensor] = None)
         call = lambda: check(lib.lx_gemm_bf16_ws(arr, n, workspace.data_ptr(), workspace.numel(), _stream()), "lx_gemm_bf16_ws")
     else:
         call = lambda: check(lib.lx_gemm_bf16(arr, n, _stream()), "lx_gemm_bf16")
-    if TIMER is not None and TIMER.active:
-        def _bytes(p):   # each operand read once, the output written once (the fp32 residual epilogue also reads it)
-            epi = p.epilogue & 0xff
-            out_b = 2 if epi == LX_EPI_STORE_BF16 else (8 if epi == LX_EPI_RESID_F32 else 4)
-            return 2.0 * p.M * p.K + 2.0 * p.N * p.K + float(out_b) * p.M * p.N
-        s, e = TIMER.bracket("gemm", sum(2.0 * p.M * p.N * p.K for p in problems), sum(_bytes(p) for p in problems))
-        s.record()
-        call()
-        e.record()
-        return
-    call()
+
+    def _bytes(p):   # each operand read once, the output written once (the fp32 residual epilogue also reads it)
+        epi = p.epilogue & 0xff
+        out_b = 2 if epi == LX_EPI_STORE_BF16 else (8 if epi == LX_EPI_RESID_F32 else 4)
+        return 2.0 * p.M * p.K + 2.0 * p.N * p.K + float(out_b) * p.M * p.N
+    _timed("gemm", lambda: (sum(2.0 * p.M * p.N * p.K for p in problems), sum(_bytes(p) for p in problems)), call)
 
 
 def gemm_last_plan() -> int:
@@ -222,16 +232,10 @@ def lora_down(X: torch.Tensor, Adown: torch.Tensor, T: torch.Tensor, n_split: in
     """T (slab 0) [M,R] fp32; with n_split > 1 slab s lives split_stride floats further (same row stride).
     X and Adown both bf16, or both fp16 (the operand images of the fp16-operand mode: lx_lora_down_f16)."""
     _req(T, torch.float32, "T")
-    if X.dtype == torch.float16:
-        _req(Adown, torch.float16, "Adown")
-        if not X.is_cuda:
-            raise ValueError("X: must live on the GPU (the hot path has no CPU fallback)")
-        check(lib.lx_lora_down_f16(X.data_ptr(), X.stride(0), Adown.data_ptr(), T.data_ptr(), T.stride(0), X.shape[0], X.shape[1],
-                                   Adown.shape[0], n_split, split_stride, _stream()), "lx_lora_down_f16")
-        return
-    _req(X, torch.bfloat16, "X"); _req(Adown, torch.bfloat16, "Adown")
-    check(lib.lx_lora_down(X.data_ptr(), X.stride(0), Adown.data_ptr(), T.data_ptr(), T.stride(0), X.shape[0], X.shape[1],
-                           Adown.shape[0], n_split, split_stride, _stream()), "lx_lora_down")
+    dt, nm = (torch.float16, "lx_lora_down_f16") if X.dtype == torch.float16 else (torch.bfloat16, "lx_lora_down")
+    _req(X, dt, "X"); _req(Adown, dt, "Adown")
+    check(getattr(lib, nm)(X.data_ptr(), X.stride(0), Adown.data_ptr(), T.data_ptr(), T.stride(0), X.shape[0], X.shape[1],
+                           Adown.shape[0], n_split, split_stride, _stream()), nm)
 
 
 def lora_down_terms(terms, T: torch.Tensor, slab_stride: int) -> None:
@@ -274,6 +278,31 @@ def rope_table(ids: torch.Tensor, axes=(16, 56, 56), theta: float = 10000.0, out
     return cos, sin
 
 
+def _ln_segs(segs):
+    """[(row0, n_rows, rows_per_batch, shift_tensor, scale_tensor), ...] -> lx_ln_seg[len(segs)]"""
+    arr = (L.LnSeg * len(segs))()
+    for i, (row0, n_rows, rpb, sh, sc) in enumerate(segs):
+        arr[i].row0, arr[i].n_rows, arr[i].rows_per_batch = row0, n_rows, rpb
+        arr[i].shift, arr[i].scale = sh.data_ptr(), sc.data_ptr()
+    return arr
+
+
+def _qkv_segs(segs, vt=True):
+    """[(row0, rows_per_batch, vt_pos0, wq, wk, cos, sin), ...] -> lx_qkv_seg[len(segs)]; vt=False: no V^T image, vt_pos0 = 0"""
+    arr = (L.QkvSeg * len(segs))()
+    for i, (row0, rpb, vt0, wq, wk, cos, sin) in enumerate(segs):
+        arr[i].row0, arr[i].rows_per_batch, arr[i].vt_pos0 = row0, rpb, vt0 if vt else 0
+        arr[i].wq, arr[i].wk, arr[i].cos_tab, arr[i].sin_tab = _p(wq), _p(wk), _p(cos), _p(sin)
+    return arr
+
+
+def _fill_bias(d, bias) -> None:
+    """the 3 x 3 (query segment, key segment) additive bias table of an attention descriptor; None: zeros"""
+    for i in range(3):
+        for j in range(3):
+            d.bias[i][j] = 0.0 if bias is None else float(bias[i][j])
+
+
 def ln_modulate(X, shift, scale, Y, rows_per_batch, eps=1e-6, mod_ld=None, f16_ovf=None) -> None:
     _req(X, torch.float32, "X"); _req(shift, torch.float32, "shift"); _req(scale, torch.float32, "scale")
     if Y.dtype == torch.float16:          # the fp16 operand image: the one-segment form of lx_ln_modulate_f16_segs
@@ -296,44 +325,23 @@ def ln_modulate_segs(X, segs, Y, mod_ld, eps=1e-6, lora=None, f16_ovf=None) -> N
     lora = (Adown [R, D] in Y's 16-bit format, T [rows, >= R] fp32 (row stride T.stride(0)), first row, row count): also the LoRA
     down-projection of those rows of Y, T[row - first] = Y_row . Adown^T, on the matrix pipe inside the same launch (what
     lora_down(Y[first:first+count], Adown, T) computes; D = 3072 | 256)."""
-    n = len(segs)
-    arr = (L.LnSeg * n)()
-    for i, (row0, n_rows, rpb, sh, sc) in enumerate(segs):
-        arr[i].row0, arr[i].n_rows, arr[i].rows_per_batch = row0, n_rows, rpb
-        arr[i].shift, arr[i].scale = sh.data_ptr(), sc.data_ptr()
-    if Y.dtype == torch.float16 and lora is not None:
-        A, T, r0, cnt = lora
-        _req(A, torch.float16, "Adown"); _req(T, torch.float32, "T")
-        assert A.is_contiguous() and A.shape[1] == X.shape[1] and T.shape[0] >= cnt and T.stride(1) == 1
-        check(lib.lx_ln_modulate_lora_f16_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, Y.data_ptr(), Y.stride(0), X.shape[1], eps,
-                                               A.data_ptr(), A.shape[0], T.data_ptr(), T.stride(0), r0, cnt, _p(f16_ovf), _stream()),
-              "lx_ln_modulate_lora_f16_segs")
-        return
-    if Y.dtype == torch.float16:
-        check(lib.lx_ln_modulate_f16_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, Y.data_ptr(), Y.stride(0), X.shape[1], eps, _p(f16_ovf),
-                                          _stream()), "lx_ln_modulate_f16_segs")
-        return
+    f16 = Y.dtype == torch.float16
+    nm, extra = "lx_ln_modulate" + ("_lora" if lora is not None else "") + ("_f16" if f16 else "") + "_segs", ()
     if lora is not None:
         A, T, r0, cnt = lora
-        _req(A, torch.bfloat16, "Adown"); _req(T, torch.float32, "T")
+        _req(A, torch.float16 if f16 else torch.bfloat16, "Adown"); _req(T, torch.float32, "T")
         assert A.is_contiguous() and A.shape[1] == X.shape[1] and T.shape[0] >= cnt and T.stride(1) == 1
-        check(lib.lx_ln_modulate_lora_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, Y.data_ptr(), Y.stride(0), X.shape[1], eps,
-                                           A.data_ptr(), A.shape[0], T.data_ptr(), T.stride(0), r0, cnt, _stream()), "lx_ln_modulate_lora_segs")
-        return
-    check(lib.lx_ln_modulate_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, Y.data_ptr(), Y.stride(0), X.shape[1], eps, _stream()),
-          "lx_ln_modulate_segs")
+        extra = (A.data_ptr(), A.shape[0], T.data_ptr(), T.stride(0), r0, cnt)
+    if f16:
+        extra += (_p(f16_ovf),)
+    check(getattr(lib, nm)(X.data_ptr(), X.stride(0), _ln_segs(segs), len(segs), mod_ld, Y.data_ptr(), Y.stride(0), X.shape[1], eps, *extra, _stream()), nm)
 
 
 def qkv_prep_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, VT, eps=1e-6, in_f16=False) -> None:
     """segs: list of (row0, rows_per_batch, vt_pos0, wq, wk, cos, sin); one launch. in_f16: the q / k / v columns hold IEEE fp16 (the 16-bit
     store of an fp16-operand projection without the fused epilogue); q / k are written back as bf16, V^T as bf16 either way."""
-    n = len(segs)
-    arr = (L.QkvSeg * n)()
-    for i, (row0, rpb, vt0, wq, wk, cos, sin) in enumerate(segs):
-        arr[i].row0, arr[i].rows_per_batch, arr[i].vt_pos0 = row0, rpb, vt0
-        arr[i].wq, arr[i].wk, arr[i].cos_tab, arr[i].sin_tab = _p(wq), _p(wk), _p(cos), _p(sin)
     fn, nm = (lib.lx_qkv_prep_f16in_segs, "lx_qkv_prep_f16in_segs") if in_f16 else (lib.lx_qkv_prep_segs, "lx_qkv_prep_segs")
-    check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, arr, n, n_batches, H, eps, _p(VT), VT.shape[-1] if VT is not None else 0, _stream()), nm)
+    check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, _p(VT), VT.shape[-1] if VT is not None else 0, _stream()), nm)
 
 
 def _attn_desc(Q, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale):
@@ -343,9 +351,7 @@ def _attn_desc(Q, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt
     d.q_col, d.k_col, d.o_col, d.B, d.H, d.n_seg = q_col, k_col, o_col, B, H, len(seg_len)
     for i in range(len(seg_len)):
         d.seg_row0[i], d.seg_len[i], d.seg_vt0[i] = seg_row0[i], seg_len[i], seg_vt0[i]
-    for i in range(3):
-        for j in range(3):
-            d.bias[i][j] = 0.0 if bias is None else float(bias[i][j])
+    _fill_bias(d, bias)
     d.scale = (1.0 / math.sqrt(128.0)) if scale is None else scale
     return d
 
@@ -371,15 +377,7 @@ def attn_fwd(Q, K, VT, O, *, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_v
     d.flags = flags
     d.qseg_mask = qseg_mask
     d.f16_ovf = _p(f16_ovf)               # (ATTN_O_F16: O is written as fp16, saturated; int32 device counter of clipping waves)
-    if TIMER is not None:
-        S = sum(seg_len)
-        Sq = _q_rows(seg_len, n_qseg, qseg_mask)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * Sq * S * 128)
-        s.record()
-        check(lib.lx_attn_fwd(C.byref(d), _stream()), "lx_attn_fwd")
-        e.record()
-        return
-    check(lib.lx_attn_fwd(C.byref(d), _stream()), "lx_attn_fwd")
+    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, n_qseg, qseg_mask), sum(seg_len)), lambda: check(lib.lx_attn_fwd(C.byref(d), _stream()), "lx_attn_fwd"))
 
 
 # ---- attention under a caller's mask (include/lx.h lx_attn_fwd_masked) ------------------------------------------------------------
@@ -411,9 +409,7 @@ def _seg_desc(B, H, seg_len, seg_vt0, bias) -> AttnDesc:
     d.B, d.H, d.n_seg = B, H, len(seg_len)
     for i in range(len(seg_len)):
         d.seg_len[i], d.seg_vt0[i] = seg_len[i], seg_vt0[i]
-    for i in range(3):
-        for j in range(3):
-            d.bias[i][j] = 0.0 if bias is None else float(bias[i][j])
+    _fill_bias(d, bias)
     return d
 
 
@@ -451,14 +447,8 @@ def attn_fwd_masked(Q, K, VT, O, mask, *, q_col, k_col, o_col, B, H, seg_row0, s
     m = _mask_desc(mask, workspace)
     if not prepped:
         check(lib.lx_attn_mask_prep(C.byref(d), C.byref(m), _stream()), "lx_attn_mask_prep")
-    if TIMER is not None and TIMER.active:
-        S = sum(seg_len)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * _q_rows(seg_len, n_qseg, qseg_mask) * S * 128)
-        s.record()
-        check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked")
-        e.record()
-        return workspace
-    check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked")
+    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, n_qseg, qseg_mask), sum(seg_len)),
+           lambda: check(lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), _stream()), "lx_attn_fwd_masked"))
     return workspace
 
 
@@ -473,13 +463,8 @@ FP8_Q_SCALE = 2048.0 * (1.0 / math.sqrt(128.0)) * 1.4426950408889634 / FP8_K_SCA
 def qkv_prep_fp8_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, Q8, K8, VT8, eps=1e-6, in_f16=False) -> None:
     """segs as in qkv_prep_segs; Q8 / K8: uint8 [rows, H*128]; VT8: uint8 [B, H, 128, Spad]. The 16-bit QKV buffer (bf16, or fp16 with
     in_f16) is not modified."""
-    n = len(segs)
-    arr = (L.QkvSeg * n)()
-    for i, (row0, rpb, vt0, wq, wk, cos, sin) in enumerate(segs):
-        arr[i].row0, arr[i].rows_per_batch, arr[i].vt_pos0 = row0, rpb, vt0
-        arr[i].wq, arr[i].wk, arr[i].cos_tab, arr[i].sin_tab = _p(wq), _p(wk), _p(cos), _p(sin)
     fn, nm = (lib.lx_qkv_prep_fp8_f16in_segs, "lx_qkv_prep_fp8_f16in_segs") if in_f16 else (lib.lx_qkv_prep_fp8_segs, "lx_qkv_prep_fp8_segs")
-    check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, arr, n, n_batches, H, eps, Q8.data_ptr(), K8.data_ptr(), Q8.stride(0),
+    check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, Q8.data_ptr(), K8.data_ptr(), Q8.stride(0),
              VT8.data_ptr(), VT8.shape[-1], FP8_Q_SCALE, FP8_K_SCALE, FP8_V_SCALE, _stream()), nm)
 
 
@@ -489,25 +474,13 @@ def attn_fwd_fp8(Q8, K8, VT8, O, *, o_col, B, H, seg_row0, seg_len, seg_vt0, bia
     d = _attn_desc(Q8, K8, VT8, O, 0, 0, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
     d.flags, d.f16_ovf, d.qseg_mask = flags, _p(f16_ovf), qseg_mask
     args = (C.byref(d), 1.0 / (FP8_Q_SCALE * FP8_K_SCALE), 1.0 / FP8_V_SCALE, _stream())
-    if TIMER is not None:
-        S = sum(seg_len)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * _q_rows(seg_len, 0, qseg_mask) * S * 128)
-        s.record()
-        check(lib.lx_attn_fwd_fp8(*args), "lx_attn_fwd_fp8")
-        e.record()
-        return
-    check(lib.lx_attn_fwd_fp8(*args), "lx_attn_fwd_fp8")
+    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, 0, qseg_mask), sum(seg_len)), lambda: check(lib.lx_attn_fwd_fp8(*args), "lx_attn_fwd_fp8"))
 
 
 # ---- fp8 GEMM path (include/lx.h "fp8 GEMM path") ----------------------------------------------------------------------
 def ln_modulate_fp8_segs(X, segs, Y, Y8, mod_ld, y8_scale, eps=1e-6) -> None:
     """segs as in ln_modulate_segs; Y bf16 (or None) and Y8 uint8 (e4m3 of y * y8_scale), same row indexing."""
-    n = len(segs)
-    arr = (L.LnSeg * n)()
-    for i, (row0, n_rows, rpb, sh, sc) in enumerate(segs):
-        arr[i].row0, arr[i].n_rows, arr[i].rows_per_batch = row0, n_rows, rpb
-        arr[i].shift, arr[i].scale = sh.data_ptr(), sc.data_ptr()
-    check(lib.lx_ln_modulate_fp8_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, _p(Y), Y.stride(0) if Y is not None else 0, Y8.data_ptr(),
+    check(lib.lx_ln_modulate_fp8_segs(X.data_ptr(), X.stride(0), _ln_segs(segs), len(segs), mod_ld, _p(Y), Y.stride(0) if Y is not None else 0, Y8.data_ptr(),
                                       Y8.stride(0), float(y8_scale), X.shape[1], eps, _stream()), "lx_ln_modulate_fp8_segs")
 
 
@@ -533,24 +506,14 @@ def split_bf16(src: torch.Tensor, dst: torch.Tensor, lo_off: int) -> None:
 
 
 def ln_modulate_split_segs(X, segs, Y, mod_ld, y_lo_off, eps=1e-6) -> None:
-    n = len(segs)
-    arr = (L.LnSeg * n)()
-    for i, (row0, n_rows, rpb, sh, sc) in enumerate(segs):
-        arr[i].row0, arr[i].n_rows, arr[i].rows_per_batch = row0, n_rows, rpb
-        arr[i].shift, arr[i].scale = sh.data_ptr(), sc.data_ptr()
-    check(lib.lx_ln_modulate_split_segs(X.data_ptr(), X.stride(0), arr, n, mod_ld, Y.data_ptr(), Y.stride(0), y_lo_off, X.shape[1], eps,
+    check(lib.lx_ln_modulate_split_segs(X.data_ptr(), X.stride(0), _ln_segs(segs), len(segs), mod_ld, Y.data_ptr(), Y.stride(0), y_lo_off, X.shape[1], eps,
                                         _stream()), "lx_ln_modulate_split_segs")
 
 
 def qkv_prep_f32_segs(QKV, q_col, k_col, segs, n_batches, H, eps=1e-6) -> None:
     """segs as in qkv_prep_segs (the vt_pos0 entry is ignored); QKV fp32 [M, ld], q / k normalised + rotated in place."""
     _req(QKV, torch.float32, "QKV")
-    n = len(segs)
-    arr = (L.QkvSeg * n)()
-    for i, (row0, rpb, vt0, wq, wk, cos, sin) in enumerate(segs):
-        arr[i].row0, arr[i].rows_per_batch, arr[i].vt_pos0 = row0, rpb, 0
-        arr[i].wq, arr[i].wk, arr[i].cos_tab, arr[i].sin_tab = _p(wq), _p(wk), _p(cos), _p(sin)
-    check(lib.lx_qkv_prep_f32_segs(QKV.data_ptr(), QKV.stride(0), q_col, k_col, arr, n, n_batches, H, eps, _stream()), "lx_qkv_prep_f32_segs")
+    check(lib.lx_qkv_prep_f32_segs(QKV.data_ptr(), QKV.stride(0), q_col, k_col, _qkv_segs(segs, vt=False), len(segs), n_batches, H, eps, _stream()), "lx_qkv_prep_f32_segs")
 
 
 def attn_fwd_f32(QKV, O, *, q_col, k_col, v_col, o_col, o_lo_off, B, H, seg_row0, seg_len, bias=None, scale=None) -> None:
@@ -561,18 +524,9 @@ def attn_fwd_f32(QKV, O, *, q_col, k_col, v_col, o_col, o_lo_off, B, H, seg_row0
     d.B, d.H, d.n_seg = B, H, len(seg_len)
     for i in range(len(seg_len)):
         d.seg_row0[i], d.seg_len[i] = seg_row0[i], seg_len[i]
-    for i in range(3):
-        for j in range(3):
-            d.bias[i][j] = 0.0 if bias is None else float(bias[i][j])
+    _fill_bias(d, bias)
     d.scale = (1.0 / math.sqrt(128.0)) if scale is None else scale
-    if TIMER is not None and TIMER.active:
-        S = sum(seg_len)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * S * S * 128)
-        s.record()
-        check(lib.lx_attn_fwd_f32(C.byref(d), _stream()), "lx_attn_fwd_f32")
-        e.record()
-        return
-    check(lib.lx_attn_fwd_f32(C.byref(d), _stream()), "lx_attn_fwd_f32")
+    _timed("attn", _attn_cost(B, H, sum(seg_len), sum(seg_len)), lambda: check(lib.lx_attn_fwd_f32(C.byref(d), _stream()), "lx_attn_fwd_f32"))
 
 
 def qkv_prep_split_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, QK2, q2_col, k2_col, lo_off, VT2, eps=1e-6) -> None:
@@ -580,12 +534,7 @@ def qkv_prep_split_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, QK2, q2_co
     hi at q2_col / k2_col + h*128, lo lo_off columns further) and VT2 bf16 [2, B, H, 128, Spad] (the hi and the lo V^T image)."""
     _req(QKV, torch.float32, "QKV"); _req(QK2, torch.bfloat16, "QK2"); _req(VT2, torch.bfloat16, "VT2")
     assert VT2.dim() == 5 and VT2.shape[0] == 2 and VT2.is_contiguous() and QK2.stride(1) == 1
-    n = len(segs)
-    arr = (L.QkvSeg * n)()
-    for i, (row0, rpb, vt0, wq, wk, cos, sin) in enumerate(segs):
-        arr[i].row0, arr[i].rows_per_batch, arr[i].vt_pos0 = row0, rpb, vt0
-        arr[i].wq, arr[i].wk, arr[i].cos_tab, arr[i].sin_tab = _p(wq), _p(wk), _p(cos), _p(sin)
-    check(lib.lx_qkv_prep_split_segs(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, arr, n, n_batches, H, eps, QK2.data_ptr(), QK2.stride(0),
+    check(lib.lx_qkv_prep_split_segs(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, QK2.data_ptr(), QK2.stride(0),
                                      q2_col, k2_col, lo_off, VT2.data_ptr(), VT2.shape[-1], VT2.stride(0), _stream()), "lx_qkv_prep_split_segs")
 
 
@@ -597,14 +546,7 @@ def attn_fwd_split(QK2, VT2, O, *, q_col, k_col, qk_lo_off, o_col, o_lo_off, B, 
     d = _attn_desc(QK2, QK2, VT2, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
     d.flags = flags
     args = (C.byref(d), qk_lo_off, VT2.stride(0), o_lo_off, _stream())
-    if TIMER is not None and TIMER.active:
-        S = sum(seg_len)
-        s, e = TIMER.bracket("attn", 4.0 * B * H * S * S * 128)
-        s.record()
-        check(lib.lx_attn_fwd_split(*args), "lx_attn_fwd_split")
-        e.record()
-        return
-    check(lib.lx_attn_fwd_split(*args), "lx_attn_fwd_split")
+    _timed("attn", _attn_cost(B, H, sum(seg_len), sum(seg_len)), lambda: check(lib.lx_attn_fwd_split(*args), "lx_attn_fwd_split"))
 
 
 def euler_step(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> None:
