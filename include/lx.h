@@ -26,7 +26,9 @@ extern "C" {
 
 /* ABI history:
  *  0.4.4  + lx_gemm_last_plan (which launch plan lx_gemm_bf16 / lx_gemm_bf16_ws chose); additive extension of 0.4.4 (no layout change,
- *         lx_attn_desc unchanged): + lx_attn_mask_desc, lx_attn_mask_workspace, lx_attn_mask_prep, lx_attn_fwd_masked
+ *         lx_attn_desc unchanged): + lx_attn_mask_desc, lx_attn_mask_workspace, lx_attn_mask_prep, lx_attn_fwd_masked;
+ *         a second additive extension of 0.4.4 (no layout change): + lx_qkv_prep_split_kv_segs (the key pair into an image of its own);
+ *         lx_attn_fwd_split takes n_qseg / qseg_mask and keys / V^T from buffers other than the query buffer
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -440,9 +442,21 @@ int lx_attn_fwd_f32(const lx_attn_f32_desc* d, void* stream);
 int lx_qkv_prep_split_segs(const float* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches, int H,
                            float eps, void* QK2, int ld2, int q2_col, int k2_col, int lo_off, void* VT2, int vt_ld, long long vt_lo_off,
                            void* stream);
-/* Joint attention (the lx_attn_fwd contract; n_qseg must be 0) on those pairs: d->Q / d->K / d->VT are the hi images (q_col, k_col,
- * ldq, ldk, vt_ld as in lx_attn_fwd), the lo images sit qk_lo_off columns / vt_lo_off elements further. fp32 online softmax with an
- * exact running maximum. d->O (bf16, ldo) gets the output as a pair: hi at o_col + h*128 + d, lo o_lo_off columns further (0: hi only). */
+/* The same pass with the key pair in an image of its own: q pairs into Q2 (bf16 [M, ldq2], hi at q2_col + h*128, lo lo_off columns
+ * further), k pairs into K2 (bf16 [M, ldk2], the same rows, hi at k2_col + h*128, lo lo_off columns further), V^T pairs into VT2 as above.
+ * Only the rows of the given segments of Q2 / K2 and their 64-slot tiles (vt_pos0 .. + rows_per_batch rounded up to 64, which must end
+ * inside vt_ld) of the two V^T images are written: a launch over some segments leaves the other segments' keys and V^T columns as they
+ * are (the per-layer images of a step-invariant condition stream). */
+int lx_qkv_prep_split_kv_segs(const float* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches, int H,
+                              float eps, void* Q2, int ldq2, int q2_col, void* K2, int ldk2, int k2_col, int lo_off, void* VT2, int vt_ld,
+                              long long vt_lo_off, void* stream);
+/* Joint attention (the lx_attn_fwd contract) on those pairs: d->Q / d->K / d->VT are the hi images (q_col, k_col, ldq, ldk, vt_ld as in
+ * lx_attn_fwd; K and VT may be buffers other than Q), the lo images sit qk_lo_off columns (q and k alike) / vt_lo_off elements further.
+ * fp32 online softmax with an exact running maximum (flags: 0 | LX_ATTN_Q_LOG2 | LX_ATTN_BOUNDED). d->O (bf16, ldo) gets the output as
+ * a pair: hi at o_col + h*128 + d, lo o_lo_off columns further (0: hi only). n_qseg and qseg_mask mean what they mean in lx_attn_fwd
+ * and lx_attn_fwd_masked: segments without queries serve keys and values, their rows of O (hi and lo) are not written, the grid covers
+ * the 256-row query tiles of the query segments only, and a query row's result does not depend on the subset (rejected when a segment
+ * without queries shares rows of O with a query segment). Every segment's V^T tiles must end inside vt_ld. */
 int lx_attn_fwd_split(const lx_attn_desc* d, int qk_lo_off, long long vt_lo_off, int o_lo_off, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

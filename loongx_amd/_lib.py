@@ -117,6 +117,7 @@ _SIGS = {
     "lx_qkv_prep_f32_segs": (C.c_int, [_P, _I, _I, _I, C.POINTER(QkvSeg), _I, _I, _I, _F, _P]),
     "lx_attn_fwd_f32": (C.c_int, [C.POINTER(AttnF32Desc), _P]),
     "lx_qkv_prep_split_segs": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(QkvSeg), _I, _I, _I, _F, _P, _I, _I, _I, _I, _P, _I, C.c_longlong, _P]),
+    "lx_qkv_prep_split_kv_segs": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(QkvSeg), _I, _I, _I, _F, _P, _I, _I, _P, _I, _I, _I, _P, _I, C.c_longlong, _P]),
     "lx_attn_fwd_split": (C.c_int, [C.POINTER(AttnDesc), _I, C.c_longlong, _I, _P]),
     "lx_groupnorm_workspace_bytes": (_Z, [_I, _I, _I]),
     "lx_groupnorm_silu": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _Z, _P]),

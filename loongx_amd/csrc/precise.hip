@@ -285,6 +285,7 @@ __device__ __forceinline__ int sp_vt_interleave(int key) {   // within every 16 
 struct QkvSplitArgs {
   const float* QKV; int ld, q_col, k_col, v_col;
   uint16_t* QK2; int ld2, q2_col, k2_col, lo_off;
+  uint16_t* K2; int ldk2;         // where the key pair goes: QK2 / ld2 (lx_qkv_prep_split_segs) or a key image of its own (.._kv_segs)
   uint16_t* VT2; int vt_ld; long long vt_lo_off;
   int vt_pos0[3];
   int H;
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(256) void qkv_prep_split_kernel(const QkvSplitArgs 
         uint16_t hh[8], ll[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) split2(y[i], hh[i], ll[i]);
-        uint16_t* op = a.QK2 + grow * a.ld2 + (which ? a.k2_col : a.q2_col) + h * 128 + sub * 8;
+        uint16_t* op = (which ? a.K2 + grow * a.ldk2 + a.k2_col : a.QK2 + grow * a.ld2 + a.q2_col) + h * 128 + sub * 8;
         u32x4 oh, ol;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -387,7 +388,9 @@ __global__ __launch_bounds__(256) void qkv_prep_split_kernel(const QkvSplitArgs 
 
 struct AttnSplitArgs {
   lx_attn_desc d;
-  int qt_start[4];
+  int qq_start[4];        // prefix of 256-row query tiles over the segments that HAVE queries (n_qseg / qseg_mask): the launch's items.
+                          // With every segment a query segment it is the all-segments prefix; nothing here is keyed by a tile's index
+                          // among all segments (attn_mask.hip keeps both prefixes because its prep pass's lists are)
   int qk_lo_off;          // columns from the hi to the lo image of q and k
   long long vt_lo_off;    // elements from the hi to the lo V^T image
   int o_lo_off;           // columns from the hi to the lo half of the output pair (0: hi only)
@@ -410,13 +413,16 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
   const int l31 = lane & 31, lhi = lane >> 5;
   const int BH = D.B * D.H;
   const int bh = blockIdx.x % BH;
-  const int qt = blockIdx.x / BH;
+  const int qc = blockIdx.x / BH;
   const int b = bh / D.H, h = bh % D.H;
+  // the last segment whose range starts at or before qc: a segment without queries has an empty range (its start is its successor's, or
+  // the item count behind the last query segment) and is never chosen. A query row's tile, wave and lane depend on its position in its
+  // own segment only, so its arithmetic is the same under every subset.
   int sq = 0;
 #pragma unroll
   for (int s = 1; s < 3; ++s)
-    if (s < D.n_seg && qt >= args.qt_start[s]) sq = s;
-  const int q_in_seg = (qt - args.qt_start[sq]) * QBLK + wave * 32 + l31;
+    if (s < D.n_seg && qc >= args.qq_start[s]) sq = s;
+  const int q_in_seg = (qc - args.qq_start[sq]) * QBLK + wave * 32 + l31;
   const int q_len = D.seg_len[sq];
   const bool q_valid = q_in_seg < q_len;
   const size_t q_row = (size_t)D.seg_row0[sq] + (size_t)b * q_len + min(q_in_seg, q_len - 1);
@@ -662,33 +668,61 @@ extern "C" int lx_attn_fwd_f32(const lx_attn_f32_desc* d, void* stream) {
 }
 
 
+static int lx_qkv_prep_split_impl(const char* fn, const float* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg,
+                                  int n_batches, int H, float eps, void* QK2, int ld2, int q2_col, void* K2, int ldk2, int k2_col, int lo_off,
+                                  void* VT2, int vt_ld, long long vt_lo_off, bool key_image, void* stream) {
+  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "%s: 1..3 segments", fn);
+  LX_CHECK_ARG(QKV && QK2 && K2 && VT2 && n_batches > 0 && H > 0, "%s: bad arguments", fn);
+  LX_CHECK_ARG(ld % 4 == 0 && q_col % 4 == 0 && k_col % 4 == 0 && v_col % 4 == 0 && ((uintptr_t)QKV & 15) == 0,
+               "%s: ld / column offsets must be multiples of 4, QKV 16-byte aligned", fn);
+  LX_CHECK_ARG(ld2 % 8 == 0 && q2_col % 8 == 0 && k2_col % 8 == 0 && lo_off % 8 == 0 && lo_off >= H * 128 && ((uintptr_t)QK2 & 15) == 0,
+               "%s: ld2 / q2_col / k2_col / lo_off must be multiples of 8 (lo_off >= H*128), QK2 16-byte aligned", fn);
+  LX_CHECK_ARG(ldk2 % 8 == 0 && ((uintptr_t)K2 & 15) == 0, "%s: ldk2 must be a multiple of 8, K2 16-byte aligned", fn);
+  LX_CHECK_ARG(vt_ld % 64 == 0 && vt_lo_off % 8 == 0 && vt_lo_off >= (long long)n_batches * H * 128 * vt_ld && ((uintptr_t)VT2 & 15) == 0,
+               "%s: vt_ld %% 64, vt_lo_off %% 8 and the lo V^T image behind the hi image required", fn);
+  QkvSegsP segs;
+  QkvSplitArgs a;
+  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, a.vt_pos0);
+  if (t < 0) return t;
+  if (key_image) {
+    // a launch over some segments into images that keep other segments' entries: nothing may land outside the rows and the 64-slot
+    // tiles of the segments it is given
+    LX_CHECK_ARG(q2_col >= 0 && k2_col >= 0 && ld2 >= q2_col + lo_off + H * 128 && ldk2 >= k2_col + lo_off + H * 128,
+                 "%s: q2_col / k2_col + lo_off + H*128 must fit ldq2=%d / ldk2=%d", fn, ld2, ldk2);
+    for (int i = 0; i < n_seg; ++i) {
+      const long long vt_end = (long long)seg[i].vt_pos0 + (seg[i].rows_per_batch + 63) / 64 * 64;
+      LX_CHECK_ARG(vt_end <= vt_ld, "%s: segment %d's V^T tiles end at %lld > vt_ld=%d", fn, i, vt_end, vt_ld);
+    }
+  }
+  a.QKV = QKV; a.ld = ld; a.q_col = q_col; a.k_col = k_col; a.v_col = v_col;
+  a.QK2 = (uint16_t*)QK2; a.ld2 = ld2; a.q2_col = q2_col; a.k2_col = k2_col; a.lo_off = lo_off;
+  a.K2 = (uint16_t*)K2; a.ldk2 = ldk2;
+  a.VT2 = (uint16_t*)VT2; a.vt_ld = vt_ld; a.vt_lo_off = vt_lo_off; a.H = H; a.eps = eps;
+  hipLaunchKernelGGL(qkv_prep_split_kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, a, segs);
+  LX_LAUNCH_CHECK(fn);
+  return LX_OK;
+}
+
 extern "C" int lx_qkv_prep_split_segs(const float* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
                                       int H, float eps, void* QK2, int ld2, int q2_col, int k2_col, int lo_off, void* VT2, int vt_ld,
                                       long long vt_lo_off, void* stream) {
-  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_qkv_prep_split_segs: 1..3 segments");
-  LX_CHECK_ARG(QKV && QK2 && VT2 && n_batches > 0 && H > 0, "lx_qkv_prep_split_segs: bad arguments");
-  LX_CHECK_ARG(ld % 4 == 0 && q_col % 4 == 0 && k_col % 4 == 0 && v_col % 4 == 0 && ((uintptr_t)QKV & 15) == 0,
-               "lx_qkv_prep_split_segs: ld / column offsets must be multiples of 4, QKV 16-byte aligned");
-  LX_CHECK_ARG(ld2 % 8 == 0 && q2_col % 8 == 0 && k2_col % 8 == 0 && lo_off % 8 == 0 && lo_off >= H * 128 && ((uintptr_t)QK2 & 15) == 0,
-               "lx_qkv_prep_split_segs: ld2 / q2_col / k2_col / lo_off must be multiples of 8 (lo_off >= H*128), QK2 16-byte aligned");
-  LX_CHECK_ARG(vt_ld % 64 == 0 && vt_lo_off % 8 == 0 && vt_lo_off >= (long long)n_batches * H * 128 * vt_ld && ((uintptr_t)VT2 & 15) == 0,
-               "lx_qkv_prep_split_segs: vt_ld %% 64, vt_lo_off %% 8 and the lo V^T image behind the hi image required");
-  QkvSegsP segs;
-  QkvSplitArgs a;
-  const int t = lx_qkv_segs("lx_qkv_prep_split_segs", seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, a.vt_pos0);
-  if (t < 0) return t;
-  a.QKV = QKV; a.ld = ld; a.q_col = q_col; a.k_col = k_col; a.v_col = v_col;
-  a.QK2 = (uint16_t*)QK2; a.ld2 = ld2; a.q2_col = q2_col; a.k2_col = k2_col; a.lo_off = lo_off;
-  a.VT2 = (uint16_t*)VT2; a.vt_ld = vt_ld; a.vt_lo_off = vt_lo_off; a.H = H; a.eps = eps;
-  hipLaunchKernelGGL(qkv_prep_split_kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, a, segs);
-  LX_LAUNCH_CHECK("lx_qkv_prep_split_segs");
-  return LX_OK;
+  return lx_qkv_prep_split_impl("lx_qkv_prep_split_segs", QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, QK2, ld2, q2_col, QK2, ld2,
+                                k2_col, lo_off, VT2, vt_ld, vt_lo_off, false, stream);
+}
+
+extern "C" int lx_qkv_prep_split_kv_segs(const float* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg,
+                                         int n_batches, int H, float eps, void* Q2, int ldq2, int q2_col, void* K2, int ldk2, int k2_col,
+                                         int lo_off, void* VT2, int vt_ld, long long vt_lo_off, void* stream) {
+  return lx_qkv_prep_split_impl("lx_qkv_prep_split_kv_segs", QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, Q2, ldq2, q2_col, K2, ldk2,
+                                k2_col, lo_off, VT2, vt_ld, vt_lo_off, true, stream);
 }
 
 extern "C" int lx_attn_fwd_split(const lx_attn_desc* d, int qk_lo_off, long long vt_lo_off, int o_lo_off, void* stream) {
   LX_CHECK_ARG(d && d->Q && d->K && d->VT && d->O, "lx_attn_fwd_split: NULL operand");
   LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "lx_attn_fwd_split: n_seg=%d must be 1..3", d->n_seg);
-  LX_CHECK_ARG(d->B >= 1 && d->H >= 1 && d->n_qseg == 0 && d->qseg_mask == 0, "lx_attn_fwd_split: bad B/H (n_qseg / qseg_mask are not supported here)");
+  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "lx_attn_fwd_split: bad B/H");
+  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd_split: n_qseg=%d must be 0..n_seg", d->n_qseg);
+  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd_split: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
   LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd_split: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required");
   LX_CHECK_ARG(d->q_col % 8 == 0 && d->k_col % 8 == 0 && d->o_col % 4 == 0, "lx_attn_fwd_split: column offsets must be 16-byte aligned");
   LX_CHECK_ARG(qk_lo_off % 8 == 0 && qk_lo_off >= d->H * 128 && vt_lo_off % 8 == 0 && vt_lo_off > 0 && o_lo_off % 4 == 0 && o_lo_off >= 0,
@@ -696,19 +730,33 @@ extern "C" int lx_attn_fwd_split(const lx_attn_desc* d, int qk_lo_off, long long
   AttnSplitArgs a;
   a.d = *d;
   a.qk_lo_off = qk_lo_off; a.vt_lo_off = vt_lo_off; a.o_lo_off = o_lo_off;
+  // which segments have queries, as in lx_attn_fwd: qseg_mask when given, else the first n_qseg (0: all)
+  const int qmask = d->qseg_mask != 0 ? d->qseg_mask : (1 << (d->n_qseg > 0 ? d->n_qseg : d->n_seg)) - 1;
+  for (int s = 0; s < d->n_seg; ++s) {
+    LX_CHECK_ARG(d->seg_len[s] >= 1, "lx_attn_fwd_split: empty segment %d", s);
+    LX_CHECK_ARG(d->seg_vt0[s] >= 0 && d->seg_vt0[s] % 64 == 0, "lx_attn_fwd_split: seg_vt0 must be 64-aligned");
+    const long long vt_end = (long long)d->seg_vt0[s] + (d->seg_len[s] + SP_KV - 1) / SP_KV * SP_KV;
+    LX_CHECK_ARG(vt_end <= d->vt_ld, "lx_attn_fwd_split: segment %d's V^T tiles end at %lld > vt_ld=%d", s, vt_end, d->vt_ld);
+  }
+  // "the rows of O of a segment without queries are not written" can only hold if no query segment's rows [seg_row0, + B * seg_len) share them
+  for (int s = 0; s < d->n_seg; ++s)
+    for (int q = 0; q < d->n_seg; ++q) {
+      if (((qmask >> s) & 1) || !((qmask >> q) & 1)) continue;
+      const long long s0 = d->seg_row0[s], s1 = s0 + (long long)d->B * d->seg_len[s], q0 = d->seg_row0[q], q1 = q0 + (long long)d->B * d->seg_len[q];
+      LX_CHECK_ARG(s1 <= q0 || q1 <= s0, "lx_attn_fwd_split: n_qseg / qseg_mask leave segment %d without queries, but its rows [%lld, %lld) of O overlap "
+                   "query segment %d's rows [%lld, %lld)", s, s0, s1, q, q0, q1);
+    }
   int t = 0;
   for (int s = 0; s < 3; ++s) {
-    a.qt_start[s] = t;
-    if (s < d->n_seg) {
-      LX_CHECK_ARG(d->seg_len[s] >= 1, "lx_attn_fwd_split: empty segment %d", s);
-      LX_CHECK_ARG(d->seg_vt0[s] % 64 == 0, "lx_attn_fwd_split: seg_vt0 must be 64-aligned");
+    a.qq_start[s] = t;
+    if (s < d->n_seg && ((qmask >> s) & 1)) {
       bool any = false;
       for (int k = 0; k < d->n_seg; ++k) any |= d->bias[s][k] > -1e37f;
       LX_CHECK_ARG(any, "lx_attn_fwd_split: query segment %d is masked from every key segment", s);
       t += (d->seg_len[s] + 255) / 256;
     }
   }
-  a.qt_start[3] = t;
+  a.qq_start[3] = t;
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_Q_LOG2 | LX_ATTN_BOUNDED)) == 0 && (!(d->flags & LX_ATTN_BOUNDED) || (d->flags & LX_ATTN_Q_LOG2)),
                "lx_attn_fwd_split: flags=%d: unknown bit, or LX_ATTN_BOUNDED without LX_ATTN_Q_LOG2", d->flags);
   if (d->flags & LX_ATTN_BOUNDED) hipLaunchKernelGGL(attn_split_kernel<true>, dim3(t * d->B * d->H), dim3(512), 0, (hipStream_t)stream, a);

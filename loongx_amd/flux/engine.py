@@ -168,6 +168,7 @@ class DiTEngine:
         self.cond_cached = False         # the per-layer images hold this conditioning's condition keys / values
         self.cond_skip = False           # the forward being enqueued runs without the condition rows
         self.KC = self.VTC = None        # [layers, M, D] keys / [layers, B, H, 128, vt_ld] V^T, allocated on first use
+        self.KC2 = self.VTC2 = None      # precise mode's: [layers, M, 2D] key pairs (hi | lo) / [layers, 2, B, H, 128, vt_ld] V^T pairs
         # (Round 5 removed three measured-negative options that lived here as environment switches: the q/k/v adapters' down-projection
         # inside ln_modulate (LX_LN_LORA: -1.1 %; it could absorb the 57 launches per step that read the AdaLN-normalised stream, not the 75
         # that read an attention output or a GELU hidden), adapter rows on merged weights W' = W + s B A (LX_LORA_MERGE: +11.5 GB, the GEMMs
@@ -231,7 +232,7 @@ class DiTEngine:
         self.graphs = {}
         self.shape = (B, T, N, C)
         self.cond_ready = False
-        self.KC = self.VTC = None                                  # per-layer key / V^T images of the condition cache: shape-bound
+        self.KC = self.VTC = self.KC2 = self.VTC2 = None          # per-layer key / V^T images of the condition cache: shape-bound
         self.cond_cache = self.cond_cached = False
         self.XN2 = self.Y32 = self.YA = self.lat2 = None          # precise-mode buffers, allocated by _setup_precise()
         self.XN8 = self.Y8 = None                                  # fp8-GEMM operand images, allocated by _setup_fp8()
@@ -1154,17 +1155,35 @@ class DiTEngine:
         self._launch_streams(desc, self.gemm_ws(), main, txt, only=only, lora=lora, **kw)
         return lora
 
-    def _attention_p(self, wq, wk, wq_txt, wk_txt) -> None:
-        """fp32 q / k / v in Y32 = [k | v | q]: per-head RMSNorm + RoPE in fp32, fp32 attention, output pair into YA's attn columns."""
+    def _attention_p(self, wq, wk, wq_txt, wk_txt, layer: Optional[int] = None, img_only: bool = False) -> None:
+        """fp32 q / k / v in Y32 = [k | v | q]: per-head RMSNorm + RoPE in fp32, fp32 attention, output pair into YA's attn columns.
+        layer: the block's index among all blocks, for the per-layer images of the condition cache. img_only: only the image segment has
+        queries (the last single block of a forward; split-bf16 attention only -- the exact-fp32 kernel has no query-segment subset)."""
         D, H, B = self.cfg.inner_dim, self.cfg.num_attention_heads, self.B
-        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(self._streams(), (wq, wk, wq_txt, wk_txt))
         if self.precise_attn_split:
             # split-bf16 attention: hi.hi + hi.lo + lo.hi on the bf16 MFMA (3/16 of the fp32-MFMA cost), fp32 softmax
-            ops.qkv_prep_split_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, q2_col=2 * D, k2_col=0, lo_off=D, VT2=self.VT2)
-            ops.attn_fwd_split(self.QK2, self.VT2, self.YA, q_col=2 * D, k_col=0, qk_lo_off=D, o_col=0, o_lo_off=5 * D, B=B, H=H,
+            cached = self.cond_cache and layer is not None
+            qsegs = self._qsegs(self._streams(), wq, wk, wq_txt, wk_txt)          # the prep pass: the streams with rows in this forward
+            streams = self._all_streams() if cached else self._streams()      # key / value segments
+            seg_row0, seg_len, seg_vt0, bias, _ = self._attn_segments(streams)
+            kw, vt = {}, self.VT2
+            if cached:
+                # k and V^T pairs of this forward's streams into the layer's images (q into the shared QK2): the condition stream's part is
+                # written by the first forward of a conditioning and left alone by the cond_skip forwards, which read it from there
+                vt = self.VTC2[layer]
+                ops.qkv_prep_split_kv_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, 2 * D, self.KC2[layer], 0, D, vt)
+                kw["K"] = self.KC2[layer]
+            else:
+                ops.qkv_prep_split_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, q2_col=2 * D, k2_col=0, lo_off=D, VT2=vt)
+            if img_only:
+                kw["qseg_mask"] = 1 << [s.name for s in streams].index("img")
+            elif cached and self.cond_skip:
+                kw["n_qseg"] = len(self._streams())
+            ops.attn_fwd_split(self.QK2, vt, self.YA, q_col=2 * D, k_col=0, qk_lo_off=D, o_col=0, o_lo_off=5 * D, B=B, H=H,
                                seg_row0=seg_row0, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias,
-                               flags=(ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0)
+                               flags=(ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0, **kw)
             return
+        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(self._streams(), (wq, wk, wq_txt, wk_txt))
         ops.qkv_prep_f32_segs(self.Y32, 2 * D, 0, qsegs, B, H)
         ops.attn_fwd_f32(self.Y32, self.YA, q_col=2 * D, k_col=0, v_col=D, o_col=0, o_lo_off=5 * D, B=B, H=H, seg_row0=seg_row0,
                          seg_len=seg_len, bias=bias)
@@ -1177,7 +1196,7 @@ class DiTEngine:
         p = f"d{i}"
         self._ln_p(base, 0, D)
         self._gemm_streams_p(self.XN2, D, D, self.Y32, p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_F32, lora_mod_cols=D, lora_toff_max=2)
-        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
+        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"], layer=i)
         gate = {s_: base[s_] + 2 * D for s_ in base}
         lora = self._gemm_streams_p(self.YA, D, 5 * D, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
         if self.C and self.model_config.get("add_cond_attn", False):                          # block.py:233-234
@@ -1205,7 +1224,7 @@ class DiTEngine:
         only = ("img",) if image_out_only else None
         self._gemm_streams_p(self.XN2, D, D, self.YA[:, D:], p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, c_lo_off=5 * D,
                              w_rows=self._every_stream(slice(3 * D, 7 * D)), t_col0=3 * r, only=only, lora=lora)
-        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
+        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"], layer=cfg.num_layers + j, img_only=image_out_only)
         gate = {s_: b + 2 * D for s_ in base}
         self._gemm_streams_p(self.YA, 5 * D, 5 * D, self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate, only=only)
 
@@ -1219,7 +1238,6 @@ class DiTEngine:
             ops.convert(lat, latents.reshape(self.B * self.N, -1).contiguous())
             self._embed(lat, "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora)
         self.rows(self.X, "txt").copy_(self.X_txt_init)
-        # (cond_skip is never set in precise mode: _qkv_epilogue() is False there, so _cond_cache_ok() is)
         if self.C and not self.cond_skip:
             self.rows(self.X, "cond").copy_(self.X_cond_init)
         if mods_ready:                      # self.mods already holds this step's row of the prepare_schedule() table
@@ -1273,8 +1291,20 @@ class DiTEngine:
         timed = ops.TIMER is not None and ops.TIMER.next_call()      # event brackets need the eager launch path
         self.cond_cache = self._cond_cache_ok()
         skip = self.cond_cache and self.cond_cached            # the condition stream's keys / values of this conditioning are cached
-        if self.cond_cache and self.KC is None:                # per-layer key / V^T images (outside any capture)
-            nl = self.cfg.num_layers + self.cfg.num_single_layers
+        nl = self.cfg.num_layers + self.cfg.num_single_layers
+        # (one set at a time: an engine that alternates between bf16 and precise conditionings drops the other mode's images -- and the
+        #  step graphs that hold their addresses -- when it allocates this mode's)
+        if self.cond_cache and self.precise:                   # per-layer key / V^T pair images (outside any capture)
+            if self.KC2 is None:
+                if self.KC is not None:
+                    self.KC = self.VTC = None
+                    self.graphs = {}
+                self.KC2 = torch.zeros(nl, self.M, 2 * self.cfg.inner_dim, dtype=torch.bfloat16, device=self.device)
+                self.VTC2 = torch.zeros((nl, 2) + tuple(self.VT.shape), dtype=torch.bfloat16, device=self.device)
+        elif self.cond_cache and self.KC is None:              # per-layer key / V^T images (outside any capture)
+            if self.KC2 is not None:
+                self.KC2 = self.VTC2 = None
+                self.graphs = {}
             self.KC = torch.zeros(nl, self.M, self.cfg.inner_dim, dtype=torch.bfloat16, device=self.device)
             self.VTC = torch.zeros((nl,) + tuple(self.VT.shape), dtype=torch.bfloat16, device=self.device)
         if not self.use_graph or timed:
@@ -1324,9 +1354,11 @@ class DiTEngine:
 
     def _cond_cache_ok(self) -> bool:
         """The condition stream is step-invariant and this kernel set can keep its keys / values per layer: condition queries
-        masked from text and image keys (block.py:106-120), the fused projection epilogue in use (it writes the per-layer
-        images), no add_cond_attn (which also needs the condition stream's attention OUTPUT every step)."""
-        if (not (self.cond_cache_enabled and self.C and self._qkv_epilogue()) or self.model_config.get("add_cond_attn", False)
+        masked from text and image keys (block.py:106-120), something that writes the per-layer images -- the fused projection
+        epilogue, or in precise mode the split-bf16 attention's prep pass (LX_PRECISE_ATTN=f32 recomputes: that kernel reads fp32 q / k / v
+        from one buffer) --, no add_cond_attn (which also needs the condition stream's attention OUTPUT every step)."""
+        writes = self.precise_attn_split if self.precise else self._qkv_epilogue()
+        if (not (self.cond_cache_enabled and self.C and writes) or self.model_config.get("add_cond_attn", False)
                 or self.model_config.get("attn_fp8", False)):          # (the per-layer images are bf16: the fp8 attention recomputes)
             return False
         ab = self.attn_bias["cond"]

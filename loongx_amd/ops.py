@@ -538,15 +538,29 @@ def qkv_prep_split_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, QK2, q2_co
                                      q2_col, k2_col, lo_off, VT2.data_ptr(), VT2.shape[-1], VT2.stride(0), _stream()), "lx_qkv_prep_split_segs")
 
 
+def qkv_prep_split_kv_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, Q2, q2_col, K2, k2_col, lo_off, VT2, eps=1e-6) -> None:
+    """qkv_prep_split_segs with the key pair in an image of its own: q pairs into Q2 (hi at q2_col), k pairs into the same rows of K2
+    bf16 [M, ldk] (hi at k2_col), both lo halves lo_off columns further; VT2 as there. Rows and V^T tiles of other segments stay as they are."""
+    _req(QKV, torch.float32, "QKV"); _req(Q2, torch.bfloat16, "Q2"); _req(K2, torch.bfloat16, "K2"); _req(VT2, torch.bfloat16, "VT2")
+    assert VT2.dim() == 5 and VT2.shape[0] == 2 and VT2.is_contiguous() and Q2.stride(1) == 1 and K2.stride(1) == 1
+    check(lib.lx_qkv_prep_split_kv_segs(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, Q2.data_ptr(),
+                                        Q2.stride(0), q2_col, K2.data_ptr(), K2.stride(0), k2_col, lo_off, VT2.data_ptr(), VT2.shape[-1], VT2.stride(0),
+                                        _stream()), "lx_qkv_prep_split_kv_segs")
+
+
 def attn_fwd_split(QK2, VT2, O, *, q_col, k_col, qk_lo_off, o_col, o_lo_off, B, H, seg_row0, seg_len, seg_vt0, bias=None, scale=None,
-                   flags=0) -> None:
+                   flags=0, K=None, VT=None, n_qseg=0, qseg_mask=0) -> None:
     """Precise-mode attention on the bf16 matrix pipe: q / k pairs in QK2 (hi at q_col / k_col, lo qk_lo_off columns further), the two V^T
-    images in VT2 [2, B, H, 128, Spad]; O bf16 gets the output pair (hi at o_col, lo o_lo_off columns further)."""
-    _req(QK2, torch.bfloat16, "QK2"); _req(VT2, torch.bfloat16, "VT2"); _req(O, torch.bfloat16, "O")
-    d = _attn_desc(QK2, QK2, VT2, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
-    d.flags = flags
-    args = (C.byref(d), qk_lo_off, VT2.stride(0), o_lo_off, _stream())
-    _timed("attn", _attn_cost(B, H, sum(seg_len), sum(seg_len)), lambda: check(lib.lx_attn_fwd_split(*args), "lx_attn_fwd_split"))
+    images in VT2 [2, B, H, 128, Spad]; O bf16 gets the output pair (hi at o_col, lo o_lo_off columns further).
+    K / VT: the key pairs (bf16 [M, ldk], hi at k_col) / the V^T images ([2, B, H, 128, Spad]) when they live elsewhere (default: QK2 / VT2);
+    n_qseg / qseg_mask as in attn_fwd."""
+    K, VT = QK2 if K is None else K, VT2 if VT is None else VT
+    _req(QK2, torch.bfloat16, "QK2"); _req(K, torch.bfloat16, "K"); _req(VT, torch.bfloat16, "VT"); _req(O, torch.bfloat16, "O")
+    assert VT.dim() == 5 and VT.shape[0] == 2 and VT.is_contiguous()
+    d = _attn_desc(QK2, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
+    d.flags, d.n_qseg, d.qseg_mask = flags, n_qseg, qseg_mask
+    args = (C.byref(d), qk_lo_off, VT.stride(0), o_lo_off, _stream())
+    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, n_qseg, qseg_mask), sum(seg_len)), lambda: check(lib.lx_attn_fwd_split(*args), "lx_attn_fwd_split"))
 
 
 def euler_step(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> None:
