@@ -418,7 +418,8 @@ int lx_qkv_prep_f32_segs(float* QKV, int ld, int q_col, int k_col, const lx_qkv_
 /* Joint attention (the lx_attn_fwd contract: up to 3 token segments, additive (query segment, key segment) bias, -INFINITY masks
  * a pair) with fp32 q / k / v read from one [M, ld] buffer at q_col / k_col / v_col (head h at + h*128), exact fp32 products and
  * accumulation on v_mfma_f32_32x32x2_f32, fp32 online softmax. O (bf16, ldo) gets the output as a hi/lo pair: hi at
- * o_col + h*128 + d, lo o_lo_off columns further (o_lo_off = 0: hi only). */
+ * o_col + h*128 + d, lo o_lo_off columns further (o_lo_off = 0: hi only). Every segment has queries: a segment whose bias row is
+ * -INFINITY against every key segment (the reference's softmax of nothing: NaN) is rejected before the launch, as in lx_attn_fwd_split. */
 typedef struct lx_attn_f32_desc {
   const float* QKV; int32_t ld, q_col, k_col, v_col;
   void* O; int32_t ldo, o_col, o_lo_off;

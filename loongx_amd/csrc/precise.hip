@@ -658,6 +658,12 @@ extern "C" int lx_attn_fwd_f32(const lx_attn_f32_desc* d, void* stream) {
     t += (d->seg_len[i] + 127) / 128;
   }
   a.qtile0[d->n_seg] = t;
+  // every segment has queries here: a bias row of -inf only would leave its rows without a single key (softmax of nothing)
+  for (int i = 0; i < d->n_seg; ++i) {
+    bool any = false;
+    for (int j = 0; j < d->n_seg; ++j) any |= d->bias[i][j] > -1e37f;
+    LX_CHECK_ARG(any, "lx_attn_fwd_f32: query segment %d is masked from every key segment", i);
+  }
   const float log2e = 1.4426950408889634f;
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) a.bias[i][j] = d->bias[i][j] * log2e;        // -inf stays -inf

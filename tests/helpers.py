@@ -227,3 +227,75 @@ def duan_tie_case(seed=3):
     scale = torch.tensor([1.0, 2.0, 0.5, 3.0]).view(1, 4, 1)
     x = (x[:, :4] * scale).repeat(1, 4, 1).contiguous()
     return d, x, c, keep_k
+
+
+# ------------------------------------------------------------------------------------------------ precise attention, float64
+# The reference of tests/test_precise_attn_tiles_gpu.py (tests/test_precise_attn_ref_cpu.py pins it to torch's own SDPA on the CPU).
+VT_PERM16 = (0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15)     # slot j of every 16 holds key VT_PERM16[j] (an involution)
+
+
+def seg_edges(lens):
+    e = [0]
+    for L in lens:
+        e.append(e[-1] + L)
+    return e
+
+
+def seg_attn_ref(q, k, v, lens, bias, factor):
+    """Joint attention over the concatenated segments in float64: softmax_k(factor * q.k + bias[query segment][key segment]) v, natural-log
+    units, -inf masks a pair (a row masked from every key comes out NaN, as torch's softmax gives it). q, k, v [..., S, 128], S = sum(lens)."""
+    e = seg_edges(lens)
+    m = torch.zeros(e[-1], e[-1], dtype=torch.float64, device=q.device)
+    for i in range(len(lens)):
+        for j in range(len(lens)):
+            m[e[i]:e[i + 1], e[j]:e[j + 1]] = float(bias[i][j])
+    s = torch.matmul(q.double(), k.double().transpose(-1, -2)) * factor + m
+    return torch.matmul(torch.softmax(s, -1), v.double())
+
+
+def vt_deinterleave(vt, lens, vt0):
+    """V^T image [..., 128, Spad] (segment s at slots vt0[s] .., keys in the 16-key order [0-3, 8-11, 4-7, 12-15]) -> v [..., S, 128] in
+    key order over the concatenated segments."""
+    perm = torch.tensor(VT_PERM16)
+    idx = torch.cat([p0 + (torch.arange(L) & ~15) + perm[torch.arange(L) & 15] for L, p0 in zip(lens, vt0)])
+    return vt[..., idx.to(vt.device)].transpose(-1, -2)
+
+
+def bf16_pair(x):
+    """(hi, lo) = (bf16(x), bf16(x - hi)) of an fp32 tensor, as fp32: what the split producers write."""
+    hi = x.to(torch.bfloat16).float()
+    return hi, (x - hi).to(torch.bfloat16).float()
+
+
+NEAR_BOUND_TARGET = 90.0      # the constructed |score| in log2 units; lx.h's contract for LX_ATTN_BOUNDED is <= 100
+NEAR_BOUND_LENS = (70, 200)
+# (query segment, query position, key segment, key position, sign): the key of head 0 there is made parallel to that query; the keys sit
+# in a first tile, at a 64-key tile's last key, in a ragged last tile and in the second segment
+NEAR_BOUND_PAIRS = ((0, 3, 0, 63, 1.0), (0, 40, 1, 199, -1.0), (1, 5, 0, 69, -1.0), (1, 150, 1, 17, 1.0))
+
+
+def near_bound_qkv(q_factor, seed=29):
+    """fp32 [k | v | q] rows (B = 1, H = 2, segments NEAR_BOUND_LENS; q already carries q_factor = scale * log2 e) in which, for every
+    entry of NEAR_BOUND_PAIRS, q.k of head 0 is sign * NEAR_BOUND_TARGET log2 units. Every other score stays far smaller: such a key is
+    ~5.5x a random key's length, so the other queries see it at ~8 +- and at most ~35."""
+    H, D = 2, 256
+    g = torch.Generator().manual_seed(seed)
+    buf = torch.randn(sum(NEAR_BOUND_LENS), 3 * D, generator=g)
+    buf[:, 2 * D:] *= q_factor
+    for sq, qp, sk, kp, sign in NEAR_BOUND_PAIRS:
+        q = buf[seg_edges(NEAR_BOUND_LENS)[sq] + qp, 2 * D:2 * D + 128].double()
+        buf[seg_edges(NEAR_BOUND_LENS)[sk] + kp, :128] = (sign * NEAR_BOUND_TARGET / float(q @ q) * q).float()
+    return buf
+
+
+def max_abs_score_log2(q, k, lens, bias):
+    """max over all (query, key) pairs of |q.k + bias * log2 e| in float64 (q carries scale * log2 e); q, k [..., S, 128]. Pairs masked
+    by -inf are skipped by the kernel and do not count."""
+    e = seg_edges(lens)
+    s = torch.matmul(q.double(), k.double().transpose(-1, -2))
+    worst = 0.0
+    for i in range(len(lens)):
+        for j in range(len(lens)):
+            if bias[i][j] != float("-inf"):
+                worst = max(worst, float((s[..., e[i]:e[i + 1], e[j]:e[j + 1]] + bias[i][j] * 1.4426950408889634).abs().max()))
+    return worst

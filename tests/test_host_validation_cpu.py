@@ -1,4 +1,4 @@
-"""CPU-only: what the ln-modulate and qkv-prep entry points reject on the host, which status they return and the complete
+"""CPU-only: what the ln-modulate, qkv-prep and precise attention entry points reject on the host, which status they return and the complete
 lx_last_error() text, check order included. Every call here is refused before anything is launched (fake, aligned addresses:
 nothing dereferences them), so a call that would pass validation never appears -- where an entry point ACCEPTS a value that
 another one rejects, the accepting call carries a later defect (an empty segment 1) and the test pins that later message."""
@@ -328,3 +328,52 @@ def test_qkv_prep_single_segment_form():
     _rejected(_qkv_plain(vt_pos0=32), "lx_qkv_prep: vt_pos0 must be a multiple of 64")
     _rejected(_qkv_plain(vt_pos0=32, sin=None), "lx_qkv_prep: cos/sin tables must come together")
     _rejected(_qkv_plain(ld=772, vt_ld=96, vt_pos0=32), "lx_qkv_prep: ld and column offsets must be multiples of 8")
+
+
+# ---- precise attention: a query segment without a single key ------------------------------------------------------------------------
+NINF = float("-inf")
+DEAD2 = [[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [NINF, NINF, NINF]]
+
+
+def _attn_f32(bias, n_seg=3, seg_len=(40, 100, 70), o_lo_off=256):
+    d = _lib.AttnF32Desc()
+    d.QKV = d.O = A
+    d.ld, d.q_col, d.k_col, d.v_col = 768, 512, 0, 256
+    d.ldo, d.o_col, d.o_lo_off = 512, 0, o_lo_off
+    d.B, d.H, d.n_seg = 2, 2, n_seg
+    for i, (r, L) in enumerate(zip((0, 80, 280), seg_len)):
+        d.seg_row0[i], d.seg_len[i] = r, L
+    for i in range(3):
+        for j in range(3):
+            d.bias[i][j] = bias[i][j]
+    d.scale = 0.088
+    return _lib.lib.lx_attn_fwd_f32(C.byref(d), None)
+
+
+def _attn_split(bias, n_seg=3):
+    d = _lib.AttnDesc()
+    d.Q = d.K = d.VT = d.O = A
+    d.ldq = d.ldk = 1024
+    d.ldo, d.vt_ld = 512, 320
+    d.q_col, d.k_col, d.o_col, d.B, d.H, d.n_seg = 512, 0, 0, 2, 2, n_seg
+    for i, (r, L, v) in enumerate(zip((0, 80, 280), (40, 100, 70), (0, 64, 192))):
+        d.seg_row0[i], d.seg_len[i], d.seg_vt0[i] = r, L, v
+    for i in range(3):
+        for j in range(3):
+            d.bias[i][j] = bias[i][j]
+    d.scale = 0.088
+    return _lib.lib.lx_attn_fwd_split(C.byref(d), 256, 2 * 2 * 128 * 320, 256, None)
+
+
+def test_precise_attention_refuses_a_query_segment_masked_from_every_key():
+    """Both precise attention entry points, the same message, before any launch (the reference's softmax of such a row is NaN; the engine's
+    bias table always keeps the diagonal). lx_attn_fwd_f32 has no query-segment subset: every segment is a query segment."""
+    _rejected(_attn_split(DEAD2), "lx_attn_fwd_split: query segment 2 is masked from every key segment")
+    _rejected(_attn_f32(DEAD2), "lx_attn_fwd_f32: query segment 2 is masked from every key segment")
+    dead0 = [[NINF, NINF, NINF], [0.0, 0.0, 0.0], [NINF, NINF, NINF]]
+    _rejected(_attn_f32(dead0), "lx_attn_fwd_f32: query segment 0 is masked from every key segment")
+    # columns of segments past n_seg do not count as keys; rows past n_seg are not looked at
+    _rejected(_attn_f32([[0.0, 0.0, 0.0], [NINF, NINF, 0.0], [0.0, 0.0, 0.0]], n_seg=2), "lx_attn_fwd_f32: query segment 1 is masked from every key segment")
+    _rejected(_attn_f32([[0.0, NINF, 0.0], [NINF, 0.0, 0.0], DEAD2[2]], n_seg=2, seg_len=(40, 0, 70)), "lx_attn_fwd_f32: empty segment 1")
+    # the earlier checks still come first
+    _rejected(_attn_f32(DEAD2, o_lo_off=258), "lx_attn_fwd_f32: ldo / o_col / o_lo_off must be multiples of 4")

@@ -412,6 +412,29 @@ def test_precise_forward_matches_reference_goldens():
     assert 5e-4 < e16 < 2.5e-2
 
 
+TOL_F32_VS_SPLIT = 6e-6      # 2 x the 3.08e-6 measured on MI355X between the two forwards below (each 1.4e-5 from the goldens)
+
+
+def test_precise_forward_on_the_exact_fp32_attention_kernel(monkeypatch):
+    """LX_PRECISE_ATTN=f32: the same forward with every attention on lx_attn_fwd_f32 (fp32 MFMA) instead of lx_attn_fwd_split, against
+    the same reference goldens at the same tolerance, and against the split-path forward on the same inputs."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    G = load("flux_tiny.npz")
+    tr = tiny_transformer()
+    eng = _engine(tr)
+    split = _run(eng, G)
+    assert eng.precise_attn_split
+    monkeypatch.setenv("LX_PRECISE_ATTN", "f32")
+    eng32 = _engine(tr)
+    f32 = _run(eng32, G)
+    assert not eng32.precise_attn_split
+    e_gold, e_split = relerr(f32, G["fwd_cond"]), relerr(f32, split)
+    print(f"PRECISE_F32_ENGINE vs goldens {e_gold:.3e} (split path {relerr(split, G['fwd_cond']):.3e}); vs split path {e_split:.3e}")
+    assert e_gold < TOL_P
+    assert 0.0 < e_split < TOL_F32_VS_SPLIT                           # two different kernels: not bit-equal, but both fp32-class
+
+
 @pytest.mark.parametrize("mc,cf", [({"union_cond_attn": False}, None), ({"independent_condition": True}, None), ({}, 0.5),
                                    ({"latent_lora": True}, None), ({"add_cond_attn": True}, None)])
 def test_precise_model_config_modes(mc, cf):
