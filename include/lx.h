@@ -29,6 +29,8 @@ extern "C" {
  *         lx_attn_desc unchanged): + lx_attn_mask_desc, lx_attn_mask_workspace, lx_attn_mask_prep, lx_attn_fwd_masked;
  *         a second additive extension of 0.4.4 (no layout change): + lx_qkv_prep_split_kv_segs (the key pair into an image of its own);
  *         lx_attn_fwd_split takes n_qseg / qseg_mask and keys / V^T from buffers other than the query buffer
+ *         a third additive extension of 0.4.4 (no layout change): + lx_qkv_prep_kv_segs, lx_qkv_prep_kv_f16in_segs (the 16-bit RMSNorm + RoPE +
+ *         V^T pass with the keys in an image of their own)
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -287,6 +289,21 @@ int lx_qkv_prep_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const l
  * q and k are read as fp16 and written back in place as bf16 (what lx_attn_fwd reads), V^T gets bf16(v). block.py:38-41,60-67,74-78,92-99. */
 int lx_qkv_prep_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
                            int H, float eps, void* VT, int vt_ld, void* stream);
+
+/* lx_qkv_prep_segs with the keys in an image of their own: the same arithmetic (per-head RMSNorm + RoPE of q and k in fp32, one bf16
+ * rounding), q written in place into QKV, k written as bf16 into the same rows of K2 (bf16 [M, ldk2], head h at column k2_col + h*128;
+ * ldk2, k2_col % 8 == 0, k2_col + H*128 <= ldk2) -- the k columns of QKV are NOT modified --, V^T into VT (required) in the layout above.
+ * Only the rows of the given segments of K2 and their own 64-slot tiles of VT (vt_pos0 .. + rows_per_batch rounded up to 64, vt_pos0 >= 0,
+ * which must end inside vt_ld; the tail of a segment's last tile is zero-filled) are written: a launch over some segments leaves the other
+ * segments' keys and V^T columns as they are (the per-layer images of a step-invariant condition stream -- model_config
+ * independent_condition / union_cond_attn = False -- on stream lengths, or with callers, that LX_EPI_QKV's qkv_k does not serve). The
+ * contract of lx_qkv_prep_split_kv_segs, for the bf16 attention kernel. The fp8 pass (lx_qkv_prep_fp8_segs) has always had this form: K8 and
+ * VT8 are pointers of their own, and it writes only the launched segments' rows and tiles of them. */
+int lx_qkv_prep_kv_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
+                        int H, float eps, void* K2, int ldk2, int k2_col, void* VT, int vt_ld, void* stream);
+/* The same reading fp16 q / k / v columns (see lx_qkv_prep_f16in_segs): q is written back in place as bf16, the fp16 k columns stay */
+int lx_qkv_prep_kv_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
+                              int H, float eps, void* K2, int ldk2, int k2_col, void* VT, int vt_ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Joint attention over up to 3 token segments [text | image | condition] -- replaces

@@ -239,9 +239,14 @@ __device__ __forceinline__ u32x4 f16x8_to_bf16x8(const u32x4 raw) {
   return o;
 }
 
-template <bool FAST, bool IN_F16 = false>
+// KIMG (lx_qkv_prep_kv_segs): k goes to the same rows of a key image of its own (K2, head h at k2_col + h*128) and the k columns of QKV stay
+// as they are; q is still written in place. Together with the V^T stores below -- only the 64-slot tiles of the launched segments, the tail
+// of a segment's last tile zero-filled -- a launch over some segments leaves the other segments' keys and V^T columns alone: the per-layer
+// images of a step-invariant condition stream on shapes (or with operands) the fused projection epilogue does not take.
+template <bool FAST, bool IN_F16 = false, bool KIMG = false>
 __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QKV, int ld, int q_col, int k_col, int v_col,
-                                                       const QkvSegs segs, float eps, uint16_t* __restrict__ VT, int vt_ld, int H) {
+                                                       const QkvSegs segs, float eps, uint16_t* __restrict__ VT, int vt_ld, int H,
+                                                       uint16_t* __restrict__ K2, int ldk2, int k2_col) {
   __shared__ uint16_t vt_s[64][128 + 8];
   int sg = 0;
   while (sg < segs.n - 1 && (int)blockIdx.x >= segs.tile0[sg + 1]) ++sg;
@@ -263,6 +268,7 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
 #pragma unroll 1
     for (int half = 0; half < 2; ++half) {
       uint16_t* rowp[2];
+      uint16_t* kdst[2];
       bool valid[2];
       u32x4 raw[2][3];
       f32x4 cs[2][4];
@@ -272,6 +278,7 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
         valid[u] = p < rows_per_batch;
         const int pc = valid[u] ? p : 0;          // row 0 of the batch stands in for rows past the end (loaded, never stored)
         rowp[u] = QKV + (rbase + pc) * ld + h * 128 + sub * 8;
+        kdst[u] = KIMG ? K2 + (rbase + pc) * ldk2 + k2_col + h * 128 + sub * 8 : rowp[u] + k_col;
         raw[u][0] = *(const u32x4*)(rowp[u] + q_col);
         raw[u][1] = *(const u32x4*)(rowp[u] + k_col);
         raw[u][2] = *(const u32x4*)(rowp[u] + v_col);
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
         }
         if (valid[u]) {
           *(u32x4*)(rowp[u] + q_col) = out[0];
-          *(u32x4*)(rowp[u] + k_col) = out[1];
+          *(u32x4*)kdst[u] = out[1];
         }
         if (VT) *(u32x4*)&vt_s[(half * 2 + u) * 16 + rloc][sub * 8] = valid[u] ? raw[u][2] : u32x4{0u, 0u, 0u, 0u};
       }
@@ -336,6 +343,10 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
     for (int which = 0; which < 2; ++which) {   // 0: q, 1: k
       const float* wn = which ? wk : wq;
       uint16_t* ptr = rowp + (which ? k_col : q_col);
+      uint16_t* dst = ptr;
+      if constexpr (KIMG) {
+        if (which) dst = K2 + (rbase + (valid ? p : 0)) * ldk2 + k2_col + h * 128 + sub * 8;
+      }
       u32x4 raw = {0u, 0u, 0u, 0u};
       if (valid) raw = *(const u32x4*)ptr;
       float x[8];
@@ -363,7 +374,7 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
         u32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
-        *(u32x4*)ptr = o;
+        *(u32x4*)dst = o;
       }
     }
     if (VT) {  // stash V[key][d] for the transpose
@@ -818,7 +829,7 @@ static int qkv_launch(void* QKV, int ld, int q_col, int k_col, int v_col, const 
   for (int i = 0; i < segs.n; ++i) fast = fast && segs.wq[i] && segs.wk[i] && segs.cos_tab[i];
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col, k_col, v_col, segs, eps,
-                       (uint16_t*)VT, vt_ld, H);
+                       (uint16_t*)VT, vt_ld, H, (uint16_t*)nullptr, 0, 0);
   };
   if (in_f16) launch(qkv_prep_kernel<false, true>);
   else if (fast) launch(qkv_prep_kernel<true>);
@@ -843,6 +854,49 @@ extern "C" int lx_qkv_prep_segs(void* QKV, int ld, int q_col, int k_col, int v_c
 extern "C" int lx_qkv_prep_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
                                       int H, float eps, void* VT, int vt_ld, void* stream) {
   return qkv_launch(QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, VT, vt_ld, stream, true);
+}
+
+// lx_qkv_prep_kv_segs / lx_qkv_prep_kv_f16in_segs: the pass above with the keys in an image of their own (qkv_prep_kernel<.., KIMG>). A launch
+// over some segments into images that keep other segments' entries: nothing may land outside the rows and the 64-slot tiles of the segments
+// it is given, so every tile has to end inside vt_ld and the key columns inside ldk2 (checked here, before the launch).
+static int qkv_kv_launch(const char* fn, bool in_f16, void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg,
+                         int n_batches, int H, float eps, void* K2, int ldk2, int k2_col, void* VT, int vt_ld, void* stream) {
+  LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "%s: 1..3 segments", fn);
+  LX_CHECK_ARG(QKV && K2 && VT && n_batches > 0 && H > 0, "%s: bad arguments", fn);
+  LX_CHECK_ARG(ld % 8 == 0 && q_col % 8 == 0 && k_col % 8 == 0 && v_col % 8 == 0 && ((uintptr_t)QKV & 15) == 0,
+               "%s: ld and column offsets must be multiples of 8, QKV 16-byte aligned", fn);
+  LX_CHECK_ARG(ldk2 % 8 == 0 && k2_col % 8 == 0 && k2_col >= 0 && ldk2 >= k2_col + H * 128 && ((uintptr_t)K2 & 15) == 0,
+               "%s: ldk2=%d / k2_col=%d must be multiples of 8 with k2_col + H*128 <= ldk2, K2 16-byte aligned", fn, ldk2, k2_col);
+  LX_CHECK_ARG(vt_ld % 64 == 0 && ((uintptr_t)VT & 15) == 0, "%s: vt_ld must be a multiple of 64, VT 16-byte aligned", fn);
+  QkvSegs segs;
+  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, segs.vt_pos0);
+  if (t < 0) return t;
+  for (int i = 0; i < n_seg; ++i) {
+    const long long vt_end = (long long)seg[i].vt_pos0 + (seg[i].rows_per_batch + 63) / 64 * 64;
+    LX_CHECK_ARG(vt_end <= vt_ld, "%s: segment %d's V^T tiles end at %lld > vt_ld=%d", fn, i, vt_end, vt_ld);
+  }
+  bool fast = true;
+  for (int i = 0; i < segs.n; ++i) fast = fast && segs.wq[i] && segs.wk[i] && segs.cos_tab[i];
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (uint16_t*)QKV, ld, q_col, k_col, v_col, segs, eps,
+                       (uint16_t*)VT, vt_ld, H, (uint16_t*)K2, ldk2, k2_col);
+  };
+  if (in_f16) launch(qkv_prep_kernel<false, true, true>);
+  else if (fast) launch(qkv_prep_kernel<true, false, true>);
+  else launch(qkv_prep_kernel<false, false, true>);
+  LX_LAUNCH_CHECK(fn);
+  return LX_OK;
+}
+
+extern "C" int lx_qkv_prep_kv_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
+                                   int H, float eps, void* K2, int ldk2, int k2_col, void* VT, int vt_ld, void* stream) {
+  return qkv_kv_launch("lx_qkv_prep_kv_segs", false, QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, K2, ldk2, k2_col, VT, vt_ld, stream);
+}
+
+extern "C" int lx_qkv_prep_kv_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg, int n_batches,
+                                         int H, float eps, void* K2, int ldk2, int k2_col, void* VT, int vt_ld, void* stream) {
+  return qkv_kv_launch("lx_qkv_prep_kv_f16in_segs", true, QKV, ld, q_col, k_col, v_col, seg, n_seg, n_batches, H, eps, K2, ldk2, k2_col, VT, vt_ld,
+                       stream);
 }
 
 static int qkv_fp8_segs_launch(bool in_f16, const void* QKV, int ld, int q_col, int k_col, int v_col, const lx_qkv_seg* seg, int n_seg,

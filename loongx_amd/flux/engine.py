@@ -169,6 +169,7 @@ class DiTEngine:
         self.cond_skip = False           # the forward being enqueued runs without the condition rows
         self.KC = self.VTC = None        # [layers, M, D] keys / [layers, B, H, 128, vt_ld] V^T, allocated on first use
         self.KC2 = self.VTC2 = None      # precise mode's: [layers, M, 2D] key pairs (hi | lo) / [layers, 2, B, H, 128, vt_ld] V^T pairs
+        self.KC8 = self.VTC8 = None      # attn_fp8's: [layers, M, D] e4m3 keys / [layers, B, H, 128, vt_ld] e4m3 V^T (half the bf16 images)
         # (Round 5 removed three measured-negative options that lived here as environment switches: the q/k/v adapters' down-projection
         # inside ln_modulate (LX_LN_LORA: -1.1 %; it could absorb the 57 launches per step that read the AdaLN-normalised stream, not the 75
         # that read an attention output or a GELU hidden), adapter rows on merged weights W' = W + s B A (LX_LORA_MERGE: +11.5 GB, the GEMMs
@@ -232,7 +233,7 @@ class DiTEngine:
         self.graphs = {}
         self.shape = (B, T, N, C)
         self.cond_ready = False
-        self.KC = self.VTC = self.KC2 = self.VTC2 = None          # per-layer key / V^T images of the condition cache: shape-bound
+        self.KC = self.VTC = self.KC2 = self.VTC2 = self.KC8 = self.VTC8 = None      # per-layer key / V^T images of the condition cache: shape-bound
         self.cond_cache = self.cond_cached = False
         self.XN2 = self.Y32 = self.YA = self.lat2 = None          # precise-mode buffers, allocated by _setup_precise()
         self.XN8 = self.Y8 = None                                  # fp8-GEMM operand images, allocated by _setup_fp8()
@@ -836,6 +837,8 @@ class DiTEngine:
         if self.model_config.get("attn_fp8", False):      # e4m3 q / k / V^T images straight from the accumulators
             self._fp8_images()
             kw.update(q8=self.rows(self.Q8, s.name), k8=self.rows(self.K8, s.name), vt=self.VT8)
+            if self.cond_cache and len(qkv) > 4:    # the per-layer e4m3 key / V^T images (q stays in the shared Q8)
+                kw.update(k8=self.rows(self.KC8[qkv[4]], s.name), vt=self.VTC8[qkv[4]])
         elif self.cond_cache and len(qkv) > 4:      # per-layer key / V^T images: the condition rows' entries outlive the step
             kw.update(k=self.rows(self.KC[qkv[4]], s.name), vt=self.VTC[qkv[4]])
         return kw
@@ -874,9 +877,14 @@ class DiTEngine:
         cfg = self.cfg
         D, H, B = cfg.inner_dim, cfg.num_attention_heads, self.B
         Y = self.Y
-        cached = self.cond_cache and layer is not None and prepped
+        cached = self.cond_cache and layer is not None
         streams = self._all_streams() if cached else self._streams()      # key / value segments (queries: the streams of this forward)
-        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(streams, (wq, wk, wq_txt, wk_txt))
+        seg_row0, seg_len, seg_vt0, bias, _ = self._attn_segments(streams)
+        # the separate q / k / v pass: the streams with rows in this forward (a cond_skip forward leaves the condition stream's part of the
+        # per-layer images as the first forward of the conditioning wrote it)
+        qsegs = [] if prepped else self._qsegs(self._streams(), wq, wk, wq_txt, wk_txt)
+        # cached, in a cond_skip forward: only the text / image segments have queries (img_only: qseg_mask, which wins)
+        nq = len(self._streams()) if cached and self.cond_skip and not img_only else 0
         flags = (ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0
         if not self.pair_plan:             # the batch-size-invariant plans: the attention kernel must not depend on the batch size either
             flags |= ops.ATTN_INVARIANT
@@ -904,18 +912,23 @@ class DiTEngine:
             # opt-in fp8 (e4m3) attention (BASELINE configs[4]): q / k / v^T go to byte images, both attention products run on
             # the 64-deep f8f6f4 MFMA; softmax statistics and the output accumulators stay fp32 (include/lx.h, lx_attn_fwd_fp8)
             self._fp8_images()
+            # cached: keys / V^T of this forward's streams into the layer's e4m3 images, where the attention reads all streams' from
+            K8, VT8 = (self.KC8[layer], self.VTC8[layer]) if cached else (self.K8, self.VT8)
             if not prepped:                # otherwise the projection epilogue already wrote the three byte images
-                ops.qkv_prep_fp8_segs(Y, 2 * D, 0, D, qsegs, B, H, self.Q8, self.K8, self.VT8, in_f16=self.f16)
+                ops.qkv_prep_fp8_segs(Y, 2 * D, 0, D, qsegs, B, H, self.Q8, K8, VT8, in_f16=self.f16)
             f8 = (ops.ATTN_O_F16 if self.f16 else 0) | (ops.ATTN_P_EXP2 if self.model_config.get("attn_fp8_exp2", False) else 0)
-            ops.attn_fwd_fp8(self.Q8, self.K8, self.VT8, Y, o_col=2 * D, B=B, H=H, seg_row0=seg_row0, seg_len=seg_len,
+            if cached:
+                okw["n_qseg"] = nq
+            ops.attn_fwd_fp8(self.Q8, K8, VT8, Y, o_col=2 * D, B=B, H=H, seg_row0=seg_row0, seg_len=seg_len,
                              seg_vt0=seg_vt0, bias=bias, flags=f8, **okw)
             return
         if cached:
             # keys from the layer's key image, V^T from the layer's V^T image (the condition stream's part written by the first
             # forward of this conditioning); in a cond_skip forward only the text / image segments have queries
+            if not prepped:                # no fused epilogue (stream lengths it does not take, or switched off): the separate pass writes them
+                ops.qkv_prep_kv_segs(Y, 2 * D, 0, D, qsegs, B, H, self.KC[layer], 0, self.VTC[layer], in_f16=self.f16)
             ops.attn_fwd(Y, self.KC[layer], self.VTC[layer], Y, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
-                         seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, n_qseg=(len(self._streams()) if self.cond_skip else 0) if not img_only else 0,
-                         flags=flags, **okw)
+                         seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, n_qseg=nq, flags=flags, **okw)
             return
         if not prepped:                    # otherwise the projection launch already normalised / rotated k and q and wrote V^T
             # (fp16 operand mode: an unfused projection stored k | v | q as fp16 -- the pass reads them as such and leaves bf16 k / q, bf16 V^T)
@@ -1292,21 +1305,24 @@ class DiTEngine:
         self.cond_cache = self._cond_cache_ok()
         skip = self.cond_cache and self.cond_cached            # the condition stream's keys / values of this conditioning are cached
         nl = self.cfg.num_layers + self.cfg.num_single_layers
-        # (one set at a time: an engine that alternates between bf16 and precise conditionings drops the other mode's images -- and the
-        #  step graphs that hold their addresses -- when it allocates this mode's)
-        if self.cond_cache and self.precise:                   # per-layer key / V^T pair images (outside any capture)
-            if self.KC2 is None:
-                if self.KC is not None:
-                    self.KC = self.VTC = None
+        # (one set at a time: an engine that alternates between bf16 / fp16, attn_fp8 and precise conditionings drops the other mode's images
+        #  -- and the step graphs that hold their addresses -- when it allocates this mode's)
+        if self.cond_cache:                                    # this mode's per-layer key / V^T images (outside any capture)
+            want = "KC2" if self.precise else "KC8" if self.model_config.get("attn_fp8", False) else "KC"
+            if getattr(self, want) is None:
+                if any(getattr(self, n) is not None for n in ("KC", "KC2", "KC8")):
+                    self.KC = self.VTC = self.KC2 = self.VTC2 = self.KC8 = self.VTC8 = None
                     self.graphs = {}
-                self.KC2 = torch.zeros(nl, self.M, 2 * self.cfg.inner_dim, dtype=torch.bfloat16, device=self.device)
-                self.VTC2 = torch.zeros((nl, 2) + tuple(self.VT.shape), dtype=torch.bfloat16, device=self.device)
-        elif self.cond_cache and self.KC is None:              # per-layer key / V^T images (outside any capture)
-            if self.KC2 is not None:
-                self.KC2 = self.VTC2 = None
-                self.graphs = {}
-            self.KC = torch.zeros(nl, self.M, self.cfg.inner_dim, dtype=torch.bfloat16, device=self.device)
-            self.VTC = torch.zeros((nl,) + tuple(self.VT.shape), dtype=torch.bfloat16, device=self.device)
+                D, vts, bf16 = self.cfg.inner_dim, tuple(self.VT.shape), torch.bfloat16
+                if want == "KC2":                              # key pairs (hi | lo), the hi and the lo V^T image
+                    self.KC2 = torch.zeros(nl, self.M, 2 * D, dtype=bf16, device=self.device)
+                    self.VTC2 = torch.zeros((nl, 2) + vts, dtype=bf16, device=self.device)
+                elif want == "KC8":                            # e4m3 bytes: half the bf16 images
+                    self.KC8 = torch.zeros(nl, self.M, D, dtype=torch.uint8, device=self.device)
+                    self.VTC8 = torch.zeros((nl,) + vts, dtype=torch.uint8, device=self.device)
+                else:
+                    self.KC = torch.zeros(nl, self.M, D, dtype=bf16, device=self.device)
+                    self.VTC = torch.zeros((nl,) + vts, dtype=bf16, device=self.device)
         if not self.use_graph or timed:
             if pre:
                 self.mods.copy_(self.sched[1][step_index])
@@ -1355,11 +1371,12 @@ class DiTEngine:
     def _cond_cache_ok(self) -> bool:
         """The condition stream is step-invariant and this kernel set can keep its keys / values per layer: condition queries
         masked from text and image keys (block.py:106-120), something that writes the per-layer images -- the fused projection
-        epilogue, or in precise mode the split-bf16 attention's prep pass (LX_PRECISE_ATTN=f32 recomputes: that kernel reads fp32 q / k / v
-        from one buffer) --, no add_cond_attn (which also needs the condition stream's attention OUTPUT every step)."""
-        writes = self.precise_attn_split if self.precise else self._qkv_epilogue()
-        if (not (self.cond_cache_enabled and self.C and writes) or self.model_config.get("add_cond_attn", False)
-                or self.model_config.get("attn_fp8", False)):          # (the per-layer images are bf16: the fp8 attention recomputes)
+        epilogue or the separate q / k / v pass (lx_qkv_prep_kv_segs; lx_qkv_prep_fp8_segs with attn_fp8, into e4m3 images), in precise mode the
+        split-bf16 attention's prep pass (LX_PRECISE_ATTN=f32 recomputes: that kernel reads fp32 q / k / v from one buffer); not the e4m3
+        GEMM path, whose blocks have no per-layer images --, no add_cond_attn (which also needs the condition stream's attention OUTPUT
+        every step)."""
+        writes = self.precise_attn_split if self.precise else not self.gemm_fp8
+        if not (self.cond_cache_enabled and self.C and writes) or self.model_config.get("add_cond_attn", False):
             return False
         ab = self.attn_bias["cond"]
         return ab["txt"] == NEG_INF and ab["img"] == NEG_INF

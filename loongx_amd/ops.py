@@ -344,6 +344,16 @@ def qkv_prep_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, VT, eps=1e-6, in
     check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, _p(VT), VT.shape[-1] if VT is not None else 0, _stream()), nm)
 
 
+def qkv_prep_kv_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, K2, k2_col, VT, eps=1e-6, in_f16=False) -> None:
+    """qkv_prep_segs with the keys in an image of their own: q in place, k (bf16) into the same rows of K2 bf16 [M, ldk2] at k2_col + h*128
+    (the k columns of QKV stay as they are), V^T into VT. Rows and V^T tiles of segments that are not in `segs` stay as they are."""
+    _req(K2, torch.bfloat16, "K2"); _req(VT, torch.bfloat16, "VT")
+    assert K2.stride(1) == 1 and VT.is_contiguous()
+    fn, nm = (lib.lx_qkv_prep_kv_f16in_segs, "lx_qkv_prep_kv_f16in_segs") if in_f16 else (lib.lx_qkv_prep_kv_segs, "lx_qkv_prep_kv_segs")
+    check(fn(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, _qkv_segs(segs), len(segs), n_batches, H, eps, K2.data_ptr(), K2.stride(0), k2_col,
+             VT.data_ptr(), VT.shape[-1], _stream()), nm)
+
+
 def _attn_desc(Q, K, VT, O, q_col, k_col, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale):
     d = AttnDesc()
     d.Q, d.K, d.VT, d.O = Q.data_ptr(), K.data_ptr(), VT.data_ptr(), O.data_ptr()
@@ -468,13 +478,15 @@ def qkv_prep_fp8_segs(QKV, q_col, k_col, v_col, segs, n_batches, H, Q8, K8, VT8,
              VT8.data_ptr(), VT8.shape[-1], FP8_Q_SCALE, FP8_K_SCALE, FP8_V_SCALE, _stream()), nm)
 
 
-def attn_fwd_fp8(Q8, K8, VT8, O, *, o_col, B, H, seg_row0, seg_len, seg_vt0, bias=None, scale=None, flags=0, f16_ovf=None, qseg_mask=0) -> None:
+def attn_fwd_fp8(Q8, K8, VT8, O, *, o_col, B, H, seg_row0, seg_len, seg_vt0, bias=None, scale=None, flags=0, f16_ovf=None, qseg_mask=0,
+                 n_qseg=0) -> None:
     """flags: 0 | ATTN_O_F16 (O written as fp16 for an fp16-operand output projection) | ATTN_P_EXP2 (probabilities by v_exp_f32 + e4m3
-    rounding instead of the log-linear byte code of the score); qseg_mask as in attn_fwd"""
+    rounding instead of the log-linear byte code of the score); n_qseg / qseg_mask as in attn_fwd. K8 / VT8 may be images other than the
+    one Q8 sits in (the per-layer images of the condition cache)."""
     d = _attn_desc(Q8, K8, VT8, O, 0, 0, o_col, B, H, seg_row0, seg_len, seg_vt0, bias, scale)
-    d.flags, d.f16_ovf, d.qseg_mask = flags, _p(f16_ovf), qseg_mask
+    d.flags, d.f16_ovf, d.qseg_mask, d.n_qseg = flags, _p(f16_ovf), qseg_mask, n_qseg
     args = (C.byref(d), 1.0 / (FP8_Q_SCALE * FP8_K_SCALE), 1.0 / FP8_V_SCALE, _stream())
-    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, 0, qseg_mask), sum(seg_len)), lambda: check(lib.lx_attn_fwd_fp8(*args), "lx_attn_fwd_fp8"))
+    _timed("attn", _attn_cost(B, H, _q_rows(seg_len, n_qseg, qseg_mask), sum(seg_len)), lambda: check(lib.lx_attn_fwd_fp8(*args), "lx_attn_fwd_fp8"))
 
 
 # ---- fp8 GEMM path (include/lx.h "fp8 GEMM path") ----------------------------------------------------------------------
