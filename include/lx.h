@@ -31,6 +31,7 @@ extern "C" {
  *         lx_attn_fwd_split takes n_qseg / qseg_mask and keys / V^T from buffers other than the query buffer
  *         a third additive extension of 0.4.4 (no layout change): + lx_qkv_prep_kv_segs, lx_qkv_prep_kv_f16in_segs (the 16-bit RMSNorm + RoPE +
  *         V^T pass with the keys in an image of their own)
+ *         a fourth additive extension of 0.4.4 (no layout change): + lx_softmax_rows_valid (the VAE's row softmax over a padded key axis)
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -568,6 +569,11 @@ int lx_groupnorm_silu(const void* x, int x_is_bf16, int B, int P, int C, int G, 
 int lx_im2col3x3(const void* x, int B, int H, int W, int C, int mode, void* out, int Kpad, void* stream);
 /* P(bf16)[m, :] = softmax(scale * S(fp32)[m, :]) -- the single-head mid-block attention of the VAE */
 int lx_softmax_rows(const float* S, int lds, float scale, void* P, int ldp, int M, int N, void* stream);
+/* The same over a key axis padded to the GEMM's granule: P(bf16)[m, 0:n_valid] = softmax(scale * S(fp32)[m, 0:n_valid]) and
+ * P[m, n_valid:n_store] = +0. Columns >= n_valid of S (scores against pad keys) may hold anything, NaN / Inf included: they are never
+ * read. Nothing at or beyond column n_store of a row of P is written. Any n_valid >= 1, n_store >= n_valid, lds >= n_valid,
+ * ldp >= n_store; rows of S 16-byte and rows of P 8-byte aligned (base and leading dimension) take 16 / 8 B accesses, others scalar ones. */
+int lx_softmax_rows_valid(const float* S, int lds, float scale, void* P, int ldp, int M, int n_valid, int n_store, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,8 +5,9 @@
 //   * GroupNorm(32 groups, eps, affine) [+ SiLU]: partial sums per (image, row chunk, group), then one normalising pass;
 //   * im2col for 3x3 convolutions: pad 1 / stride 1, the encoder's stride-2 downsample with its (0,1,0,1) padding, and the
 //     decoder's nearest-neighbour 2x upsample folded into the gather (the upsampled image is never materialised);
-//   * row softmax (fp32 scores -> bf16 probabilities) for the single-head mid-block attention.
-// All accesses are 8-16 B per lane along the channel axis.
+//   * row softmax (fp32 scores -> bf16 probabilities) for the single-head mid-block attention, and its form for a key axis padded
+//     to the GEMM's granule (token counts that are no multiple of 64): the pad keys get probability +0.
+// All accesses are 8-16 B per lane along the channel axis (the padded softmax falls back to scalar ones on unaligned rows).
 #include "common.h"
 
 namespace {
@@ -149,6 +150,48 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   }
 }
 
+// ---- row softmax over the first n_valid columns of a row whose key axis is padded: P[row, 0:n_valid] = softmax(scale * S[row, 0:n_valid]),
+// P[row, n_valid:n_store] = +0. One wave per row. Columns >= n_valid of S (scores against padding: anything, NaN included) are never
+// loaded; nothing at or beyond column n_store of P is written. VEC: every row of S starts 16-byte and every row of P 8-byte aligned, so
+// columns [0, n_valid & ~3) go four per lane and only the < 4 columns behind them one per lane; otherwise every access is a scalar one.
+template <bool VEC>
+__global__ __launch_bounds__(256) void softmax_rows_valid_kernel(const float* __restrict__ S, int lds, float scale, uint16_t* __restrict__ Pm, int ldp,
+                                                                 int M, int n_valid, int n_store) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float* s = S + (size_t)row * lds;
+  uint16_t* p = Pm + (size_t)row * ldp;
+  const int nv = VEC ? (n_valid & ~3) : 0;                // [0, nv) in vectors, [nv, n_valid) one column per lane
+  float m = -INFINITY;
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+    m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) m = fmaxf(m, s[c]);
+  m = wave_max(m) * scale;
+  float l = 0.f;
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) l += __expf(v[k] * scale - m);
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) l += __expf(s[c] * scale - m);
+  const float inv = 1.0f / wave_sum(l);
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+    float o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = __expf(v[k] * scale - m) * inv;
+    *(u32x2*)(p + c) = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) p[c] = f32_to_bf16(__expf(s[c] * scale - m) * inv);
+  // the pad keys' probabilities: scalar up to the next multiple of 4 (z0), vectors up to the last one (z1), scalar to n_store
+  const int z0 = VEC ? min((n_valid + 3) & ~3, n_store) : n_store, z1 = VEC ? max(z0, n_store & ~3) : n_store;
+  for (int c = n_valid + lane; c < z0; c += 64) p[c] = 0;
+  for (int c = z0 + lane * 4; c < z1; c += 256) *(u32x2*)(p + c) = u32x2{0u, 0u};
+  for (int c = z1 + lane; c < n_store; c += 64) p[c] = 0;
+}
+
 }  // namespace
 
 extern "C" size_t lx_groupnorm_workspace_bytes(int B, int P, int G) {
@@ -194,5 +237,16 @@ extern "C" int lx_softmax_rows(const float* S, int lds, float scale, void* P, in
   LX_CHECK_ARG(S && P && M > 0 && N > 0 && N % 4 == 0 && lds % 4 == 0 && ldp % 4 == 0, "lx_softmax_rows: N, lds, ldp must be multiples of 4");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, N);
   LX_LAUNCH_CHECK("lx_softmax_rows");
+  return LX_OK;
+}
+
+extern "C" int lx_softmax_rows_valid(const float* S, int lds, float scale, void* P, int ldp, int M, int n_valid, int n_store, void* stream) {
+  LX_CHECK_ARG(S && P, "lx_softmax_rows_valid: NULL operand");
+  LX_CHECK_ARG(M > 0 && n_valid >= 1 && n_store >= n_valid, "lx_softmax_rows_valid: need M > 0 and 1 <= n_valid <= n_store (M=%d n_valid=%d n_store=%d)", M, n_valid, n_store);
+  LX_CHECK_ARG(lds >= n_valid && ldp >= n_store, "lx_softmax_rows_valid: need lds >= n_valid and ldp >= n_store (lds=%d ldp=%d n_valid=%d n_store=%d)", lds, ldp, n_valid, n_store);
+  const bool vec = ((uintptr_t)S & 15) == 0 && lds % 4 == 0 && ((uintptr_t)P & 7) == 0 && ldp % 4 == 0;
+  if (vec) hipLaunchKernelGGL(softmax_rows_valid_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  else hipLaunchKernelGGL(softmax_rows_valid_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  LX_LAUNCH_CHECK("lx_softmax_rows_valid");
   return LX_OK;
 }

@@ -605,9 +605,16 @@ def im2col3x3(x: torch.Tensor, out: torch.Tensor, mode: int = 0) -> None:
     check(lib.lx_im2col3x3(x.data_ptr(), B, H, W, Cc, mode, out.data_ptr(), out.shape[1], _stream()), "lx_im2col3x3")
 
 
-def softmax_rows(S: torch.Tensor, P: torch.Tensor, scale: float) -> None:
+def softmax_rows(S: torch.Tensor, P: torch.Tensor, scale: float, n_valid: Optional[int] = None) -> None:
+    """P bf16 = softmax(scale * S) row by row. n_valid: only the first n_valid columns of S are keys (the others may hold anything);
+    their probabilities fill P[:, :n_valid] and the remaining columns of P, up to P.shape[1], are set to +0."""
     _req(S, torch.float32, "S"); _req(P, torch.bfloat16, "P")
-    check(lib.lx_softmax_rows(S.data_ptr(), S.stride(0), scale, P.data_ptr(), P.stride(0), S.shape[0], S.shape[1], _stream()), "lx_softmax_rows")
+    if n_valid is None:
+        check(lib.lx_softmax_rows(S.data_ptr(), S.stride(0), scale, P.data_ptr(), P.stride(0), S.shape[0], S.shape[1], _stream()), "lx_softmax_rows")
+        return
+    assert P.shape[0] == S.shape[0] and S.shape[1] >= n_valid, "softmax_rows: S and P need the same rows, S at least n_valid columns"
+    check(lib.lx_softmax_rows_valid(S.data_ptr(), S.stride(0), scale, P.data_ptr(), P.stride(0), S.shape[0], int(n_valid), P.shape[1], _stream()),
+          "lx_softmax_rows_valid")
 
 
 # ---- CS3 / DGF -------------------------------------------------------------------------------------------

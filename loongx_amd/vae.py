@@ -7,7 +7,10 @@ Reference call sites: `vae.decode(latents / scaling_factor + shift_factor)` (src
 Inside, activations are NHWC: the residual stream is fp32 `[B*H*W, C]`, GEMM operands bf16. Every convolution is an implicit
 GEMM on the DiT's MFMA kernel (`lx_im2col3x3` rows x `[Cout, 9 Cin]` weights, bias / fp32-residual epilogues fused), the
 mid-block attention is two GEMMs around `lx_softmax_rows`, GroupNorm+SiLU is `lx_groupnorm_silu` (csrc/vae.hip). torch owns
-buffers and the NCHW<->NHWC layout moves only. Parameter names are diffusers' (`decoder.up_blocks.0.resnets.1.conv1.weight` ...),
+buffers and the NCHW<->NHWC layout moves only. Any latent grid decodes and any image whose sides the encoder can halve encodes: a
+token count P = h*w that is no multiple of 64 pads the attention's key axis to Ppad = roundup(P, 64) and `lx_softmax_rows_valid`
+gives the pad keys probability +0 (multiples of 64 take the unpadded launches). Scratch per image: P * Ppad * 6 bytes (fp32 scores
++ bf16 probabilities). Parameter names are diffusers' (`decoder.up_blocks.0.resnets.1.conv1.weight` ...),
 so `vae/diffusion_pytorch_model.safetensors` of a FLUX.1 checkpoint loads as is.
 """
 from __future__ import annotations
@@ -82,9 +85,9 @@ class LxAutoencoderKL:
         self.w[name + ".shape"] = (co, ci, kh)
 
     # ---- building blocks (x: fp32 [B*H*W, C]) ----------------------------------------------------------------------------
-    def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True) -> torch.Tensor:
+    def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         C = x.shape[1]
-        y = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
+        y = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device) if out is None else out
         ops.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y.view(B, -1, C), self.G, 1e-6, silu)
         return y
 
@@ -125,6 +128,8 @@ class LxAutoencoderKL:
 
     def _attn(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
         """Single-head attention over the P = H*W tokens of each image (diffusers Attention, residual_connection=True)."""
+        if P % 64:
+            return self._attn_ragged(x, B, P, p)
         C = x.shape[1]
         n = self._gn(x, B, p + ".group_norm", silu=False)
         q, k = self._lin(n, p + ".to_q"), self._lin(n, p + ".to_k")
@@ -142,6 +147,34 @@ class LxAutoencoderKL:
         self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
         return x
 
+    def _attn_ragged(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
+        """_attn for a token count that is no multiple of 64 (the GEMM's K granule; its N granule is 8): the key axis is padded to
+        Ppad = roundup(P, 64). The images lie back to back in n and k ([B*P, C]), so the Ppad key rows of image b run into image b+1's
+        rows and, for the last image, into a zero tail that both buffers carry: every row a GEMM reads lies inside its allocation and
+        is finite (real rows of a neighbour, or zeros). Columns [P, Ppad) of S and of v^T are therefore finite garbage; the softmax
+        reads none of the former and writes exact zeros for those keys, so the latter contribute nothing to P v."""
+        C = x.shape[1]
+        Pp = _pad_to(P, 64)
+        rows = (B - 1) * P + Pp                                                                       # the last image's Ppad rows end here
+        n = torch.zeros(rows, C, dtype=torch.bfloat16, device=self.device)
+        k = torch.zeros(rows, C, dtype=torch.bfloat16, device=self.device)
+        self._gn(x, B, p + ".group_norm", silu=False, out=n[: B * P])
+        q = self._lin(n[: B * P], p + ".to_q")
+        self._lin(n[: B * P], p + ".to_k", out=k[: B * P])
+        Wv, bv = self.w[p + ".to_v.w"], self.w[p + ".to_v.bias"]
+        S = torch.empty(P, Pp, dtype=torch.float32, device=self.device)
+        Pm = torch.empty(P, Pp, dtype=torch.bfloat16, device=self.device)
+        vT = torch.empty(C, Pp, dtype=torch.bfloat16, device=self.device)
+        o = torch.empty(B * P, C, dtype=torch.bfloat16, device=self.device)
+        for b in range(B):
+            r, rp = slice(b * P, (b + 1) * P), slice(b * P, b * P + Pp)
+            ops.gemm([ops.gemm_desc(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32)])                      # S[:, :P] = q k^T
+            ops.softmax_rows(S, Pm, 1.0 / math.sqrt(C), n_valid=P)                                    # Pm[:, P:] = +0
+            ops.gemm([ops.gemm_desc(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16)])                      # v^T[:, :P] = Wv n^T
+            ops.gemm([ops.gemm_desc(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)])
+        self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
+        return x
+
     def _mid(self, x, B, H, W, p):
         x = self._resnet(x, B, H, W, p + ".resnets.0")
         x = self._attn(x, B, H * W, p + ".attentions.0")
@@ -153,11 +186,9 @@ class LxAutoencoderKL:
     # ---- public surface -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
-        """z [B, latent, h, w] -> image [B, 3, 8h, 8w] fp32."""
+        """z [B, latent, h, w] (any h, w >= 1) -> image [B, 3, 8h, 8w] fp32."""
         cfg = self.config
         B, _, H, W = z.shape
-        if (H * W) % 64:
-            raise ValueError(f"the mid-block attention runs on the GEMM kernel: latent h*w={H * W} must be a multiple of 64")
         x, _, _ = self._conv3(self._nhwc_bf16(z).view(B * H * W, -1), B, H, W, "decoder.conv_in")
         x = self._mid(x, B, H, W, "decoder.mid_block")
         rev = list(reversed(cfg.block_out_channels))
@@ -179,8 +210,8 @@ class LxAutoencoderKL:
         cfg = self.config
         B, _, H, W = images.shape
         nd = len(cfg.block_out_channels) - 1
-        if H % (1 << nd) or W % (1 << nd) or ((H >> nd) * (W >> nd)) % 64:
-            raise ValueError(f"image {H}x{W}: sides must be multiples of {1 << nd} and the latent grid a multiple of 64 tokens")
+        if H % (1 << nd) or W % (1 << nd):
+            raise ValueError(f"image {H}x{W}: sides must be multiples of {1 << nd} (the encoder halves them {nd} times)")
         x, _, _ = self._conv3(self._nhwc_bf16(images).view(B * H * W, -1), B, H, W, "encoder.conv_in")
         for i in range(len(cfg.block_out_channels)):
             for j in range(cfg.layers_per_block):
