@@ -118,7 +118,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_pipe_kernel(const AttnArgs arg
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
   }
-  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * 1.4426950408889634f;
+  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * LX_LOG2E;
 
   f32x16 oacc[4];
 #pragma unroll
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_pipe_kernel(const AttnArgs arg
       g_left = seg_len(g_seg);
       g_cur.krow = pick(g_seg, row00, row01, row02) + b * g_left;
       g_cur.vpos = pick(g_seg, vt00, vt01, vt02);
-      g_cur.bl = pick(g_seg, bia0, bia1, bia2) * 1.4426950408889634f;
+      g_cur.bl = pick(g_seg, bia0, bia1, bia2) * LX_LOG2E;
     }
     g_cur.nvalid = min(g_left, KVBLK);
     g_cur.nclamp = g_cur.nvalid;
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_pipe_kernel(const AttnArgs arg
 // (values <= 2^DEFER_THR = 256 < 448). Operand convention of the f8f6f4 MFMA (checked on hardware, tools/ubench/fp8_mfma):
 // lane (row = lane % 32, g = lane / 32) supplies 32 bytes, and byte p of group g is the same k index on both operands. So the
 // K / Q fragments simply take d = half*64 + g*32 + p, the P fragment is the lane's own 32 probabilities in register order
-// (p = kb*16 + r), and the V^T image stores its keys in exactly that order (qkv_prep_fp8_kernel, vt8_key()).
+// (p = kb*16 + r), and the V^T image stores its keys in exactly that order (qkv_prep_fp8_kernel, lx_vt8_key()).
 // Structure: the plain 8-wave kernel (two waves per SIMD); stage = 8 KiB K (64 keys x 128 B, slot ^= (key>>1)&7) + 8 KiB V^T
 // (128 d x 64 B, slot ^= (d>>2)&3), double buffered, one 1-KiB LDS-DMA piece per wave and operand.
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_fp8_pipe_kernel(const AttnArgs
       qf[hf] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
     }
   }
-  const float c2 = D.scale * qk_descale * 1.4426950408889634f;      // (!POW2: multiplies every score; POW2: it is 2^(e8m0 - 127))
+  const float c2 = D.scale * qk_descale * LX_LOG2E;      // (!POW2: multiplies every score; POW2: it is 2^(e8m0 - 127))
   f32x16 oacc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_fp8_pipe_kernel(const AttnArgs
       g_left = seg_len(g_seg);
       g_cur.krow = pick(g_seg, row00, row01, row02) + b * g_left;
       g_cur.vpos = pick(g_seg, vt00, vt01, vt02);
-      g_cur.bl = pick(g_seg, bia0, bia1, bia2) * 1.4426950408889634f;
+      g_cur.bl = pick(g_seg, bia0, bia1, bia2) * LX_LOG2E;
     }
     g_cur.nvalid = min(g_left, KVBLK);
     g_cur.nclamp = g_cur.nvalid;
@@ -1039,7 +1039,7 @@ extern "C" int lx_attn_fwd_fp8(const lx_attn_desc* d, float qk_descale, float v_
   // softmax scale x log2(e) x operand descale an exact power of two 2^-k (ops.py chooses the q scale so)? Then the score MFMAs
   // apply it as an MX block scale and the scores come out as exp2 arguments (lx_attn_fp8_pipe_kernel, POW2); any other combination of
   // scales runs the generic form (one fma per score)
-  const double c2 = (double)d->scale * (double)qk_descale * 1.4426950408889634;
+  const double c2 = (double)d->scale * (double)qk_descale * LX_LOG2E_F64;
   const int k = (int)lround(-log2(c2));
   const bool pow2 = k >= 1 && k <= 60 && fabs(c2 * ldexp(1.0, k) - 1.0) < 1e-5;
   hipStream_t st = (hipStream_t)stream;

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void lx_attn4_kernel(const AttnArgs args, c
       g_left = pick(r, rl0, rl1, rl2);
       g_cur.ksoff = (pick(r, row00, row01, row02) + it.b * g_left) * ldk * 2 + it.h * (DH * 2);
       g_cur.vsoff = pick(r, vt00, vt01, vt02) * 2 + it.bh * DH * vt_ld * 2;
-      g_cur.bl = pick(sq_, pick(r, b00, b01, b02), pick(r, b10, b11, b12), pick(r, b20, b21, b22)) * 1.4426950408889634f;
+      g_cur.bl = pick(sq_, pick(r, b00, b01, b02), pick(r, b10, b11, b12), pick(r, b20, b21, b22)) * LX_LOG2E;
       g_cur.w = gw;
     }
     g_cur.nvalid = min(g_left, KVBLK);

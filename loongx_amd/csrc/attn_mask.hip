@@ -23,7 +23,6 @@
 namespace {
 
 constexpr int MQBLK = 256;                 // query rows per tile (8 waves x 32)
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr float MASKED = -3.0e30f;         // score (log2 units) of a masked pair; below every attended score, which is clamped to >= -1e30
 constexpr float ATT_MIN = -1.0e30f;
 enum { CLS_EMPTY = 0, CLS_FULL = 1, CLS_PARTIAL = 2 };
@@ -49,8 +48,6 @@ struct PrepArgs {
   void* data;
 };
 
-__device__ __forceinline__ int mask_key(int p) { return ((p >> 4) & 1) * 32 + 8 * ((p & 15) >> 2) + 4 * (p >> 5) + (p & 3); }
-
 __device__ __forceinline__ int seg_of(int t, const int (&start)[4], int n_seg) {
   int s = 0;
   if (n_seg > 1 && t >= start[1]) s = 1;
@@ -58,14 +55,14 @@ __device__ __forceinline__ int seg_of(int t, const int (&start)[4], int n_seg) {
   return s;
 }
 
-// one workgroup per tile: 4 waves x 64 rows each, lane = position p of the row (key mask_key(p))
+// one workgroup per tile: 4 waves x 64 rows each, lane = position p of the row (key lx_vt8_key(p))
 template <bool FLOAT>
 __global__ __launch_bounds__(256) void lx_attn_mask_prep_kernel(const PrepArgs a) {
   const MaskGeom& g = a.g;
   const int kt = blockIdx.x, qt = blockIdx.y, plane = blockIdx.z;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sq = seg_of(qt, g.qt_start, g.n_seg), sk = seg_of(kt, g.kt_start, g.n_seg);
-  const int q0 = (qt - g.qt_start[sq]) * MQBLK, k_in = (kt - g.kt_start[sk]) * KVBLK + mask_key(lane);
+  const int q0 = (qt - g.qt_start[sq]) * MQBLK, k_in = (kt - g.kt_start[sk]) * KVBLK + lx_vt8_key(lane);
   const int lq = g.seg_len[sq], lk = g.seg_len[sk];
   const bool pair_on = a.bias[sq][sk] > -1e37f;
   const bool key_ok = pair_on && k_in < lk;
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(256) void lx_attn_mask_prep_kernel(const PrepArgs a
       nonfull |= !on || v != 0.f;
     }
     if constexpr (FLOAT) {
-      ((float*)a.data)[(tile * MQBLK + i) * KVBLK + lane] = on ? fmaxf(v * LOG2E, ATT_MIN) : MASKED;
+      ((float*)a.data)[(tile * MQBLK + i) * KVBLK + lane] = on ? fmaxf(v * LX_LOG2E, ATT_MIN) : MASKED;
     } else {
       const uint64_t w = __builtin_amdgcn_ballot_w64(on);
       if (lane == 0) ((uint64_t*)a.data)[tile * MQBLK + i] = w;
@@ -159,7 +156,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
   }
-  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * LOG2E;
+  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * LX_LOG2E;
   f32x16 oacc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -235,7 +232,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
         sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kb], 0, 0, 0);
       }
     // scores -> exp2 arguments (log2 units); score (kb, r) of this lane is key kb*32 + 8*(r>>2) + 4*lhi + (r&3) of the tile
-    const float bl = D.bias[sq][sk] * LOG2E;
+    const float bl = D.bias[sq][sk] * LX_LOG2E;
     const int nvalid = min(KVBLK, D.seg_len[sk] - ktl * KVBLK);
     if (cls == CLS_PARTIAL) {
       f32x4 mb[8];

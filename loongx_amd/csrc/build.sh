@@ -15,7 +15,7 @@ SRCS=(api gemm gemm_f16 gemm_modes gemm4 gemm4_f16 gemm4_split attn attn4 attn_m
 declare -A EXTRA=([attn]="-fno-honor-nans" [attn4]="-fno-honor-nans")
 pids=()
 for s in "${SRCS[@]}"; do
-  if [[ ! -f "$OBJ/$s.o" || "$HERE/$s.hip" -nt "$OBJ/$s.o" || "$HERE/common.h" -nt "$OBJ/$s.o" || "$HERE/attn_common.h" -nt "$OBJ/$s.o" || "$HERE/gemm_common.h" -nt "$OBJ/$s.o" || "$HERE/gemm8.h" -nt "$OBJ/$s.o" || "$HERE/gemm4.h" -nt "$OBJ/$s.o" || "$HERE/../../include/lx.h" -nt "$OBJ/$s.o" || "$HERE/build.sh" -nt "$OBJ/$s.o" ]]; then
+  if [[ ! -f "$OBJ/$s.o" || "$HERE/$s.hip" -nt "$OBJ/$s.o" || "$HERE/common.h" -nt "$OBJ/$s.o" || "$HERE/attn_common.h" -nt "$OBJ/$s.o" || "$HERE/row_common.h" -nt "$OBJ/$s.o" || "$HERE/gemm_common.h" -nt "$OBJ/$s.o" || "$HERE/gemm8.h" -nt "$OBJ/$s.o" || "$HERE/gemm4.h" -nt "$OBJ/$s.o" || "$HERE/../../include/lx.h" -nt "$OBJ/$s.o" || "$HERE/build.sh" -nt "$OBJ/$s.o" ]]; then
     "$HIPCC" "${FLAGS[@]}" ${EXTRA[$s]:-} -c "$HERE/$s.hip" -o "$OBJ/$s.o" &
     pids+=($!)
   fi

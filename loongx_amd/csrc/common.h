@@ -57,6 +57,32 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   bf16x2 v = {(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(uint32_t, v);
 }
+// "pack two 16-bit images into a word": element `lo` at the lower address
+__device__ __forceinline__ uint32_t pack_u16x2(uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); }
+// x -> the bf16 pair of the precise mode: hi = bf16(x), lo = bf16(x - hi); hi + lo carries x to 16 significand bits
+__device__ __forceinline__ void split_bf16_pair(float x, uint16_t& hi, uint16_t& lo) {
+  hi = f32_to_bf16(x);
+  lo = f32_to_bf16(x - bf16_to_f32(hi));
+}
+// fp32 -> OCP e4m3 (v_cvt_pk_fp8_f32), four at a time, saturating by an explicit clamp to +-448
+__device__ __forceinline__ float clamp_e4m3(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(a), clamp_e4m3(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(c), clamp_e4m3(d), w, true);
+  return (uint32_t)w;
+}
+// Key order of the V^T images. 16-bit images: within every 16 keys [0-3, 8-11, 4-7, 12-15], slot <-> key (an involution) -- the order in
+// which a lane of the attention kernels holds its probabilities after the swapped QK^T product. e4m3 images: byte j = g*32 + p of a
+// 64-key tile row holds the key below -- lane group g's 32 probabilities for the 32x32x64 f8f6f4 MFMA's B operand (lx_attn_fp8_pipe_kernel, attn.hip).
+__device__ __forceinline__ int lx_vt_interleave(int key) {
+  return (key & ~15) | (((key >> 2) & 1) << 3) | (((key >> 3) & 1) << 2) | (key & 3);
+}
+__device__ __forceinline__ int lx_vt8_key(int j) {   // j in [0, 64)
+  const int g = j >> 5, p = j & 31;
+  return (p >> 4) * 32 + 8 * ((p & 15) >> 2) + 4 * g + (p & 3);
+}
+constexpr double LX_LOG2E_F64 = 1.4426950408889634;   // log2(e): the softmax kernels keep scores in log2 units (v_exp_f32 is 2^x)
+constexpr float LX_LOG2E = (float)LX_LOG2E_F64;
 // ---- IEEE fp16 operand images (LX_OPERANDS_F16: 11 significand bits on the matrix pipe's A operand instead of bf16's 8) -------------
 // fp32 pair -> fp16 pair, round-to-nearest-even (v_cvt_pk_f16_f32), SATURATED to +-65504 (v_med3_f32: fp16 has 5 exponent bits; the
 // reference clips its fp16 residual stream the same way, block.py:275-276, 336-337). `mx` collects max |x| of everything converted
@@ -175,11 +201,16 @@ enum LxVtPos0 {
   LX_VT_POS0_MULT64_NONNEG     // a multiple of 64, >= 0
 };
 
-// Segs: QkvSegs (rowops.hip) | QkvSegsP (precise.hip, which has no vt_pos0 member): the members they share are filled here, tile0[]
-// (the prefix sum of the segments' 64-row tiles) included; vt_pos0[] (NULL: not wanted) is wherever the caller's kernel reads it.
+// up to 3 token streams of a q/k/v-prep launch; tile0[] is the prefix sum of their 64-row tiles, vt_pos0[] the first slot of each stream in
+// a V^T row (kernels that write no V^T image ignore it)
+struct QkvSegs {
+  int n;
+  int row0[3], rows_per_batch[3], vt_pos0[3], tile0[4];
+  const float* wq[3]; const float* wk[3]; const float* cos_tab[3]; const float* sin_tab[3];
+};
+
 // -> the tiles of all segments together
-template <class Segs>
-inline int lx_qkv_segs(const char* name, const lx_qkv_seg* seg, int n_seg, LxVtPos0 vt_rule, Segs& segs, int* vt_pos0) {
+inline int lx_qkv_segs(const char* name, const lx_qkv_seg* seg, int n_seg, LxVtPos0 vt_rule, QkvSegs& segs) {
   segs.n = n_seg;
   int t = 0;
   for (int i = 0; i < n_seg; ++i) {
@@ -187,9 +218,8 @@ inline int lx_qkv_segs(const char* name, const lx_qkv_seg* seg, int n_seg, LxVtP
     LX_CHECK_ARG((seg[i].cos_tab == nullptr) == (seg[i].sin_tab == nullptr), "%s: cos/sin tables must come together", name);
     LX_CHECK_ARG(vt_rule == LX_VT_POS0_ANY || (seg[i].vt_pos0 % 64 == 0 && (vt_rule == LX_VT_POS0_MULT64 || seg[i].vt_pos0 >= 0)),
                  "%s: vt_pos0 must be a multiple of 64", name);
-    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch;
+    segs.row0[i] = seg[i].row0; segs.rows_per_batch[i] = seg[i].rows_per_batch; segs.vt_pos0[i] = seg[i].vt_pos0;
     segs.wq[i] = seg[i].wq; segs.wk[i] = seg[i].wk; segs.cos_tab[i] = seg[i].cos_tab; segs.sin_tab[i] = seg[i].sin_tab;
-    if (vt_pos0) vt_pos0[i] = seg[i].vt_pos0;
     segs.tile0[i] = t;
     t += (seg[i].rows_per_batch + 63) / 64;
   }

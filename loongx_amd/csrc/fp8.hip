@@ -4,54 +4,25 @@
 //   * bf16 / fp32 -> e4m3 row converter (the attention output before to_out / proj_out);
 //   * LoRA down-projection reading an e4m3 activation image (the MLP hidden exists only as fp8 in this mode).
 // OCP e4m3 (gfx950 v_cvt_pk_fp8_f32, saturating by an explicit clamp to +-448). HBM-bound row kernels, 8-16 B per lane.
-#include "common.h"
+#include "row_common.h"
 
 namespace {
 
-__device__ __forceinline__ float clamp8(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
-__device__ __forceinline__ uint32_t pk8(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp8(a), clamp8(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp8(c), clamp8(d), w, true);
-  return (uint32_t)w;
-}
-
-// one wave per row, three passes over the (L2-resident) row; Y (bf16) may be NULL
+// one wave per row (the three-pass row body of row_common.h); Y (bf16) may be NULL
 __global__ __launch_bounds__(256) void ln_modulate_fp8_kernel(const float* __restrict__ X, int ldx, const LnSegs segs, int mod_ld, uint16_t* __restrict__ Y,
                                                               int ldy, uint8_t* __restrict__ Y8, int ldy8, float s8, int M, int D, float eps) {
-  int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  int sg = 0, acc_rows = 0;
-  while (sg < segs.n - 1 && row >= acc_rows + segs.n_rows[sg]) { acc_rows += segs.n_rows[sg]; ++sg; }
-  const int rin = row - acc_rows;
-  row = segs.row0[sg] + rin;
+  int row = blockIdx.x * 4 + (threadIdx.x >> 6), rin, sg;
+  if (!ln_row(segs, M, row, rin, sg)) return;
   const int lane = threadIdx.x & 63;
   const float* xr = X + (size_t)row * ldx;
-  float s = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q += (v[k] - mean) * (v[k] - mean);
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  const int b = rin / segs.rows_per_batch[sg];
-  const float* sh = segs.shift[sg] + (size_t)b * mod_ld;
-  const float* sc = segs.scale[sg] + (size_t)b * mod_ld;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    const f32x4 a = *(const f32x4*)(sc + c);
-    const f32x4 bsh = *(const f32x4*)(sh + c);
-    float o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (v[k] - mean) * rstd * (1.0f + a[k]) + bsh[k];
+  float mean, rstd;
+  ln_row_stats(xr, D, lane, mean, rstd, eps);
+  const float *sc, *sh;
+  ln_mod_rows(segs, sg, rin, mod_ld, sc, sh);
+  ln_emit(xr, sc, sh, D, lane, mean, rstd, [&](int c, const float (&o)[4]) {
     if (Y) *(u32x2*)(Y + (size_t)row * ldy + c) = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-    *(uint32_t*)(Y8 + (size_t)row * ldy8 + c) = pk8(o[0] * s8, o[1] * s8, o[2] * s8, o[3] * s8);
-  }
+    *(uint32_t*)(Y8 + (size_t)row * ldy8 + c) = pack_fp8x4(o[0] * s8, o[1] * s8, o[2] * s8, o[3] * s8);
+  });
 }
 
 __global__ __launch_bounds__(256) void convert_fp8_kernel(const void* __restrict__ src, int src_bf16, int lds, uint8_t* __restrict__ dst, int ldd, float s8,
@@ -70,7 +41,7 @@ __global__ __launch_bounds__(256) void convert_fp8_kernel(const void* __restrict
 #pragma unroll
       for (int j = 0; j < 4; ++j) { x[j] = a[j]; x[4 + j] = b[j]; }
     }
-    *(u32x2*)(dst + (size_t)m * ldd + k) = u32x2{pk8(x[0] * s8, x[1] * s8, x[2] * s8, x[3] * s8), pk8(x[4] * s8, x[5] * s8, x[6] * s8, x[7] * s8)};
+    *(u32x2*)(dst + (size_t)m * ldd + k) = u32x2{pack_fp8x4(x[0] * s8, x[1] * s8, x[2] * s8, x[3] * s8), pack_fp8x4(x[4] * s8, x[5] * s8, x[6] * s8, x[7] * s8)};
   }
 }
 

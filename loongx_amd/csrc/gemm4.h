@@ -454,7 +454,7 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const int rk = qkv_vt_interleave(gk * 8 + k), dk = t * 32 + (lane >> 1);
+            const int rk = lx_vt_interleave(gk * 8 + k), dk = t * 32 + (lane >> 1);
             e[t][k] = pt[rk * G4_PLD + dk];
           }
 #pragma unroll
@@ -466,6 +466,7 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
           *(u32x4*)((uint16_t*)P.qkv_vt + ((size_t)(b * H + h) * 128 + d) * P.qkv_vt_ld + P.qkv_vt_pos0 + p0 + gk * 8) = o;
         }
       } else {
+        // k / q: the norm / rotation arithmetic mirrors rms_rope8 (row_common.h); it stays a copy here: patch layout, DPP row sum, counted waits
         uint16_t* const out = (qkind == 0 && P.qkv_k) ? (uint16_t*)P.qkv_k : (uint16_t*)P.C;
         const int out_ld = (qkind == 0 && P.qkv_k) ? P.qkv_k_ld : P.ldc;
         f32x4 cs[4][2], pv[4][2];

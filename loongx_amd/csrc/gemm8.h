@@ -146,6 +146,7 @@ __device__ __forceinline__ bool lora_in_prologue(const lx_gemm_desc& P) { return
 // one kind (qkv_d % 256 == 0); a wave holds 64 columns, so the sum of squares of a head's row is the sum of two waves' partial
 // sums, exchanged through LDS once per tile. Everything is computed in fp32 on the accumulators: one bf16 rounding instead of
 // the two of the separate pass. (With fp16 operands the outputs are still bf16: they are the attention kernel's operands.)
+// The norm / rotation arithmetic mirrors rms_rope8 (row_common.h); it stays a copy here: accumulator layout, cross-wave sum of squares.
 template <int BM, int MI>
 __device__ __forceinline__ void gemm_epilogue_qkv(const lx_gemm_desc& P, f32x16 (&acc)[2][MI], char* smem, int m0, int n0, int m_base,
                                                   int wave, int wm, int wn, int lane, int l31, int lhi) {
@@ -223,7 +224,7 @@ __device__ __forceinline__ void gemm_epilogue_qkv(const lx_gemm_desc& P, f32x16 
         const int d = it * 16 + dl;
         float e[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) e[k] = patch[qkv_vt_interleave(g * 8 + k) * EP_LD + d];
+        for (int k = 0; k < 8; ++k) e[k] = patch[lx_vt_interleave(g * 8 + k) * EP_LD + d];
         u32x4 o = {pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]), pack_bf16x2(e[6], e[7])};
         *(u32x4*)(vtb + (size_t)d * P.qkv_vt_ld) = o;
       }

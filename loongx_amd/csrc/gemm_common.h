@@ -35,17 +35,6 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int PAIR_AUX_SC1 = 16;                    // gfx940+ buffer cache policy: sc1 (agent scope)
 
-__device__ __forceinline__ float clamp_e4m3(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
-__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(a), clamp_e4m3(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(c), clamp_e4m3(d), w, true);
-  return (uint32_t)w;
-}
-
-__device__ __forceinline__ int qkv_vt_interleave(int key) {  // within every 16 keys: [0-3, 8-11, 4-7, 12-15] (= rowops.hip)
-  return (key & ~15) | (((key >> 2) & 1) << 3) | (((key >> 3) & 1) << 2) | (key & 3);
-}
-
 // lid (position in the launch's tile order) -> (sub)problem g and tile (tm, tn): 4-tile-tall column groups inside a problem.
 // Two steps, with the descriptor copied BY VALUE in between: indexing the kernarg array lazily, field by field, made the tile
 // start a chain of nine dependent scalar-load round trips before the first operand DMA could be issued.

@@ -8,14 +8,10 @@
 //     (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, 1/16 of the bf16 rate), which writes its output as a pair.
 //
 // Reference arithmetic: src/flux/block.py:7-176 (attn_forward), :192-207 / :301-305 (AdaLN), diffusers apply_rotary_emb / RMSNorm.
-#include "common.h"
+#include "attn_common.h"
+#include "row_common.h"
 
 namespace {
-
-__device__ __forceinline__ void split2(float x, uint16_t& hi, uint16_t& lo) {
-  hi = f32_to_bf16(x);
-  lo = f32_to_bf16(x - bf16_to_f32(hi));
-}
 
 // ---- fp32 [M, K] -> bf16 [M, ...]: hi at column k, lo at column lo_off + k ---------------------------------------------------
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict__ src, int lds, uint16_t* __restrict__ dst, int ldd, int lo_off,
@@ -27,109 +23,59 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict
     const f32x4 v = *(const f32x4*)(src + (size_t)m * lds + k);
     uint16_t h[4], l[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) split2(v[c], h[c], l[c]);
+    for (int c = 0; c < 4; ++c) split_bf16_pair(v[c], h[c], l[c]);
     uint16_t* d = dst + (size_t)m * ldd + k;
-    *(u32x2*)d = u32x2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
-    *(u32x2*)(d + lo_off) = u32x2{(uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16)};
+    *(u32x2*)d = u32x2{pack_u16x2(h[0], h[1]), pack_u16x2(h[2], h[3])};
+    *(u32x2*)(d + lo_off) = u32x2{pack_u16x2(l[0], l[1]), pack_u16x2(l[2], l[3])};
   }
 }
 
-// ---- LayerNorm (no affine) + AdaLN modulation, fp32 in -> bf16 hi/lo pair out. One wave per row. --------------------------------
+// ---- LayerNorm (no affine) + AdaLN modulation, fp32 in -> bf16 hi/lo pair out. One wave per row (the row body of row_common.h). ----
 __global__ __launch_bounds__(256) void ln_modulate_split_kernel(const float* __restrict__ X, int ldx, const LnSegs segs, int mod_ld,
                                                                 uint16_t* __restrict__ Y, int ldy, int lo_off, int M, int D, float eps) {
-  int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  int sg = 0, acc_rows = 0;
-  while (sg < segs.n - 1 && row >= acc_rows + segs.n_rows[sg]) { acc_rows += segs.n_rows[sg]; ++sg; }
-  const int rin = row - acc_rows;
-  row = segs.row0[sg] + rin;
+  int row = blockIdx.x * 4 + (threadIdx.x >> 6), rin, sg;
+  if (!ln_row(segs, M, row, rin, sg)) return;
   const int lane = threadIdx.x & 63;
   const float* xr = X + (size_t)row * ldx;
-  float s = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q += (v[k] - mean) * (v[k] - mean);
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  const int b = rin / segs.rows_per_batch[sg];
-  const float* sh = segs.shift[sg] + (size_t)b * mod_ld;
-  const float* sc = segs.scale[sg] + (size_t)b * mod_ld;
+  float mean, rstd;
+  ln_row_stats(xr, D, lane, mean, rstd, eps);
+  const float *sc, *sh;
+  ln_mod_rows(segs, sg, rin, mod_ld, sc, sh);
   uint16_t* yr = Y + (size_t)row * ldy;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    const f32x4 a = *(const f32x4*)(sc + c);
-    const f32x4 bsh = *(const f32x4*)(sh + c);
+  ln_emit(xr, sc, sh, D, lane, mean, rstd, [&](int c, const float (&o)[4]) {
     uint16_t h[4], l[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) split2((v[k] - mean) * rstd * (1.0f + a[k]) + bsh[k], h[k], l[k]);
-    *(u32x2*)(yr + c) = u32x2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
-    *(u32x2*)(yr + lo_off + c) = u32x2{(uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16)};
-  }
+    for (int k = 0; k < 4; ++k) split_bf16_pair(o[k], h[k], l[k]);
+    *(u32x2*)(yr + c) = u32x2{pack_u16x2(h[0], h[1]), pack_u16x2(h[2], h[3])};
+    *(u32x2*)(yr + lo_off + c) = u32x2{pack_u16x2(l[0], l[1]), pack_u16x2(l[2], l[3])};
+  });
 }
 
 // ---- per-head RMSNorm(weight) + interleaved-pair RoPE on fp32 q and k, in place -------------------------------------------------
-// Block = 64 positions x 1 head x 1 batch; 16 lanes own one (row, head) vector of 128 floats (8 each = 4 rotary pairs).
-struct QkvSegsP {
-  int n;
-  int row0[3], rows_per_batch[3], tile0[4];
-  const float* wq[3]; const float* wk[3]; const float* cos_tab[3]; const float* sin_tab[3];
-};
-
-__global__ __launch_bounds__(256) void qkv_prep_f32_kernel(float* __restrict__ QKV, int ld, int q_col, int k_col, const QkvSegsP segs, float eps) {
-  int sg = 0;
-  while (sg < segs.n - 1 && (int)blockIdx.x >= segs.tile0[sg + 1]) ++sg;
-  const int p0 = ((int)blockIdx.x - segs.tile0[sg]) * 64;
-  const int rows_per_batch = segs.rows_per_batch[sg];
-  const float* __restrict__ cos_tab = segs.cos_tab[sg];
-  const float* __restrict__ sin_tab = segs.sin_tab[sg];
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int sub = tid & 15, rloc = tid >> 4;
-  const size_t rbase = (size_t)segs.row0[sg] + (size_t)b * rows_per_batch;
+// Block = 64 positions x 1 head x 1 batch; 16 lanes own one (row, head) vector of 128 floats (8 each = 4 rotary pairs). Tile decode,
+// table rows and arithmetic are row_common.h's; the pass loop is written out here and not qkv_prep_rows<IO>: through the policy hipcc
+// puts the q stores and the k loads of a pass into one branch, back to back, and the launch measured 24.2 against 23.6 us at the
+// engine's 2560 rows x 24 heads (this form: 23.6).
+__global__ __launch_bounds__(256) void qkv_prep_f32_kernel(float* __restrict__ QKV, int ld, int q_col, int k_col, const QkvSegs segs, float eps) {
+  QkvTile t;
+  qkv_tile(segs, blockIdx, threadIdx, t);
+  const float* __restrict__ cos_tab = segs.cos_tab[t.sg];
+  const float* __restrict__ sin_tab = segs.sin_tab[t.sg];
+  const size_t rbase = t.rbase();
 #pragma unroll 1
   for (int pass = 0; pass < 4; ++pass) {
-    const int p = p0 + pass * 16 + rloc;
-    const bool valid = p < rows_per_batch;
-    float* rowp = QKV + (rbase + (valid ? p : 0)) * ld + h * 128 + sub * 8;
-    f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (cos_tab && valid) {
-      const float* ct = cos_tab + (size_t)p * 128 + sub * 8;
-      const float* st = sin_tab + (size_t)p * 128 + sub * 8;
-      c0 = *(const f32x4*)ct; c1 = *(const f32x4*)(ct + 4);
-      s0 = *(const f32x4*)st; s1 = *(const f32x4*)(st + 4);
-    }
+    const int p = t.p0 + pass * 16 + t.rloc;
+    const bool valid = p < t.rows_per_batch;
+    float* rowp = QKV + (rbase + (valid ? p : 0)) * ld + t.h * 128 + t.sub * 8;
+    f32x4 c0, c1, s0, s1;
+    rope_rows(cos_tab, sin_tab, p, t.sub, valid, c0, c1, s0, s1);
 #pragma unroll
     for (int which = 0; which < 2; ++which) {   // 0: q, 1: k
-      const float* wn = which ? segs.wk[sg] : segs.wq[sg];
       float* ptr = rowp + (which ? k_col : q_col);
       f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
       if (valid) { a0 = *(const f32x4*)ptr; a1 = *(const f32x4*)(ptr + 4); }
-      float x[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-      if (wn) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-        const f32x4 w0 = *(const f32x4*)(wn + sub * 8), w1 = *(const f32x4*)(wn + sub * 8 + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = x[i] * r * w0[i]; x[4 + i] = x[4 + i] * r * w1[i]; }
-      }
-      float y[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {   // pairs (2i, 2i+1): out = x*cos + rot*sin, rot = (-x_odd, x_even)
-        const float ce = i < 2 ? c0[2 * i] : c1[2 * i - 4], co = i < 2 ? c0[2 * i + 1] : c1[2 * i - 3];
-        const float se = i < 2 ? s0[2 * i] : s1[2 * i - 4], so = i < 2 ? s0[2 * i + 1] : s1[2 * i - 3];
-        y[2 * i] = x[2 * i] * ce - x[2 * i + 1] * se;
-        y[2 * i + 1] = x[2 * i + 1] * co + x[2 * i] * so;
-      }
+      float x[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]}, y[8];
+      rms_rope8(x, which ? segs.wk[t.sg] : segs.wq[t.sg], t.sub, eps, c0, c1, s0, s1, y);
       if (valid) {
         *(f32x4*)ptr = f32x4{y[0], y[1], y[2], y[3]};
         *(f32x4*)(ptr + 4) = f32x4{y[4], y[5], y[6], y[7]};
@@ -255,10 +201,10 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32Args a) {
     for (int rq = 0; rq < 4; ++rq) {
       uint16_t hh[4], ll[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) split2(o[dblk][rq * 4 + c] * inv, hh[c], ll[c]);
+      for (int c = 0; c < 4; ++c) split_bf16_pair(o[dblk][rq * 4 + c] * inv, hh[c], ll[c]);
       const int d = dblk * 32 + 8 * rq + 4 * hi;
-      *(u32x2*)(op + d) = u32x2{(uint32_t)hh[0] | ((uint32_t)hh[1] << 16), (uint32_t)hh[2] | ((uint32_t)hh[3] << 16)};
-      if (a.o_lo_off) *(u32x2*)(op + a.o_lo_off + d) = u32x2{(uint32_t)ll[0] | ((uint32_t)ll[1] << 16), (uint32_t)ll[2] | ((uint32_t)ll[3] << 16)};
+      *(u32x2*)(op + d) = u32x2{pack_u16x2(hh[0], hh[1]), pack_u16x2(hh[2], hh[3])};
+      if (a.o_lo_off) *(u32x2*)(op + a.o_lo_off + d) = u32x2{pack_u16x2(ll[0], ll[1]), pack_u16x2(ll[2], ll[3])};
     }
 }
 
@@ -275,98 +221,65 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32Args a) {
 // 8 consecutive accumulator registers thanks to the 16-key interleave of the V^T images), with four 16-KiB operand tiles per
 // stage (K_hi, K_lo, V^T_hi, V^T_lo), double buffered = 128 KiB of LDS, eight 1-KiB LDS-DMA pieces per wave and tile.
 // ====================================================================================================================================
-typedef const __attribute__((address_space(1))) void* sp_gptr_t;
-typedef __attribute__((address_space(3))) void* sp_lptr_t;
-
-__device__ __forceinline__ int sp_vt_interleave(int key) {   // within every 16 keys: [0-3, 8-11, 4-7, 12-15] (= rowops.hip / gemm.hip)
-  return (key & ~15) | (((key >> 2) & 1) << 3) | (((key >> 3) & 1) << 2) | (key & 3);
-}
-
 struct QkvSplitArgs {
   const float* QKV; int ld, q_col, k_col, v_col;
   uint16_t* QK2; int ld2, q2_col, k2_col, lo_off;
   uint16_t* K2; int ldk2;         // where the key pair goes: QK2 / ld2 (lx_qkv_prep_split_segs) or a key image of its own (.._kv_segs)
   uint16_t* VT2; int vt_ld; long long vt_lo_off;
-  int vt_pos0[3];
   int H;
   float eps;
 };
 
-// Block = 64 positions x 1 head x 1 batch (as qkv_prep_f32_kernel); q / k: RMSNorm + RoPE in fp32, written as bf16 hi / lo pairs;
-// v: hi / lo pairs of the raw projection into the two V^T images (transposed through LDS, 16-key interleave).
-__global__ __launch_bounds__(256) void qkv_prep_split_kernel(const QkvSplitArgs a, const QkvSegsP segs) {
-  __shared__ float vt_s[64][128 + 4];
-  int sg = 0;
-  while (sg < segs.n - 1 && (int)blockIdx.x >= segs.tile0[sg + 1]) ++sg;
-  const int p0 = ((int)blockIdx.x - segs.tile0[sg]) * 64;
-  const int rows_per_batch = segs.rows_per_batch[sg];
-  const float* __restrict__ cos_tab = segs.cos_tab[sg];
-  const float* __restrict__ sin_tab = segs.sin_tab[sg];
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int sub = tid & 15, rloc = tid >> 4;
-  const size_t rbase = (size_t)segs.row0[sg] + (size_t)b * rows_per_batch;
-#pragma unroll 1
-  for (int pass = 0; pass < 4; ++pass) {
-    const int p = p0 + pass * 16 + rloc;
-    const bool valid = p < rows_per_batch;
-    const size_t grow = rbase + (valid ? p : 0);
-    const float* rowp = a.QKV + grow * a.ld + h * 128 + sub * 8;
-    f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (cos_tab && valid) {
-      const float* ct = cos_tab + (size_t)p * 128 + sub * 8;
-      const float* st = sin_tab + (size_t)p * 128 + sub * 8;
-      c0 = *(const f32x4*)ct; c1 = *(const f32x4*)(ct + 4);
-      s0 = *(const f32x4*)st; s1 = *(const f32x4*)(st + 4);
+// IO policy of qkv_prep_rows: the lane's 8 floats of q / k of QKV [rows, ld] in, bf16 hi / lo pairs out (lo at + lo_off columns); the
+// raw fp32 V chunk to the transpose buffer
+struct QkvSplitIO {
+  const QkvSplitArgs& a;
+  int h, sub, rloc;
+  float (*vt_s)[128 + 4];
+  size_t grow;
+  const float* rowp;
+  __device__ __forceinline__ void row(size_t r) { grow = r; rowp = a.QKV + r * a.ld + h * 128 + sub * 8; }
+  __device__ __forceinline__ void load8(int which, bool valid, float (&x)[8]) const {
+    const float* ptr = rowp + (which ? a.k_col : a.q_col);
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
+    if (valid) { a0 = *(const f32x4*)ptr; a1 = *(const f32x4*)(ptr + 4); }
+    x[0] = a0[0]; x[1] = a0[1]; x[2] = a0[2]; x[3] = a0[3]; x[4] = a1[0]; x[5] = a1[1]; x[6] = a1[2]; x[7] = a1[3];
+  }
+  __device__ __forceinline__ void store8(int which, bool valid, const float (&y)[8]) const {
+    if (!valid) return;
+    uint16_t hh[8], ll[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) split_bf16_pair(y[i], hh[i], ll[i]);
+    uint16_t* op = (which ? a.K2 + grow * a.ldk2 + a.k2_col : a.QK2 + grow * a.ld2 + a.q2_col) + h * 128 + sub * 8;
+    u32x4 oh, ol;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      oh[i] = pack_u16x2(hh[2 * i], hh[2 * i + 1]);
+      ol[i] = pack_u16x2(ll[2 * i], ll[2 * i + 1]);
     }
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {   // 0: q, 1: k
-      const float* wn = which ? segs.wk[sg] : segs.wq[sg];
-      const float* ptr = rowp + (which ? a.k_col : a.q_col);
-      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-      if (valid) { a0 = *(const f32x4*)ptr; a1 = *(const f32x4*)(ptr + 4); }
-      float x[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-      if (wn) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        const float r = rsqrtf(ss * (1.0f / 128.0f) + a.eps);
-        const f32x4 w0 = *(const f32x4*)(wn + sub * 8), w1 = *(const f32x4*)(wn + sub * 8 + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = x[i] * r * w0[i]; x[4 + i] = x[4 + i] * r * w1[i]; }
-      }
-      float y[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {   // pairs (2i, 2i+1): out = x*cos + rot*sin, rot = (-x_odd, x_even)
-        const float ce = i < 2 ? c0[2 * i] : c1[2 * i - 4], co = i < 2 ? c0[2 * i + 1] : c1[2 * i - 3];
-        const float se = i < 2 ? s0[2 * i] : s1[2 * i - 4], so = i < 2 ? s0[2 * i + 1] : s1[2 * i - 3];
-        y[2 * i] = x[2 * i] * ce - x[2 * i + 1] * se;
-        y[2 * i + 1] = x[2 * i + 1] * co + x[2 * i] * so;
-      }
-      if (valid) {
-        uint16_t hh[8], ll[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) split2(y[i], hh[i], ll[i]);
-        uint16_t* op = (which ? a.K2 + grow * a.ldk2 + a.k2_col : a.QK2 + grow * a.ld2 + a.q2_col) + h * 128 + sub * 8;
-        u32x4 oh, ol;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          oh[i] = (uint32_t)hh[2 * i] | ((uint32_t)hh[2 * i + 1] << 16);
-          ol[i] = (uint32_t)ll[2 * i] | ((uint32_t)ll[2 * i + 1] << 16);
-        }
-        *(u32x4*)op = oh;
-        *(u32x4*)(op + a.lo_off) = ol;
-      }
-    }
+    *(u32x4*)op = oh;
+    *(u32x4*)(op + a.lo_off) = ol;
+  }
+  __device__ __forceinline__ void stash_v(int pass, bool valid) const {
     f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
     if (valid) { v0 = *(const f32x4*)(rowp + a.v_col); v1 = *(const f32x4*)(rowp + a.v_col + 4); }
     *(f32x4*)&vt_s[pass * 16 + rloc][sub * 8] = v0;
     *(f32x4*)&vt_s[pass * 16 + rloc][sub * 8 + 4] = v1;
   }
+};
+
+// Block = 64 positions x 1 head x 1 batch (as qkv_prep_f32_kernel); q / k: RMSNorm + RoPE in fp32, written as bf16 hi / lo pairs;
+// v: hi / lo pairs of the raw projection into the two V^T images (transposed through LDS, 16-key interleave).
+__global__ __launch_bounds__(256) void qkv_prep_split_kernel(const QkvSplitArgs a, const QkvSegs segs) {
+  __shared__ float vt_s[64][128 + 4];
+  QkvTile t;
+  qkv_tile(segs, blockIdx, threadIdx, t);
+  const int tid = threadIdx.x;
+  QkvSplitIO io{a, t.h, t.sub, t.rloc, vt_s, 0, nullptr};
+  qkv_prep_rows(segs, t, a.eps, io);
   __syncthreads();
   // V^T rows: thread -> (d, 8 consecutive slots); slot -> source key via the (involutive) interleave
-  uint16_t* vtb = a.VT2 + ((size_t)(b * a.H + h) * 128) * a.vt_ld + a.vt_pos0[sg] + p0;
+  uint16_t* vtb = a.VT2 + ((size_t)(t.b * a.H + t.h) * 128) * a.vt_ld + segs.vt_pos0[t.sg] + t.p0;
   // (eight lanes per d: the eight key groups sit a multiple of 32 banks apart -- half of this kernel's LDS cycles are conflicts -- but
   //  the lanes of a d write 128 contiguous bytes; lanes along d instead (conflict-free reads, one 16-byte store per V^T row and lane)
   //  measured 47.9 vs 42.4 us)
@@ -376,10 +289,10 @@ __global__ __launch_bounds__(256) void qkv_prep_split_kernel(const QkvSplitArgs 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       uint16_t h0, l0, h1, l1;
-      split2(vt_s[sp_vt_interleave(g * 8 + 2 * i)][d], h0, l0);
-      split2(vt_s[sp_vt_interleave(g * 8 + 2 * i + 1)][d], h1, l1);
-      oh[i] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      ol[i] = (uint32_t)l0 | ((uint32_t)l1 << 16);
+      split_bf16_pair(vt_s[lx_vt_interleave(g * 8 + 2 * i)][d], h0, l0);
+      split_bf16_pair(vt_s[lx_vt_interleave(g * 8 + 2 * i + 1)][d], h1, l1);
+      oh[i] = pack_u16x2(h0, h1);
+      ol[i] = pack_u16x2(l0, l1);
     }
     *(u32x4*)(vtb + (size_t)d * a.vt_ld + g * 8) = oh;
     *(u32x4*)(vtb + a.vt_lo_off + (size_t)d * a.vt_ld + g * 8) = ol;
@@ -436,7 +349,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
       ql[ks] = *(const bf16x8*)(qp + args.qk_lo_off + ks * 16);
     }
   }
-  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * 1.4426950408889634f;   // scores are kept in log2 units
+  const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * LX_LOG2E;   // scores are kept in log2 units
   f32x16 oacc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -459,7 +372,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
         const int lslot = (lane & 15) ^ (key & 15);
         const int kin = min(kt * SP_KV + key, klen - 1);
         const __bf16* src = Kbase + (krow0 + kin) * D.ldk + img * args.qk_lo_off + lslot * 8;
-        __builtin_amdgcn_global_load_lds((sp_gptr_t)src, (sp_lptr_t)(base + img * SP_TILE + (j * NW + wave) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + img * SP_TILE + (j * NW + wave) * 1024), 16, 0, 0);
       }
       // V^T: one instruction = 8 d rows of 128 B; lane -> (row = lane>>3, slot = lane&7), slot ^= (d >> 1) & 7
       const int vpos = D.seg_vt0[sk] + kt * SP_KV;
@@ -468,7 +381,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
         const int drow = (j * NW + wave) * 8 + (lane >> 3);
         const int lslot = (lane & 7) ^ ((drow >> 1) & 7);
         const __bf16* src = Vbase + img * args.vt_lo_off + (size_t)drow * D.vt_ld + vpos + lslot * 8;
-        __builtin_amdgcn_global_load_lds((sp_gptr_t)src, (sp_lptr_t)(base + (2 + img) * SP_TILE + (j * NW + wave) * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + (2 + img) * SP_TILE + (j * NW + wave) * 1024), 16, 0, 0);
       }
     }
   };
@@ -512,7 +425,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
       }
     }
     // ---- online softmax (fp32, log2 domain, exact running maximum) ---------------------------------
-    const float bl = D.bias[sq][sk] * 1.4426950408889634f;
+    const float bl = D.bias[sq][sk] * LX_LOG2E;
     const int klen = D.seg_len[sk];
     const int kbase = kt * SP_KV + 4 * lhi;
     if (kt * SP_KV + SP_KV > klen) {   // ragged last tile of the segment: mask keys past its end
@@ -561,7 +474,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
       for (int i = 0; i < 4; ++i) {
         const float p0 = sacc[s >> 1][8 * (s & 1) + 2 * i], p1 = sacc[s >> 1][8 * (s & 1) + 2 * i + 1];
         const uint16_t h0 = f32_to_bf16(p0), h1 = f32_to_bf16(p1);
-        wh[i] = (uint32_t)h0 | ((uint32_t)h1 << 16);
+        wh[i] = pack_u16x2(h0, h1);
         wl[i] = pack_bf16x2(p0 - bf16_to_f32(h0), p1 - bf16_to_f32(h1));
       }
       const bf16x8 ph = __builtin_bit_cast(bf16x8, wh), pl = __builtin_bit_cast(bf16x8, wl);
@@ -590,7 +503,9 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
       for (int rq = 0; rq < 4; ++rq) {
         uint16_t hh[4], ll[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) split2(oacc[db][rq * 4 + c] * inv, hh[c], ll[c]);
+        for (int c = 0; c < 4; ++c) split_bf16_pair(oacc[db][rq * 4 + c] * inv, hh[c], ll[c]);
+        // (pack_u16x2's idiom written out: through the helper hipcc schedules and allocates attn_split_kernel<true> differently, an
+        //  accident of inlining order. Before converting it, compare that kernel's instruction stream with the previous build's.)
         *(u32x2*)(op + db * 32 + rq * 8) = u32x2{(uint32_t)hh[0] | ((uint32_t)hh[1] << 16), (uint32_t)hh[2] | ((uint32_t)hh[3] << 16)};
         if (args.o_lo_off)
           *(u32x2*)(op + args.o_lo_off + db * 32 + rq * 8) = u32x2{(uint32_t)ll[0] | ((uint32_t)ll[1] << 16), (uint32_t)ll[2] | ((uint32_t)ll[3] << 16)};
@@ -632,8 +547,8 @@ extern "C" int lx_qkv_prep_f32_segs(float* QKV, int ld, int q_col, int k_col, co
   LX_CHECK_ARG(seg && n_seg >= 1 && n_seg <= 3, "lx_qkv_prep_f32_segs: 1..3 segments");
   LX_CHECK_ARG(QKV && n_batches > 0 && H > 0, "lx_qkv_prep_f32_segs: bad arguments");
   LX_CHECK_ARG(ld % 4 == 0 && q_col % 4 == 0 && k_col % 4 == 0 && ((uintptr_t)QKV & 15) == 0, "lx_qkv_prep_f32_segs: ld / column offsets must be multiples of 4, QKV 16-byte aligned");
-  QkvSegsP segs;
-  const int t = lx_qkv_segs("lx_qkv_prep_f32_segs", seg, n_seg, LX_VT_POS0_ANY, segs, nullptr);
+  QkvSegs segs;
+  const int t = lx_qkv_segs("lx_qkv_prep_f32_segs", seg, n_seg, LX_VT_POS0_ANY, segs);
   if (t < 0) return t;
   hipLaunchKernelGGL(qkv_prep_f32_kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, QKV, ld, q_col, k_col, segs, eps);
   LX_LAUNCH_CHECK("lx_qkv_prep_f32_segs");
@@ -664,10 +579,9 @@ extern "C" int lx_attn_fwd_f32(const lx_attn_f32_desc* d, void* stream) {
     for (int j = 0; j < d->n_seg; ++j) any |= d->bias[i][j] > -1e37f;
     LX_CHECK_ARG(any, "lx_attn_fwd_f32: query segment %d is masked from every key segment", i);
   }
-  const float log2e = 1.4426950408889634f;
   for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) a.bias[i][j] = d->bias[i][j] * log2e;        // -inf stays -inf
-  a.scale_log2e = d->scale * log2e;
+    for (int j = 0; j < 3; ++j) a.bias[i][j] = d->bias[i][j] * LX_LOG2E;        // -inf stays -inf
+  a.scale_log2e = d->scale * LX_LOG2E;
   hipLaunchKernelGGL(attn_f32_kernel, dim3(t, d->H, d->B), dim3(256), 0, (hipStream_t)stream, a);
   LX_LAUNCH_CHECK("lx_attn_fwd_f32");
   return LX_OK;
@@ -686,9 +600,9 @@ static int lx_qkv_prep_split_impl(const char* fn, const float* QKV, int ld, int 
   LX_CHECK_ARG(ldk2 % 8 == 0 && ((uintptr_t)K2 & 15) == 0, "%s: ldk2 must be a multiple of 8, K2 16-byte aligned", fn);
   LX_CHECK_ARG(vt_ld % 64 == 0 && vt_lo_off % 8 == 0 && vt_lo_off >= (long long)n_batches * H * 128 * vt_ld && ((uintptr_t)VT2 & 15) == 0,
                "%s: vt_ld %% 64, vt_lo_off %% 8 and the lo V^T image behind the hi image required", fn);
-  QkvSegsP segs;
+  QkvSegs segs;
   QkvSplitArgs a;
-  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, a.vt_pos0);
+  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs);
   if (t < 0) return t;
   if (key_image) {
     // a launch over some segments into images that keep other segments' entries: nothing may land outside the rows and the 64-slot

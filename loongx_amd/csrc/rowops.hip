@@ -1,7 +1,7 @@
 // rowops.hip -- HBM-bound row kernels of the DiT step (gfx950): AdaLN LayerNorm+modulate, per-head
 // RMSNorm+RoPE(+V^T image), LoRA down-projection, skinny (M<=16) linears, timestep embedding, Euler step.
 // All loads/stores are 8-16 B per lane and coalesced; reductions are wave64 shuffles (no LDS, no atomics).
-#include "common.h"
+#include "row_common.h"
 #include <type_traits>
 
 namespace {
@@ -148,67 +148,34 @@ __global__ __launch_bounds__(256, 3) void ln_modulate_kernel(const float* __rest
   if constexpr (F16) report_f16_overflow(f16_mx, f16_ovf);
 }
 
-// generic D (multiple of 4): three passes over the (L2-resident) row
+// generic D (multiple of 4): the three-pass row body of row_common.h, 16-bit operand store
 template <bool F16 = false>
 __global__ __launch_bounds__(256) void ln_modulate_generic(const float* __restrict__ X, int ldx, const LnSegs segs, int mod_ld,
                                                            uint16_t* __restrict__ Y, int ldy, int M, int D, float eps, int* __restrict__ f16_ovf = nullptr) {
-  int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  int sg = 0, acc_rows = 0;
-  while (sg < segs.n - 1 && row >= acc_rows + segs.n_rows[sg]) { acc_rows += segs.n_rows[sg]; ++sg; }
-  const int rin = row - acc_rows;
-  row = segs.row0[sg] + rin;
-  const float* shift = segs.shift[sg];
-  const float* scale = segs.scale[sg];
-  const int rows_per_batch = segs.rows_per_batch[sg];
+  int row = blockIdx.x * 4 + (threadIdx.x >> 6), rin, sg;
+  if (!ln_row(segs, M, row, rin, sg)) return;
   const int lane = threadIdx.x & 63;
   const float* xr = X + (size_t)row * ldx;
-  float s = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q += (v[k] - mean) * (v[k] - mean);
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  const int b = rin / rows_per_batch;
-  const float* sh = shift + (size_t)b * mod_ld;
-  const float* sc = scale + (size_t)b * mod_ld;
+  float mean, rstd;
+  ln_row_stats(xr, D, lane, mean, rstd, eps);
+  const float *sc, *sh;
+  ln_mod_rows(segs, sg, rin, mod_ld, sc, sh);
   uint16_t* yr = Y + (size_t)row * ldy;
   float f16_mx = 0.f;
-  for (int c = lane * 4; c < D; c += 256) {
-    const f32x4 v = *(const f32x4*)(xr + c);
-    const f32x4 a = *(const f32x4*)(sc + c);
-    const f32x4 bsh = *(const f32x4*)(sh + c);
-    float o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (v[k] - mean) * rstd * (1.0f + a[k]) + bsh[k];
+  ln_emit(xr, sc, sh, D, lane, mean, rstd, [&](int c, const float (&o)[4]) {
     u32x2 w;
     w[0] = pack_op16x2<F16>(o[0], o[1], f16_mx);
     w[1] = pack_op16x2<F16>(o[2], o[3], f16_mx);
     *(u32x2*)(yr + c) = w;
-  }
+  });
   if constexpr (F16) report_f16_overflow(f16_mx, f16_ovf);
 }
 
 // ------------------------------------------------------------------------------------------------------
 // Q/K: RMSNorm(128, weight) + RoPE in place; V -> V^T image. Block = 64 positions x 1 head x 1 batch.
-// 16 lanes own one (row, head) vector of 128 bf16 (8 elements = 4 rotary pairs each).
+// 16 lanes own one (row, head) vector of 128 bf16 (8 elements = 4 rotary pairs each). Tile decode, arithmetic
+// and the general pass loop: row_common.h.
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int vt_interleave(int key) {  // within every 16 keys: [0-3, 8-11, 4-7, 12-15]
-  return (key & ~15) | (((key >> 2) & 1) << 3) | (((key >> 3) & 1) << 2) | (key & 3);
-}
-
-struct QkvSegs {
-  int n;
-  int row0[3], rows_per_batch[3], vt_pos0[3], tile0[4];
-  const float* wq[3]; const float* wk[3]; const float* cos_tab[3]; const float* sin_tab[3];
-};
 
 // FAST: every segment has norm_q / norm_k weights and RoPE tables (the DiT case). The launch is one resident generation of waves
 // (3840 waves on 1024 SIMDs at S = 2560), so its duration is the length of one thread's dependent chain of memory round trips,
@@ -239,6 +206,52 @@ __device__ __forceinline__ u32x4 f16x8_to_bf16x8(const u32x4 raw) {
   return o;
 }
 
+// The 16-bit source of the general pass loop (qkv_prep_rows): bf16 or fp16 q / k / v chunks of QKV [rows, ld], zeros for rows past the
+// end; V goes to the transpose buffer as bf16. The lane's chunk of a row is at h * 128 + sub * 8.
+template <bool IN_F16>
+struct Qkv16Src {
+  const uint16_t* QKV; int ld, q_col, k_col, v_col, h, sub, rloc;
+  uint16_t (*vt_s)[128 + 8];
+  const uint16_t* rowp;
+  __device__ __forceinline__ void row(size_t r) { rowp = QKV + r * ld + h * 128 + sub * 8; }
+  __device__ __forceinline__ u32x4 chunk(int col, bool valid) const {
+    u32x4 raw = {0u, 0u, 0u, 0u};
+    if (valid) raw = *(const u32x4*)(rowp + col);
+    return raw;
+  }
+  __device__ __forceinline__ void load8(int which, bool valid, float (&x)[8]) const { unpack16x8(chunk(which ? k_col : q_col, valid), x, IN_F16); }
+  __device__ __forceinline__ void stash_v(int pass, bool valid) const {
+    const u32x4 raw = chunk(v_col, valid);
+    *(u32x4*)&vt_s[pass * 16 + rloc][sub * 8] = IN_F16 ? f16x8_to_bf16x8(raw) : raw;
+  }
+};
+
+// bf16 results: q in place, k in place or (KIMG) to the key image K2; the V stash only when a V^T image is asked for
+template <bool IN_F16, bool KIMG>
+struct QkvBf16IO : Qkv16Src<IN_F16> {
+  uint16_t* K2; int ldk2, k2_col;
+  bool vt;
+  uint16_t* kdst;
+  __device__ __forceinline__ void row(size_t r) {
+    Qkv16Src<IN_F16>::row(r);
+    if constexpr (KIMG) kdst = K2 + r * ldk2 + k2_col + this->h * 128 + this->sub * 8;
+  }
+  __device__ __forceinline__ void store8(int which, bool valid, const float (&y)[8]) const {
+    if (!valid) return;
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
+    uint16_t* dst = const_cast<uint16_t*>(this->rowp) + (which ? this->k_col : this->q_col);
+    if constexpr (KIMG) {
+      if (which) dst = kdst;
+    }
+    *(u32x4*)dst = o;
+  }
+  __device__ __forceinline__ void stash_v(int pass, bool valid) const {
+    if (vt) Qkv16Src<IN_F16>::stash_v(pass, valid);
+  }
+};
+
 // KIMG (lx_qkv_prep_kv_segs): k goes to the same rows of a key image of its own (K2, head h at k2_col + h*128) and the k columns of QKV stay
 // as they are; q is still written in place. Together with the V^T stores below -- only the 64-slot tiles of the launched segments, the tail
 // of a segment's last tile zero-filled -- a launch over some segments leaves the other segments' keys and V^T columns alone: the per-layer
@@ -248,21 +261,18 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
                                                        const QkvSegs segs, float eps, uint16_t* __restrict__ VT, int vt_ld, int H,
                                                        uint16_t* __restrict__ K2, int ldk2, int k2_col) {
   __shared__ uint16_t vt_s[64][128 + 8];
-  int sg = 0;
-  while (sg < segs.n - 1 && (int)blockIdx.x >= segs.tile0[sg + 1]) ++sg;
-  const int p0 = ((int)blockIdx.x - segs.tile0[sg]) * 64;
-  const int row0 = segs.row0[sg], rows_per_batch = segs.rows_per_batch[sg], vt_pos0 = segs.vt_pos0[sg];
-  const float* __restrict__ wq = segs.wq[sg];
-  const float* __restrict__ wk = segs.wk[sg];
-  const float* __restrict__ cos_tab = segs.cos_tab[sg];
-  const float* __restrict__ sin_tab = segs.sin_tab[sg];
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
-  const int tid = threadIdx.x;
-  const int sub = tid & 15;        // 16-B chunk within the 128-wide head vector
-  const int rloc = tid >> 4;       // 0..15 : row within a 16-row pass
-  const size_t rbase = (size_t)row0 + (size_t)b * rows_per_batch;
+  QkvTile t;
+  qkv_tile(segs, blockIdx, threadIdx, t);
+  const int p0 = t.p0, h = t.h, b = t.b, tid = threadIdx.x, vt_pos0 = segs.vt_pos0[t.sg];
   if constexpr (FAST) {
+    // This body keeps its own copy of rms_rope8's arithmetic (row_common.h): written through the helper the values are the same but hipcc
+    // hoists the shuffle indices in another order and allocates other registers, and the launch sits on the default denoise step.
+    const int rows_per_batch = t.rows_per_batch, sub = t.sub, rloc = t.rloc;
+    const float* __restrict__ wq = segs.wq[t.sg];
+    const float* __restrict__ wk = segs.wk[t.sg];
+    const float* __restrict__ cos_tab = segs.cos_tab[t.sg];
+    const float* __restrict__ sin_tab = segs.sin_tab[t.sg];
+    const size_t rbase = t.rbase();
     const f32x4 wq0 = *(const f32x4*)(wq + sub * 8), wq1 = *(const f32x4*)(wq + sub * 8 + 4);
     const f32x4 wk0 = *(const f32x4*)(wk + sub * 8), wk1 = *(const f32x4*)(wk + sub * 8 + 4);
 #pragma unroll 1
@@ -327,62 +337,8 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
       }
     }
   } else {
-#pragma unroll 1
-  for (int pass = 0; pass < 4; ++pass) {
-    const int p = p0 + pass * 16 + rloc;
-    const bool valid = p < rows_per_batch;
-    uint16_t* rowp = QKV + (rbase + (valid ? p : 0)) * ld + h * 128 + sub * 8;
-    f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (cos_tab && valid) {
-      const float* ct = cos_tab + (size_t)p * 128 + sub * 8;
-      const float* st = sin_tab + (size_t)p * 128 + sub * 8;
-      c0 = *(const f32x4*)ct; c1 = *(const f32x4*)(ct + 4);
-      s0 = *(const f32x4*)st; s1 = *(const f32x4*)(st + 4);
-    }
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {   // 0: q, 1: k
-      const float* wn = which ? wk : wq;
-      uint16_t* ptr = rowp + (which ? k_col : q_col);
-      uint16_t* dst = ptr;
-      if constexpr (KIMG) {
-        if (which) dst = K2 + (rbase + (valid ? p : 0)) * ldk2 + k2_col + h * 128 + sub * 8;
-      }
-      u32x4 raw = {0u, 0u, 0u, 0u};
-      if (valid) raw = *(const u32x4*)ptr;
-      float x[8];
-      unpack16x8(raw, x, IN_F16);
-      if (wn) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-        const f32x4 w0 = *(const f32x4*)(wn + sub * 8), w1 = *(const f32x4*)(wn + sub * 8 + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = x[i] * r * w0[i]; x[4 + i] = x[4 + i] * r * w1[i]; }
-      }
-      float y[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {   // pairs (2i, 2i+1): out = x*cos + rot*sin, rot = (-x_odd, x_even)
-        const float ce = i < 2 ? c0[2 * i] : c1[2 * i - 4], co = i < 2 ? c0[2 * i + 1] : c1[2 * i - 3];
-        const float se = i < 2 ? s0[2 * i] : s1[2 * i - 4], so = i < 2 ? s0[2 * i + 1] : s1[2 * i - 3];
-        y[2 * i] = x[2 * i] * ce - x[2 * i + 1] * se;
-        y[2 * i + 1] = x[2 * i + 1] * co + x[2 * i] * so;
-      }
-      if (valid) {
-        u32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
-        *(u32x4*)dst = o;
-      }
-    }
-    if (VT) {  // stash V[key][d] for the transpose
-      u32x4 raw = {0u, 0u, 0u, 0u};
-      if (valid) raw = *(const u32x4*)(rowp + v_col);
-      *(u32x4*)&vt_s[pass * 16 + rloc][sub * 8] = IN_F16 ? f16x8_to_bf16x8(raw) : raw;
-    }
-  }
+    QkvBf16IO<IN_F16, KIMG> io{{QKV, ld, q_col, k_col, v_col, h, t.sub, t.rloc, vt_s, nullptr}, K2, ldk2, k2_col, VT != nullptr, nullptr};
+    qkv_prep_rows(segs, t, eps, io);
   }
   if (!VT) return;
   __syncthreads();
@@ -392,10 +348,10 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
     const int d = item >> 3, g = item & 7;
     uint16_t e[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) e[i] = vt_s[vt_interleave(g * 8 + i)][d];
+    for (int i = 0; i < 8; ++i) e[i] = vt_s[lx_vt_interleave(g * 8 + i)][d];
     u32x4 o;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = (uint32_t)e[2 * i] | ((uint32_t)e[2 * i + 1] << 16);
+    for (int i = 0; i < 4; ++i) o[i] = pack_u16x2(e[2 * i], e[2 * i + 1]);
     *(u32x4*)(vtb + (size_t)d * vt_ld + g * 8) = o;
   }
 }
@@ -403,20 +359,26 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(uint16_t* __restrict__ QK
 // ------------------------------------------------------------------------------------------------------
 // fp8 (OCP e4m3) variant for the fp8 attention path (BASELINE configs[4]): the same RMSNorm + RoPE arithmetic in fp32,
 // but q and k go to separate byte images Q8 / K8 [rows, H*128] scaled by q_scale / k_scale, and V to a byte V^T image whose
-// 64 keys per tile are ordered for the 32x32x64 f8f6f4 MFMA's B operand: byte j = g*32 + p of a tile row holds key
-// (p>>4)*32 + 8*((p&15)>>2) + 4*g + (p&3), i.e. exactly the order in which lane group g of the attention kernel holds its 32
-// probabilities (lx_attn_fp8_kernel). The bf16 QKV buffer is left untouched.
+// 64 keys per tile are in lx_vt8_key order (common.h). The bf16 QKV buffer is left untouched.
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float clamp_e4m3(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
-__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(a), clamp_e4m3(b), 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(c), clamp_e4m3(d), w, true);
-  return (uint32_t)w;
-}
-__device__ __forceinline__ int vt8_key(int j) {   // byte position within a 64-key tile row -> key
-  const int g = j >> 5, p = j & 31;
-  return (p >> 4) * 32 + 8 * ((p & 15) >> 2) + 4 * g + (p & 3);
-}
+template <bool IN_F16>
+struct QkvFp8IO : Qkv16Src<IN_F16> {
+  uint8_t* Q8; uint8_t* K8; int ld8;
+  float q_scale, k_scale;
+  size_t off8;
+  __device__ __forceinline__ void row(size_t r) {
+    Qkv16Src<IN_F16>::row(r);
+    off8 = r * ld8 + this->h * 128 + this->sub * 8;
+  }
+  __device__ __forceinline__ void store8(int which, bool valid, const float (&y)[8]) const {
+    if (!valid) return;
+    const float sc = which ? k_scale : q_scale;
+    u32x2 o;
+    o[0] = pack_fp8x4(y[0] * sc, y[1] * sc, y[2] * sc, y[3] * sc);
+    o[1] = pack_fp8x4(y[4] * sc, y[5] * sc, y[6] * sc, y[7] * sc);
+    *(u32x2*)((which ? K8 : Q8) + off8) = o;
+  }
+};
 
 template <bool IN_F16>
 __global__ __launch_bounds__(256) void qkv_prep_fp8_kernel(const uint16_t* __restrict__ QKV, int ld, int q_col, int k_col, int v_col,
@@ -424,79 +386,18 @@ __global__ __launch_bounds__(256) void qkv_prep_fp8_kernel(const uint16_t* __res
                                                            uint8_t* __restrict__ K8, int ld8, uint8_t* __restrict__ VT8, int vt_ld,
                                                            int H, float q_scale, float k_scale, float v_scale) {
   __shared__ uint16_t vt_s[64][128 + 8];
-  int sg = 0;
-  while (sg < segs.n - 1 && (int)blockIdx.x >= segs.tile0[sg + 1]) ++sg;
-  const int p0 = ((int)blockIdx.x - segs.tile0[sg]) * 64;
-  const int row0 = segs.row0[sg], rows_per_batch = segs.rows_per_batch[sg], vt_pos0 = segs.vt_pos0[sg];
-  const float* __restrict__ wq = segs.wq[sg];
-  const float* __restrict__ wk = segs.wk[sg];
-  const float* __restrict__ cos_tab = segs.cos_tab[sg];
-  const float* __restrict__ sin_tab = segs.sin_tab[sg];
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
-  const int tid = threadIdx.x;
-  const int sub = tid & 15;
-  const int rloc = tid >> 4;
-  const size_t rbase = (size_t)row0 + (size_t)b * rows_per_batch;
-#pragma unroll 1
-  for (int pass = 0; pass < 4; ++pass) {
-    const int p = p0 + pass * 16 + rloc;
-    const bool valid = p < rows_per_batch;
-    const size_t grow = rbase + (valid ? p : 0);
-    const uint16_t* rowp = QKV + grow * ld + h * 128 + sub * 8;
-    f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (cos_tab && valid) {
-      const float* ct = cos_tab + (size_t)p * 128 + sub * 8;
-      const float* st = sin_tab + (size_t)p * 128 + sub * 8;
-      c0 = *(const f32x4*)ct; c1 = *(const f32x4*)(ct + 4);
-      s0 = *(const f32x4*)st; s1 = *(const f32x4*)(st + 4);
-    }
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {   // 0: q, 1: k
-      const float* wn = which ? wk : wq;
-      u32x4 raw = {0u, 0u, 0u, 0u};
-      if (valid) raw = *(const u32x4*)(rowp + (which ? k_col : q_col));
-      float x[8];
-      unpack16x8(raw, x, IN_F16);
-      if (wn) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-        const f32x4 w0 = *(const f32x4*)(wn + sub * 8), w1 = *(const f32x4*)(wn + sub * 8 + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = x[i] * r * w0[i]; x[4 + i] = x[4 + i] * r * w1[i]; }
-      }
-      float y[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float ce = i < 2 ? c0[2 * i] : c1[2 * i - 4], co = i < 2 ? c0[2 * i + 1] : c1[2 * i - 3];
-        const float se = i < 2 ? s0[2 * i] : s1[2 * i - 4], so = i < 2 ? s0[2 * i + 1] : s1[2 * i - 3];
-        y[2 * i] = x[2 * i] * ce - x[2 * i + 1] * se;
-        y[2 * i + 1] = x[2 * i + 1] * co + x[2 * i] * so;
-      }
-      if (valid) {
-        const float sc = which ? k_scale : q_scale;
-        u32x2 o;
-        o[0] = pack_fp8x4(y[0] * sc, y[1] * sc, y[2] * sc, y[3] * sc);
-        o[1] = pack_fp8x4(y[4] * sc, y[5] * sc, y[6] * sc, y[7] * sc);
-        *(u32x2*)((which ? K8 : Q8) + grow * ld8 + h * 128 + sub * 8) = o;
-      }
-    }
-    u32x4 raw = {0u, 0u, 0u, 0u};
-    if (valid) raw = *(const u32x4*)(rowp + v_col);
-    *(u32x4*)&vt_s[pass * 16 + rloc][sub * 8] = IN_F16 ? f16x8_to_bf16x8(raw) : raw;
-  }
+  QkvTile t;
+  qkv_tile(segs, blockIdx, threadIdx, t);
+  QkvFp8IO<IN_F16> io{{QKV, ld, q_col, k_col, v_col, t.h, t.sub, t.rloc, vt_s, nullptr}, Q8, K8, ld8, q_scale, k_scale, 0};
+  qkv_prep_rows(segs, t, eps, io);
   __syncthreads();
   // V^T byte image: thread -> (d, 16 consecutive byte positions of the 64-key tile row)
-  uint8_t* vtb = VT8 + ((size_t)(b * H + h) * 128) * vt_ld + vt_pos0 + p0;
-  for (int item = tid; item < 128 * 4; item += 256) {
+  uint8_t* vtb = VT8 + ((size_t)(t.b * H + t.h) * 128) * vt_ld + segs.vt_pos0[t.sg] + t.p0;
+  for (int item = threadIdx.x; item < 128 * 4; item += 256) {
     const int d = item >> 2, c = item & 3;
     float e[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) e[i] = __uint_as_float((uint32_t)vt_s[vt8_key(c * 16 + i)][d] << 16) * v_scale;
+    for (int i = 0; i < 16; ++i) e[i] = __uint_as_float((uint32_t)vt_s[lx_vt8_key(c * 16 + i)][d] << 16) * v_scale;
     u32x4 o;
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = pack_fp8x4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
@@ -823,7 +724,7 @@ static int qkv_launch(void* QKV, int ld, int q_col, int k_col, int v_col, const 
   LX_CHECK_ARG(ld % 8 == 0 && q_col % 8 == 0 && k_col % 8 == 0 && v_col % 8 == 0, "lx_qkv_prep: ld and column offsets must be multiples of 8");
   if (VT) LX_CHECK_ARG(vt_ld % 64 == 0, "lx_qkv_prep: vt_ld must be a multiple of 64");
   QkvSegs segs;
-  const int t = lx_qkv_segs("lx_qkv_prep", seg, n_seg, VT ? LX_VT_POS0_MULT64 : LX_VT_POS0_ANY, segs, segs.vt_pos0);
+  const int t = lx_qkv_segs("lx_qkv_prep", seg, n_seg, VT ? LX_VT_POS0_MULT64 : LX_VT_POS0_ANY, segs);
   if (t < 0) return t;
   bool fast = true;
   for (int i = 0; i < segs.n; ++i) fast = fast && segs.wq[i] && segs.wk[i] && segs.cos_tab[i];
@@ -869,7 +770,7 @@ static int qkv_kv_launch(const char* fn, bool in_f16, void* QKV, int ld, int q_c
                "%s: ldk2=%d / k2_col=%d must be multiples of 8 with k2_col + H*128 <= ldk2, K2 16-byte aligned", fn, ldk2, k2_col);
   LX_CHECK_ARG(vt_ld % 64 == 0 && ((uintptr_t)VT & 15) == 0, "%s: vt_ld must be a multiple of 64, VT 16-byte aligned", fn);
   QkvSegs segs;
-  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs, segs.vt_pos0);
+  const int t = lx_qkv_segs(fn, seg, n_seg, LX_VT_POS0_MULT64_NONNEG, segs);
   if (t < 0) return t;
   for (int i = 0; i < n_seg; ++i) {
     const long long vt_end = (long long)seg[i].vt_pos0 + (seg[i].rows_per_batch + 63) / 64 * 64;
@@ -908,7 +809,7 @@ static int qkv_fp8_segs_launch(bool in_f16, const void* QKV, int ld, int q_col, 
   LX_CHECK_ARG(ld8 % 16 == 0 && vt8_ld % 64 == 0, "lx_qkv_prep_fp8_segs: ld8 %% 16 and vt8_ld %% 64 required");
   LX_CHECK_ARG(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "lx_qkv_prep_fp8_segs: scales must be positive");
   QkvSegs segs;
-  const int t = lx_qkv_segs("lx_qkv_prep_fp8_segs", seg, n_seg, LX_VT_POS0_MULT64, segs, segs.vt_pos0);
+  const int t = lx_qkv_segs("lx_qkv_prep_fp8_segs", seg, n_seg, LX_VT_POS0_MULT64, segs);
   if (t < 0) return t;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(t, H, n_batches), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)QKV, ld, q_col, k_col, v_col, segs, eps,
