@@ -17,7 +17,14 @@ namespace {
 constexpr int G4_STAGE = 256 * BK * 2 + BN * BK * 2;      // A tile + W tile of one K tile: 64 KiB
 constexpr int G4_LDS = 2 * G4_STAGE;
 constexpr int G4_PLD = 132;                                // fp32 row stride of the epilogue patch (128 + 4 pad)
-static_assert(G4_LDS <= 160 * 1024 && 4 * 2 * 16 * G4_PLD * 4 <= G4_LDS, "LDS budget / epilogue patches");
+// The epilogue's row ring: behind the patches every wave owns two 8-KiB slots that LDS-DMA fills with the rows a 16-row block needs
+// from memory (the residual rows of LX_EPI_RESID_F32, the RoPE rows of a q / k tile) one and two blocks ahead -- no destination
+// registers. It lies over operand stage 1, dead after the K loop, and ends 2 KiB past it.
+constexpr int G4_PATCHES = 4 * 2 * 16 * G4_PLD * 4;        // 4 waves x 2 patches: 67 584 bytes
+constexpr int G4_SLOT = 8 * 1024;                          // eight 1-KiB LDS-DMA pieces
+constexpr int G4_SMEM = G4_PATCHES + 4 * 2 * G4_SLOT > G4_LDS ? G4_PATCHES + 4 * 2 * G4_SLOT : G4_LDS;
+static_assert(G4_LDS <= G4_SMEM && G4_SMEM <= 160 * 1024 && G4_PATCHES % 1024 == 0 && G4_PATCHES + 4 * 2 * G4_SLOT <= G4_SMEM,
+              "LDS budget / epilogue patches / row ring");
 
 // (A split-tail form -- the tiles of a partial last round cut into K ranges, one workgroup each, meeting through the workspace -- was
 // built and measured in round 3: correct, but its park / fetch code made hipcc spill accumulators on EVERY tile's path (132 VGPRs, 52
@@ -51,7 +58,7 @@ template <bool SPLIT, bool F16 = false, int NP = 2>
 __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs args, const int sk_full, const int sk_parts, float* __restrict__ sk_slots,
                                                               int* __restrict__ sk_flags, int* __restrict__ sk_err) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  __shared__ __attribute__((aligned(1024))) char smem[G4_LDS];
+  __shared__ __attribute__((aligned(1024))) char smem[G4_SMEM];
   constexpr int BM = 256, A_BYTES = BM * BK * 2;
   const int pid = blockIdx.x;
   G4_STAMP(0)
@@ -362,6 +369,64 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
     nw0v = *(const f32x4*)nwp; nw1v = *(const f32x4*)(nwp + 4);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(nw0v), "+v"(nw1v)::"memory");
   }
+  // ---- the row ring (G4_SLOT above). A slot is eight LDS-DMA pieces with the lane map of the loads they replace: piece t of a residual
+  // block is rows t * 2 + (lane >> 5) at column c4 (res[t]); piece t * 2 + h of a q / k block is RoPE row t * 4 + (lane >> 4) at
+  // column c8 + 4 h (cs[t][h]) -- so lane l reads its 16 bytes back at piece * 1024 + l * 16. The slots are wave-private: a wave's own
+  // counted vmcnt orders its ds_read behind its DMA, no barrier. The k-th block of a workgroup's sequence uses slot k & 1; the first
+  // two blocks' rows are requested before the first put / park (on a split tile they travel under the parking and the exchange), block
+  // k + 2's as soon as block k's rows are in registers. Rows past M are clamped, columns past N moved inside the row: fetched, never used.
+  // (LX_G4_RESID_GLOBAL / LX_G4_ROPE_GLOBAL: measurement builds only, tools/build_variant.sh -- the per-block global loads these replaced)
+#ifdef LX_G4_RESID_GLOBAL
+  constexpr bool RING_RES = false;
+#else
+  constexpr bool RING_RES = true;
+#endif
+#ifdef LX_G4_ROPE_GLOBAL
+  constexpr bool RING_ROPE = false;
+#else
+  constexpr bool RING_ROPE = true;
+#endif
+  char* const ring = smem + G4_PATCHES + wave * (2 * G4_SLOT);
+  const bool ring_res = RING_RES && epi == LX_EPI_RESID_F32 && !qkv_tile;
+  const bool ring_rope = RING_ROPE && qkv_tile && qkind != 1;
+  const int ring_lane = ring_rope ? ((lane >> 4) * 128 + c8) * 4 : min(ncol, max(N - 4, 0)) * 4;     // this lane's byte offset inside a piece's first row
+  const int ring_mlast = M - 1 - mw0;                  // the wave's last valid row (residual rows are clamped to it, as the operand staging clamps)
+  auto ring_issue = [&](int b, int s) {                // the rows of 16-row block b of this wave -> slot s
+    const lx_rsrc_t rs_row = lx_make_rsrc(ring_rope ? (const void*)P.qkv_rope : (const void*)((const float*)P.C + (size_t)min(mw0, M - 1) * P.ldc));
+    if (ring_rope) {
+      const int gm = m_base + mw0 + b * 16, p0 = gm - (gm / P.rows_per_batch) * P.rows_per_batch;
+#pragma unroll
+      for (int p_ = 0; p_ < 8; ++p_)
+        lx_buf_to_lds(rs_row, (lptr_t)(ring + s * G4_SLOT + p_ * 1024), (uint32_t)ring_lane, (p0 + (p_ >> 1) * 4) * 512 + (p_ & 1) * 16);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int r = min(b * 16 + t * 2 + (lane >> 5), ring_mlast);
+        lx_buf_to_lds(rs_row, (lptr_t)(ring + s * G4_SLOT + t * 1024), (uint32_t)(r * P.ldc * 4 + ring_lane), 0);
+      }
+    }
+  };
+  // what a block of the ring waits for: its own eight pieces, with everything the wave issued AFTER them left in flight -- the eight
+  // pieces of the next block (when it exists) and the stores of the (at most two) blocks in between. ST = the store instructions of
+  // such a block that are certain to be issued: blocks before one that is in range are whole, so each of their row stores has active
+  // lanes wherever the wave has a column inside N. A count that is too low only waits longer; the loads of a partner's rows and of
+  // per-row gates are not counted (they are waited for before this point, or cost a longer wait).
+  auto ring_wait = [&](auto ko_, bool nxt, bool stores, auto st_) {
+    constexpr int ko = decltype(ko_)::value, ST = decltype(st_)::value, S = ST * (ko < 2 ? ko : 2);
+    if (stores) {
+      if (nxt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S + 8) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S) : "memory");
+    } else {
+      if (nxt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  };
+  // the gate row of a tile whose rows lie in one batch element (all of them at batch 1): once per tile, not eight times per block
+  const bool gate_tile = RING_RES && epi == LX_EPI_RESID_F32 && !qkv_tile && P.gate != nullptr &&
+                         (m_base + m0) / P.rows_per_batch == (m_base + m0 + BM - 1) / P.rows_per_batch;
+  f32x4 gate_t = {0.f, 0.f, 0.f, 0.f};
+  if (gate_tile && col_ok) gate_t = *(const f32x4*)(P.gate + (size_t)((m_base + m0) / P.rows_per_batch) * P.gate_ld + ncol);
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(gate_t)::"memory");
   // One 16-row block at a time through TWO patches: with one wave per SIMD nothing else covers the LDS round trips, so block i + 1 is
   // written (accumulators -> patch (i + 1) & 1) right behind the reads of block i, under their latency and block i's arithmetic and
   // stores (a strictly serial write -> wait -> read -> wait -> store chain per block measured 12 us per tile: tools/g4_probe.py).
@@ -394,20 +459,26 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
                                              (int)(((size_t)(wm * 128 + i * 16 + row) * 256 + wn * 128 + c4) * 4), 0, PAIR_AUX_SC1);
     }
   };
-  auto block = [&](auto ic_, auto nx_) {               // block i; nx = the block behind it in this workgroup's order (-1: none)
-    constexpr int i = decltype(ic_)::value, nx = decltype(nx_)::value;
+  // block i; nx = the block behind it in this workgroup's order (-1: none), ko = its place in that order (ring slot ko & 1), n2 = the
+  // block two places behind it (-1: none), whose rows go into the slot this block frees
+  auto block = [&](auto ic_, auto nx_, auto ko_, auto n2_) {
+    constexpr int i = decltype(ic_)::value, nx = decltype(nx_)::value, ko = decltype(ko_)::value, n2 = decltype(n2_)::value;
     const int mb = mw0 + i * 16;
     if (mb >= M) return;                               // (wave-uniform; the blocks behind it are out of range as well)
     const float* pt = patch + (i & 1) * (16 * G4_PLD);
+    const char* const slot = ring + (ko & 1) * G4_SLOT + lane * 16;
+    const bool ring_nxt = nx >= 0 && mw0 + nx * 16 < M;               // the next block's pieces are in flight behind this block's
     f32x4 res[8], gat[8];
-    if (epi == LX_EPI_RESID_F32 && !qkv_tile) {        // residual / gate rows of the block, requested first
+    if (epi == LX_EPI_RESID_F32 && !qkv_tile) {        // residual / gate rows of the block, requested first (the residual rows: by the ring)
       const int rpb = P.rows_per_batch;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const int m = mb + t * 2 + (lane >> 5);
         if (m < M && col_ok) {
-          res[t] = *(const f32x4*)((const float*)P.C + (size_t)m * P.ldc + ncol);
-          if (P.gate) gat[t] = *(const f32x4*)(P.gate + (size_t)((m_base + m) / rpb) * P.gate_ld + ncol);
+          if (!RING_RES) {
+            res[t] = *(const f32x4*)((const float*)P.C + (size_t)m * P.ldc + ncol);
+            if (P.gate) gat[t] = *(const f32x4*)(P.gate + (size_t)((m_base + m) / rpb) * P.gate_ld + ncol);
+          }
         }
       }
     }
@@ -470,15 +541,27 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
         uint16_t* const out = (qkind == 0 && P.qkv_k) ? (uint16_t*)P.qkv_k : (uint16_t*)P.C;
         const int out_ld = (qkind == 0 && P.qkv_k) ? P.qkv_k_ld : P.ldc;
         f32x4 cs[4][2], pv[4][2];
+        if constexpr (RING_ROPE) {                     // the block's RoPE rows, (cos, sin) pairs of this lane's 8 columns: landed in the slot
+          ring_wait(ko_, ring_nxt, true, std::integral_constant<int, 4>{});
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {                  // the block's RoPE rows: (cos, sin) pairs of this lane's 8 columns
-          const float* rp = P.qkv_rope + (size_t)(p0 + t * 4 + (lane >> 4)) * 128 + c8;
-          cs[t][0] = *(const f32x4*)rp; cs[t][1] = *(const f32x4*)(rp + 4);
+          for (int t = 0; t < 4; ++t) { cs[t][0] = *(const f32x4*)(slot + (t * 2) * 1024); cs[t][1] = *(const f32x4*)(slot + (t * 2 + 1) * 1024); }
+        } else {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const float* rp = P.qkv_rope + (size_t)(p0 + t * 4 + (lane >> 4)) * 128 + c8;
+            cs[t][0] = *(const f32x4*)rp; cs[t][1] = *(const f32x4*)(rp + 4);
+          }
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int row = t * 4 + (lane >> 4);
           pv[t][0] = *(const f32x4*)(pt + row * G4_PLD + c8); pv[t][1] = *(const f32x4*)(pt + row * G4_PLD + c8 + 4);
+        }
+        if constexpr (RING_ROPE && n2 >= 0) {          // the slot is free once its rows are in registers: block n2's rows go in
+          if (mw0 + n2 * 16 < M) {
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cs[0][0]), "+v"(cs[0][1]), "+v"(cs[1][0]), "+v"(cs[1][1]), "+v"(cs[2][0]), "+v"(cs[2][1]), "+v"(cs[3][0]), "+v"(cs[3][1])::"memory");
+            ring_issue(n2, ko & 1);
+          }
         }
         float yy[4][8];
 #pragma unroll
@@ -554,9 +637,29 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
 #pragma unroll
       for (int t = 0; t < 8; ++t) pv[t] = *(const f32x4*)(pt + (t * 2 + (lane >> 5)) * G4_PLD + c4);
       if (epi == LX_EPI_RESID_F32) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (RING_RES) {                      // the block's residual rows have landed in the slot; then block n2's rows go in
+          if (P.gate && !gate_tile) {
+            // a tile that spans two batch elements: per-row gates by plain loads, requested and awaited HERE, inside this branch -- a
+            // register that may hold a pending load on any path into the join below makes hipcc put a vmcnt(0) there, on every tile
+            const int rpb = P.rows_per_batch;
 #pragma unroll
-        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(res[t]), "+v"(gat[t]));
+            for (int t = 0; t < 8; ++t) {
+              const int m = mb + t * 2 + (lane >> 5);
+              if (m < M && col_ok) gat[t] = *(const f32x4*)(P.gate + (size_t)((m_base + m) / rpb) * P.gate_ld + ncol);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(gat[t]));
+          } else ring_wait(ko_, ring_nxt, nw0 < N, std::integral_constant<int, 8>{});
+#pragma unroll
+          for (int t = 0; t < 8; ++t) res[t] = *(const f32x4*)(slot + t * 1024);
+          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(res[0]), "+v"(res[1]), "+v"(res[2]), "+v"(res[3]), "+v"(res[4]), "+v"(res[5]), "+v"(res[6]), "+v"(res[7])::"memory");
+          if constexpr (n2 >= 0) { if (mw0 + n2 * 16 < M) ring_issue(n2, ko & 1); }
+        } else {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+          for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(res[t]), "+v"(gat[t]));
+        }
       }
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
@@ -569,8 +672,9 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
           if (epi == LX_EPI_RESID_F32) {
             f32x4 o = res[t];
             if (P.gate) {
+              const f32x4 gv = gate_tile ? gate_t : gat[t];
 #pragma unroll
-              for (int c_ = 0; c_ < 4; ++c_) o[c_] = __builtin_fmaf(gat[t][c_], v[c_], o[c_]);
+              for (int c_ = 0; c_ < 4; ++c_) o[c_] = __builtin_fmaf(gv[c_], v[c_], o[c_]);
             } else {
 #pragma unroll
               for (int c_ = 0; c_ < 4; ++c_) o[c_] += v[c_];
@@ -582,43 +686,51 @@ __global__ __launch_bounds__(G4_THREADS) void lx_gemm4_kernel(const GemmArgs arg
       }
     }
   };
-#define G4_B(I, NX) block(std::integral_constant<int, I>{}, std::integral_constant<int, NX>{})
+#define G4_B(I, NX, KO, N2) block(std::integral_constant<int, I>{}, std::integral_constant<int, NX>{}, std::integral_constant<int, KO>{}, std::integral_constant<int, N2>{})
 #define G4_K(I, NX) park(std::integral_constant<int, I>{}, std::integral_constant<int, NX>{})
+#define G4_R(B0, B1) if (ring_res || ring_rope) { if (mw0 + (B0) * 16 < M) ring_issue(B0, 0); if (mw0 + (B1) * 16 < M) ring_issue(B1, 1); }
   if (!split_tile) {                                   // a whole tile: its own straight line (a branch in the middle of it cost 3 % per launch)
+    G4_R(0, 1)
     if (mw0 < M) put(std::integral_constant<int, 0>{});
-    G4_B(0, 1); G4_B(1, 2); G4_B(2, 3); G4_B(3, 4); G4_B(4, 5); G4_B(5, 6); G4_B(6, 7); G4_B(7, -1);
+    G4_B(0, 1, 0, 2); G4_B(1, 2, 1, 3); G4_B(2, 3, 2, 4); G4_B(3, 4, 3, 5); G4_B(4, 5, 4, 6); G4_B(5, 6, 5, 7); G4_B(6, 7, 6, -1); G4_B(7, -1, 7, -1);
   } else if constexpr (NP == 2) {
     if (part == 0) {                                   // parks 4-7, then owns 0-3
+      G4_R(0, 1)
       if (mw0 + 64 < M) put(std::integral_constant<int, 4>{});
       G4_K(4, 5); G4_K(5, 6); G4_K(6, 7); G4_K(7, 0);
       exchange();
-      G4_B(0, 1); G4_B(1, 2); G4_B(2, 3); G4_B(3, -1);
+      G4_B(0, 1, 0, 2); G4_B(1, 2, 1, 3); G4_B(2, 3, 2, -1); G4_B(3, -1, 3, -1);
     } else {                                           // parks 0-3, then owns 4-7
+      G4_R(4, 5)
       if (mw0 < M) put(std::integral_constant<int, 0>{});
       G4_K(0, 1); G4_K(1, 2); G4_K(2, 3); G4_K(3, 4);
       exchange();
-      G4_B(4, 5); G4_B(5, 6); G4_B(6, 7); G4_B(7, -1);
+      G4_B(4, 5, 0, 6); G4_B(5, 6, 1, 7); G4_B(6, 7, 2, -1); G4_B(7, -1, 3, -1);
     }
   } else {                                             // thirds (consecutive blocks of a sequence alternate between the two patches: i & 1)
     if (part == 0) {                                   // parks 3-7, then owns 0-2
+      G4_R(0, 1)
       if (mw0 + 48 < M) put(std::integral_constant<int, 3>{});
       G4_K(3, 4); G4_K(4, 5); G4_K(5, 6); G4_K(6, 7); G4_K(7, 0);
       exchange();
-      G4_B(0, 1); G4_B(1, 2); G4_B(2, -1);
+      G4_B(0, 1, 0, 2); G4_B(1, 2, 1, -1); G4_B(2, -1, 2, -1);
     } else if (part == 1) {                            // parks 0-2, 7, 6, then owns 3-5
+      G4_R(3, 4)
       if (mw0 < M) put(std::integral_constant<int, 0>{});
       G4_K(0, 1); G4_K(1, 2); G4_K(2, 7); G4_K(7, 6); G4_K(6, 3);
       exchange();
-      G4_B(3, 4); G4_B(4, 5); G4_B(5, -1);
+      G4_B(3, 4, 0, 5); G4_B(4, 5, 1, -1); G4_B(5, -1, 2, -1);
     } else {                                           // parks 0-5, then owns 6-7
+      G4_R(6, 7)
       if (mw0 < M) put(std::integral_constant<int, 0>{});
       G4_K(0, 1); G4_K(1, 2); G4_K(2, 3); G4_K(3, 4); G4_K(4, 5); G4_K(5, 6);
       exchange();
-      G4_B(6, 7); G4_B(7, -1);
+      G4_B(6, 7, 0, -1); G4_B(7, -1, 1, -1);
     }
   }
 #undef G4_B
 #undef G4_K
+#undef G4_R
   if constexpr (F16) { if (bf16_out && !qkv_tile) report_f16_overflow(f16_mx, P.f16_ovf); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   G4_STAMP(5)
