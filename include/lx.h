@@ -32,6 +32,8 @@ extern "C" {
  *         a third additive extension of 0.4.4 (no layout change): + lx_qkv_prep_kv_segs, lx_qkv_prep_kv_f16in_segs (the 16-bit RMSNorm + RoPE +
  *         V^T pass with the keys in an image of their own)
  *         a fourth additive extension of 0.4.4 (no layout change): + lx_softmax_rows_valid (the VAE's row softmax over a padded key axis)
+ *         a fifth additive extension of 0.4.4 (no layout change): + lx_groupnorm_silu_split, lx_im2col3x3_split, lx_softmax_rows_split (the
+ *         VAE's row kernels on split-bf16 pair images: the precise-mode VAE)
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -574,6 +576,25 @@ int lx_softmax_rows(const float* S, int lds, float scale, void* P, int ldp, int 
  * read. Nothing at or beyond column n_store of a row of P is written. Any n_valid >= 1, n_store >= n_valid, lds >= n_valid,
  * ldp >= n_store; rows of S 16-byte and rows of P 8-byte aligned (base and leading dimension) take 16 / 8 B accesses, others scalar ones. */
 int lx_softmax_rows_valid(const float* S, int lds, float scale, void* P, int ldp, int M, int n_valid, int n_store, void* stream);
+
+/* The VAE's glue in precise mode (LxAutoencoderKL(precise=True), dtype=torch.float32): the same three steps with split-bf16 pair images
+ * (hi = bf16(v) at column c, lo = bf16(v - hi) at column lo_off + c of the same row; lo_off a multiple of 8) on the GEMM side, so that the
+ * convolutions and the attention run as k_segs = 2 | 3 launches of lx_gemm_bf16. The residual stream stays fp32. */
+/* lx_groupnorm_silu of fp32 x [B, P, C] into the pair image y (bf16, row stride ldy >= y_lo_off + C, y_lo_off >= C). The statistics are
+ * sums of x - shift (shift = the mean of the group's channels at the image's first pixel), fp32 partials in the same fixed order as
+ * lx_groupnorm_silu, combined in double: a mean that is large against the spread costs no accuracy. Only columns [0, C) and
+ * [y_lo_off, y_lo_off + C) of a row of y are written. ws: lx_groupnorm_workspace_bytes(). */
+int lx_groupnorm_silu_split(const float* x, int B, int P, int C, int G, const float* gamma, const float* beta, float eps, int silu,
+                            void* y, int ldy, int y_lo_off, void* ws, size_t ws_bytes, void* stream);
+/* lx_im2col3x3 of a pair image: x is [B, H, W] pixels, each a row of ldx bf16 with the hi channels at [0, C) and the lo channels at
+ * [x_lo_off, x_lo_off + C); out is [B*Ho*Wo, 2*Kpad]: the hi taps in columns [0, Kpad), the lo taps in [Kpad, 2*Kpad), each in
+ * lx_im2col3x3's order with columns [9C, Kpad) zero -- the A operand of a k_segs >= 2 launch with a_lo_off = Kpad. Modes as there.
+ * C % 8 == 0 with ldx % 8 == 0 and 16-byte aligned bases takes 16 B accesses, anything else (C = 3) 2 B ones. */
+int lx_im2col3x3_split(const void* x, int ldx, int x_lo_off, int B, int H, int W, int C, int mode, void* out, int Kpad, void* stream);
+/* lx_softmax_rows_valid with a pair output: P[m, c] / P[m, p_lo_off + c] = the hi / lo half of softmax(scale * S[m, 0:n_valid])[c],
+ * +0 in columns [n_valid, n_store) of both halves, nothing else written; columns >= n_valid of S are never read. n_valid == n_store is
+ * the unpadded key axis. p_lo_off >= n_store, ldp >= p_lo_off + n_store; alignment rules as for lx_softmax_rows_valid. */
+int lx_softmax_rows_split(const float* S, int lds, float scale, void* P, int ldp, int p_lo_off, int M, int n_valid, int n_store, void* stream);
 
 #ifdef __cplusplus
 }

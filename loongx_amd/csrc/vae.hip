@@ -250,3 +250,214 @@ extern "C" int lx_softmax_rows_valid(const float* S, int lds, float scale, void*
   LX_LAUNCH_CHECK("lx_softmax_rows_valid");
   return LX_OK;
 }
+
+// ==== precise mode: the same glue on split-bf16 operand pairs =======================================================================
+// A pair image holds x as hi = bf16(x) at column c and lo = bf16(x - hi) at column lo_off + c of the same row (split_bf16_pair): the
+// operand of a k_segs = 2 | 3 launch of lx_gemm_bf16. The residual stream between the GEMMs stays fp32.
+namespace {
+
+// ---- GroupNorm on fp32 x -> pair image. Same two passes and the same fixed-order fold as gn_stats_kernel / gn_apply_kernel, but the
+// sums are taken of x - shift, shift = mean of the group's channels at pixel 0 of the image: a sample of the group, so |mean - shift| is
+// of the order of the spread and E[d^2] - E[d]^2 cancels nothing to speak of, however large the mean is against the spread. The
+// partials are fp32 (of the shifted values); they are combined, and the variance formed, in double.
+__device__ __forceinline__ float gn_shift(const float* __restrict__ x0, int g, int cpg) {   // x0: pixel 0 of the image
+  float s = 0.f;
+  for (int j = 0; j < cpg; ++j) s += x0[g * cpg + j];
+  return s / (float)cpg;
+}
+
+__global__ __launch_bounds__(256) void gn_stats_shift_kernel(const float* __restrict__ x, int P, int C, int G, int rows_per_chunk, float* __restrict__ part) {
+  __shared__ float red[2][256];
+  const int chunk = blockIdx.x, b = blockIdx.y, nchunk = gridDim.x;
+  const int lanes_per_row = C / 4, rows_per_iter = 256 / lanes_per_row;
+  const int tid = threadIdx.x, c4 = (tid % lanes_per_row) * 4, rsub = tid / lanes_per_row;
+  const int r0 = chunk * rows_per_chunk, r1 = min(P, r0 + rows_per_chunk);
+  const int cpg = C / G;
+  const float* x0 = x + (size_t)b * P * C;
+  const float sh = gn_shift(x0, c4 / cpg, cpg);          // the thread's 4 channels lie in ONE group
+  float s = 0.f, q = 0.f;
+  const float* xb = x0 + c4;
+  for (int r = r0 + rsub; r < r1; r += rows_per_iter) {
+    f32x4 v = *(const f32x4*)(xb + (size_t)r * C);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] -= sh;
+    s += (v[0] + v[1]) + (v[2] + v[3]);
+    q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+  }
+  red[0][tid] = s;
+  red[1][tid] = q;
+  __syncthreads();
+  if (tid < G) {
+    const int lpg = cpg / 4;
+    float ss = 0.f, qq = 0.f;
+    for (int rs = 0; rs < rows_per_iter; ++rs)
+      for (int j = 0; j < lpg; ++j) {
+        const int t = rs * lanes_per_row + tid * lpg + j;
+        ss += red[0][t];
+        qq += red[1][t];
+      }
+    float* o = part + (((size_t)b * nchunk + chunk) * G + tid) * 2;
+    o[0] = ss;
+    o[1] = qq;
+  }
+}
+
+__global__ __launch_bounds__(256) void gn_apply_split_kernel(const float* __restrict__ x, int P, int C, int G, const float* __restrict__ part, int nchunk,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int silu,
+                                                             uint16_t* __restrict__ y, int ldy, int y_lo_off) {
+  const int b = blockIdx.y;
+  const int cpg = C / G, c4s = C / 4;
+  const size_t n4 = (size_t)P * c4s;
+  const double inv_n = 1.0 / ((double)P * (double)cpg);
+  const float* x0 = x + (size_t)b * P * C;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % c4s) * 4;
+    const size_t p = i / c4s;
+    const int g = c4 / cpg;
+    double s = 0.0, q = 0.0;
+    for (int k = 0; k < nchunk; ++k) {
+      const float* pp = part + (((size_t)b * nchunk + k) * G + g) * 2;
+      s += (double)pp[0];
+      q += (double)pp[1];
+    }
+    const double md = s * inv_n;                          // mean - shift
+    const float rstd = (float)(1.0 / sqrt(fmax(q * inv_n - md * md, 0.0) + (double)eps));
+    const float mean = (float)((double)gn_shift(x0, g, cpg) + md);
+    const f32x4 v = *(const f32x4*)(x0 + i * 4);
+    const f32x4 ga = *(const f32x4*)(gamma + c4), be = *(const f32x4*)(beta + c4);
+    uint16_t hh[4], ll[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float t = (v[c] - mean) * rstd * ga[c] + be[c];
+      if (silu) t = t / (1.0f + __expf(-t));
+      split_bf16_pair(t, hh[c], ll[c]);
+    }
+    uint16_t* o = y + ((size_t)b * P + p) * ldy + c4;
+    *(u32x2*)o = u32x2{pack_u16x2(hh[0], hh[1]), pack_u16x2(hh[2], hh[3])};
+    *(u32x2*)(o + y_lo_off) = u32x2{pack_u16x2(ll[0], ll[1]), pack_u16x2(ll[2], ll[3])};
+  }
+}
+
+// ---- im2col3x3_kernel on a pair image: pixel rows [hi C | ... | lo C] (stride ldx, lo at x_lo_off) -> rows [hi taps Kpad | lo taps Kpad].
+// A work item is (output pixel, half, tap, channel vector); the two halves are gathered independently, each exactly as the bf16 kernel does.
+template <bool VEC>
+__global__ __launch_bounds__(256) void im2col3x3_split_kernel(const uint16_t* __restrict__ x, int ldx, int x_lo_off, int B, int H, int W, int C, int mode,
+                                                              uint16_t* __restrict__ out, int Kpad) {
+  const int Ho = mode == 1 ? H / 2 : (mode == 2 ? 2 * H : H), Wo = mode == 1 ? W / 2 : (mode == 2 ? 2 * W : W);
+  constexpr int cv = VEC ? 8 : 1;
+  const int per_tap = C / cv;
+  const size_t rows = (size_t)B * Ho * Wo, items = rows * 18 * per_tap;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
+    const int cc = (int)(i % per_tap) * cv;
+    size_t r = i / per_tap;
+    const int tap = (int)(r % 9);
+    r /= 9;
+    const int half = (int)(r & 1);
+    r >>= 1;                                               // output pixel index (b, yo, xo)
+    const int xo = (int)(r % Wo), yo = (int)((r / Wo) % Ho), b = (int)(r / ((size_t)Wo * Ho));
+    const int dy = tap / 3, dx = tap % 3;
+    int yi, xi;
+    bool ok;
+    if (mode == 1) { yi = 2 * yo + dy; xi = 2 * xo + dx; ok = yi < H && xi < W; }
+    else if (mode == 2) { const int yu = yo + dy - 1, xu = xo + dx - 1; ok = yu >= 0 && yu < Ho && xu >= 0 && xu < Wo; yi = yu >> 1; xi = xu >> 1; }
+    else { yi = yo + dy - 1; xi = xo + dx - 1; ok = yi >= 0 && yi < H && xi >= 0 && xi < W; }
+    uint16_t* o = out + r * (2 * (size_t)Kpad) + (size_t)half * Kpad + tap * C + cc;
+    const uint16_t* s = x + (((size_t)b * H + (ok ? yi : 0)) * W + (ok ? xi : 0)) * ldx + half * x_lo_off + cc;
+    if (VEC) *(u32x4*)o = ok ? *(const u32x4*)s : u32x4{0u, 0u, 0u, 0u};
+    else *o = ok ? *s : (uint16_t)0;
+  }
+  // zero the K padding (columns [9C, Kpad) of both halves)
+  const int padc = Kpad - 9 * C;
+  if (padc > 0) {
+    const size_t n = rows * 2 * padc;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+      out[(i / padc) * Kpad + 9 * C + (i % padc)] = 0;      // i / padc = 2 * row + half, and a half is Kpad columns
+  }
+}
+
+// ---- softmax_rows_valid_kernel with a pair output: hi at P[row, c], lo at P[row, p_lo_off + c]; +0 in [n_valid, n_store) of both halves.
+// One wave per row; S is read as there (columns >= n_valid never). VEC additionally needs p_lo_off % 4 == 0.
+template <bool VEC>
+__global__ __launch_bounds__(256) void softmax_rows_split_kernel(const float* __restrict__ S, int lds, float scale, uint16_t* __restrict__ Pm, int ldp,
+                                                                 int p_lo_off, int M, int n_valid, int n_store) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float* s = S + (size_t)row * lds;
+  uint16_t* p = Pm + (size_t)row * ldp;
+  uint16_t* pl = p + p_lo_off;
+  const int nv = VEC ? (n_valid & ~3) : 0;
+  float m = -INFINITY;
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+    m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) m = fmaxf(m, s[c]);
+  m = wave_max(m) * scale;
+  float l = 0.f;
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) l += __expf(v[k] * scale - m);
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) l += __expf(s[c] * scale - m);
+  const float inv = 1.0f / wave_sum(l);
+  for (int c = lane * 4; c < nv; c += 256) {
+    const f32x4 v = *(const f32x4*)(s + c);
+    uint16_t hh[4], ll[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) split_bf16_pair(__expf(v[k] * scale - m) * inv, hh[k], ll[k]);
+    *(u32x2*)(p + c) = u32x2{pack_u16x2(hh[0], hh[1]), pack_u16x2(hh[2], hh[3])};
+    *(u32x2*)(pl + c) = u32x2{pack_u16x2(ll[0], ll[1]), pack_u16x2(ll[2], ll[3])};
+  }
+  for (int c = nv + lane; c < n_valid; c += 64) split_bf16_pair(__expf(s[c] * scale - m) * inv, p[c], pl[c]);
+  const int z0 = VEC ? min((n_valid + 3) & ~3, n_store) : n_store, z1 = VEC ? max(z0, n_store & ~3) : n_store;
+  for (int c = n_valid + lane; c < z0; c += 64) p[c] = pl[c] = 0;
+  for (int c = z0 + lane * 4; c < z1; c += 256) *(u32x2*)(p + c) = *(u32x2*)(pl + c) = u32x2{0u, 0u};
+  for (int c = z1 + lane; c < n_store; c += 64) p[c] = pl[c] = 0;
+}
+
+}  // namespace
+
+extern "C" int lx_groupnorm_silu_split(const float* x, int B, int P, int C, int G, const float* gamma, const float* beta, float eps, int silu,
+                                       void* y, int ldy, int y_lo_off, void* ws, size_t ws_bytes, void* stream) {
+  LX_CHECK_ARG(x && y && gamma && beta && ws, "lx_groupnorm_silu_split: NULL operand");
+  LX_CHECK_ARG(B > 0 && P > 0 && C > 0 && G > 0 && G <= 64 && C % G == 0 && (C / G) % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "lx_groupnorm_silu_split: need G <= 64, C %% G == 0, (C/G) %% 4 == 0, C/4 a divisor of 256 (C=%d G=%d)", C, G);
+  LX_CHECK_ARG(y_lo_off % 8 == 0 && y_lo_off >= C && ldy % 4 == 0 && ldy >= y_lo_off + C, "lx_groupnorm_silu_split: need y_lo_off %% 8 == 0, C <= y_lo_off, y_lo_off + C <= ldy, ldy %% 4 == 0 (C=%d ldy=%d y_lo_off=%d)", C, ldy, y_lo_off);
+  LX_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "lx_groupnorm_silu_split: misaligned operand");
+  LX_CHECK_ARG(ws_bytes >= lx_groupnorm_workspace_bytes(B, P, G), "lx_groupnorm_silu_split: workspace too small");
+  const int nchunk = P >= 4096 ? 64 : (P >= 256 ? 16 : 1);
+  const int rpc = (P + nchunk - 1) / nchunk;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n4 = (size_t)P * C / 4;
+  const int gx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+  hipLaunchKernelGGL(gn_stats_shift_kernel, dim3(nchunk, B), dim3(256), 0, s, x, P, C, G, rpc, (float*)ws);
+  hipLaunchKernelGGL(gn_apply_split_kernel, dim3(gx, B), dim3(256), 0, s, x, P, C, G, (const float*)ws, nchunk, gamma, beta, eps, silu, (uint16_t*)y, ldy, y_lo_off);
+  LX_LAUNCH_CHECK("lx_groupnorm_silu_split");
+  return LX_OK;
+}
+
+extern "C" int lx_im2col3x3_split(const void* x, int ldx, int x_lo_off, int B, int H, int W, int C, int mode, void* out, int Kpad, void* stream) {
+  LX_CHECK_ARG(x && out && B > 0 && H > 0 && W > 0 && C > 0, "lx_im2col3x3_split: bad arguments");
+  LX_CHECK_ARG(mode >= 0 && mode <= 2 && (mode != 1 || (H % 2 == 0 && W % 2 == 0)), "lx_im2col3x3_split: mode 0|1|2 (mode 1 needs even H, W)");
+  LX_CHECK_ARG(Kpad >= 9 * C && Kpad % 8 == 0, "lx_im2col3x3_split: Kpad=%d must be >= 9*C and a multiple of 8", Kpad);
+  LX_CHECK_ARG(x_lo_off % 8 == 0 && x_lo_off >= C && ldx >= x_lo_off + C, "lx_im2col3x3_split: need x_lo_off %% 8 == 0 and C <= x_lo_off, x_lo_off + C <= ldx (C=%d ldx=%d x_lo_off=%d)", C, ldx, x_lo_off);
+  const int Ho = mode == 1 ? H / 2 : (mode == 2 ? 2 * H : H), Wo = mode == 1 ? W / 2 : (mode == 2 ? 2 * W : W);
+  const bool vec = C % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0;
+  const size_t items = (size_t)B * Ho * Wo * 18 * (vec ? C / 8 : C);
+  const int grid = (int)((items + 255) / 256 < 16384 ? (items + 255) / 256 : 16384);
+  if (vec) hipLaunchKernelGGL(im2col3x3_split_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, x_lo_off, B, H, W, C, mode, (uint16_t*)out, Kpad);
+  else hipLaunchKernelGGL(im2col3x3_split_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, x_lo_off, B, H, W, C, mode, (uint16_t*)out, Kpad);
+  LX_LAUNCH_CHECK("lx_im2col3x3_split");
+  return LX_OK;
+}
+
+extern "C" int lx_softmax_rows_split(const float* S, int lds, float scale, void* P, int ldp, int p_lo_off, int M, int n_valid, int n_store, void* stream) {
+  LX_CHECK_ARG(S && P, "lx_softmax_rows_split: NULL operand");
+  LX_CHECK_ARG(M > 0 && n_valid >= 1 && n_store >= n_valid, "lx_softmax_rows_split: need M > 0 and 1 <= n_valid <= n_store (M=%d n_valid=%d n_store=%d)", M, n_valid, n_store);
+  LX_CHECK_ARG(lds >= n_valid && p_lo_off % 8 == 0 && p_lo_off >= n_store && ldp >= p_lo_off + n_store, "lx_softmax_rows_split: need lds >= n_valid, p_lo_off %% 8 == 0 and n_store <= p_lo_off, p_lo_off + n_store <= ldp (lds=%d ldp=%d p_lo_off=%d n_valid=%d n_store=%d)", lds, ldp, p_lo_off, n_valid, n_store);
+  const bool vec = ((uintptr_t)S & 15) == 0 && lds % 4 == 0 && ((uintptr_t)P & 7) == 0 && ldp % 4 == 0;
+  if (vec) hipLaunchKernelGGL(softmax_rows_split_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, p_lo_off, M, n_valid, n_store);
+  else hipLaunchKernelGGL(softmax_rows_split_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, p_lo_off, M, n_valid, n_store);
+  LX_LAUNCH_CHECK("lx_softmax_rows_split");
+  return LX_OK;
+}

@@ -617,6 +617,46 @@ def softmax_rows(S: torch.Tensor, P: torch.Tensor, scale: float, n_valid: Option
           "lx_softmax_rows_valid")
 
 
+# The same three on split-bf16 pair images (precise mode): hi at column c, lo at column lo_off + c of the same row.
+def _req_pair(t, n_cols: int, lo_off: int, name: str) -> None:
+    _req(t, torch.bfloat16, name)
+    if lo_off % 8:
+        raise ValueError(f"{name}: lo_off={lo_off} must be a multiple of 8")
+    if lo_off < n_cols or t.stride(-2) < lo_off + n_cols or t.stride(-1) != 1:
+        raise ValueError(f"{name}: rows of {t.stride(-2)} elements cannot hold a hi and a lo half of {n_cols} columns with lo_off={lo_off}")
+
+
+def groupnorm_silu_split(x: torch.Tensor, gamma, beta, y: torch.Tensor, y_lo_off: int, groups: int = 32, eps: float = 1e-6, silu: bool = True) -> None:
+    """x fp32 [B, P, C] (contiguous) -> the pair image y bf16 [B*P, >= y_lo_off + C] (row stride y.stride(0))."""
+    B, P, Cc = x.shape
+    _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta"); _req_pair(y, Cc, y_lo_off, "y")
+    assert x.is_contiguous() and y.dim() == 2 and y.shape[0] == B * P, "groupnorm_silu_split: x contiguous, one row of y per pixel"
+    nb = lib.lx_groupnorm_workspace_bytes(B, P, groups)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    check(lib.lx_groupnorm_silu_split(x.data_ptr(), B, P, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps, int(silu), y.data_ptr(), y.stride(0),
+                                      y_lo_off, ws.data_ptr(), nb, _stream()), "lx_groupnorm_silu_split")
+
+
+def im2col3x3_split(x: torch.Tensor, C_: int, x_lo_off: int, out: torch.Tensor, mode: int = 0) -> None:
+    """x bf16 [B, H, W, ld]: pair pixels of C_ channels (hi at 0, lo at x_lo_off; W, H contiguous, row stride x.stride(2)) -> out bf16
+    [B*Ho*Wo, 2*Kpad] (contiguous): hi taps | lo taps."""
+    _req_pair(x, C_, x_lo_off, "x"); _req(out, torch.bfloat16, "out")
+    B, H, W, _ = x.shape
+    ld = x.stride(2)
+    assert x.stride(1) == W * ld and x.stride(0) == H * W * ld, "im2col3x3_split: pixels must lie back to back"
+    assert out.dim() == 2 and out.is_contiguous() and out.shape[1] % 2 == 0, "im2col3x3_split: out is [rows, 2*Kpad], contiguous"
+    check(lib.lx_im2col3x3_split(x.data_ptr(), ld, x_lo_off, B, H, W, C_, mode, out.data_ptr(), out.shape[1] // 2, _stream()), "lx_im2col3x3_split")
+
+
+def softmax_rows_split(S: torch.Tensor, P: torch.Tensor, scale: float, n_valid: int, n_store: int, p_lo_off: int) -> None:
+    """The pair P (hi at column c, lo at p_lo_off + c) = softmax(scale * S[:, :n_valid]) row by row; columns [n_valid, n_store) of both
+    halves are set to +0, nothing else of P is written and columns >= n_valid of S are not read."""
+    _req(S, torch.float32, "S"); _req_pair(P, n_store, p_lo_off, "P")
+    assert P.shape[0] == S.shape[0] and S.shape[1] >= n_valid, "softmax_rows_split: S and P need the same rows, S at least n_valid columns"
+    check(lib.lx_softmax_rows_split(S.data_ptr(), S.stride(0), scale, P.data_ptr(), P.stride(0), p_lo_off, S.shape[0], int(n_valid), int(n_store), _stream()),
+          "lx_softmax_rows_split")
+
+
 # ---- CS3 / DGF -------------------------------------------------------------------------------------------
 def s4_scan(u, lam, w, D, y) -> None:
     B, H, Lq = u.shape

@@ -12,12 +12,19 @@ token count P = h*w that is no multiple of 64 pads the attention's key axis to P
 gives the pad keys probability +0 (multiples of 64 take the unpadded launches). Scratch per image: P * Ppad * 6 bytes (fp32 scores
 + bf16 probabilities). Parameter names are diffusers' (`decoder.up_blocks.0.resnets.1.conv1.weight` ...),
 so `vae/diffusion_pytorch_model.safetensors` of a FLUX.1 checkpoint loads as is.
+
+`precise=True` (what `dtype=torch.float32` selects, as for the transformer) keeps the fp32 residual stream and makes every GEMM operand a
+split-bf16 pair (hi = bf16(v), lo = bf16(v - hi), lo_off columns further in the same row): `lx_groupnorm_silu_split` writes pairs,
+`lx_split_bf16` replaces the bf16 casts, `lx_im2col3x3_split` gathers [hi taps | lo taps] rows, the GEMMs run with k_segs = 2 (weights
+that are bf16-representable, FLUX.1's) or 3 (weights packed as [W_hi | W_lo], decided per tensor at load time) and the attention's q, k,
+v^T, probabilities (`lx_softmax_rows_split`) and output are pairs too. Biases and the GroupNorm affine are fp32 in both modes. Scratch per
+image in precise mode: P * Ppad * 8 bytes (fp32 scores + the bf16 probability pair).
 """
 from __future__ import annotations
 
 import math
 from types import SimpleNamespace
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -30,6 +37,13 @@ FLUX_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=16, block_
 
 def _pad_to(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+class _Pair(NamedTuple):
+    """A GEMM operand of the precise mode: t bf16 [M, ld] with the hi halves of the C channels at columns [0, C), the lo halves at [lo, lo + C)."""
+    t: torch.Tensor
+    C: int
+    lo: int
 
 
 class DiagonalGaussianDistribution:
@@ -50,13 +64,14 @@ class DiagonalGaussianDistribution:
 
 
 class LxAutoencoderKL:
-    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[dict] = None, device="cuda"):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[dict] = None, device="cuda", precise: bool = False):
         cfg = dict(FLUX_VAE_CONFIG)
         cfg.update(config or {})
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
         self.config = SimpleNamespace(**cfg)
         self.device = torch.device(device)
         self.dtype = torch.float32
+        self.precise = bool(precise)
         self.G = cfg["norm_num_groups"]
         self.w: Dict[str, torch.Tensor] = {}
         sd = state_dict
@@ -72,12 +87,22 @@ class LxAutoencoderKL:
     # ---- weights -------------------------------------------------------------------------------------------------------
     def _pack_conv(self, name: str, w: torch.Tensor, b: Optional[torch.Tensor]) -> None:
         """[Cout, Cin, kh, kw] -> bf16 [Npad, Kpad] with column = (dy*kw + dx)*Cin + c (the im2col order), zero padded to the
-        GEMM's granules (K % 64, N % 8)."""
+        GEMM's granules (K % 64, N % 8). Precise mode also records `<name>.segs` and widens the image to [Npad, 2 Kpad] =
+        [W_hi | W_lo] where that is 3."""
         co, ci, kh, kw = w.shape
         W = w.detach().to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
         Np, Kp = _pad_to(co, 8), _pad_to(kh * kw * ci, 64)
-        Wp = torch.zeros(Np, Kp, dtype=torch.bfloat16, device=self.device)
-        Wp[:co, : kh * kw * ci] = W.to(torch.bfloat16)
+        Wh = W.to(torch.bfloat16)
+        if self.precise:
+            # k_segs of the launches on this tensor: 3 with the image [W_hi | W_lo] when any element has a bf16 residual, else 2 on the
+            # plain image. to_v is the A operand of v^T = Wv n^T against the pair n (k_segs = 3), so it always carries a lo half.
+            Wl = (W - Wh.float()).to(torch.bfloat16)
+            segs = 3 if name.endswith(".to_v") or bool((Wl != 0).any()) else 2
+            self.w[name + ".segs"] = segs
+        Wp = torch.zeros(Np, Kp * (2 if self.precise and segs == 3 else 1), dtype=torch.bfloat16, device=self.device)
+        Wp[:co, : kh * kw * ci] = Wh
+        if self.precise and segs == 3:
+            Wp[:co, Kp: Kp + kh * kw * ci] = Wl
         bp = torch.zeros(Np, dtype=torch.float32, device=self.device)
         if b is not None:
             bp[:co] = b.detach().to(self.device, torch.float32)
@@ -87,6 +112,10 @@ class LxAutoencoderKL:
     # ---- building blocks (x: fp32 [B*H*W, C]) ----------------------------------------------------------------------------
     def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         C = x.shape[1]
+        if self.precise:
+            y = torch.empty(x.shape[0], 2 * C, dtype=torch.bfloat16, device=self.device) if out is None else out
+            ops.groupnorm_silu_split(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y, C, self.G, 1e-6, silu)
+            return _Pair(y, C, C)
         y = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device) if out is None else out
         ops.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y.view(B, -1, C), self.G, 1e-6, silu)
         return y
@@ -94,10 +123,22 @@ class LxAutoencoderKL:
     def _conv3(self, h: torch.Tensor, B: int, H: int, W: int, name: str, mode: int = 0, out: Optional[torch.Tensor] = None,
                epilogue: int = LX_EPI_STORE_F32) -> Tuple[torch.Tensor, int, int]:
         """3x3 convolution of bf16 NHWC h [B*H*W, Cin] as im2col + GEMM; image by image so the im2col scratch stays one image
-        large. out: fp32 [B*Ho*Wo, Npad] (epilogue STORE_F32 / RESID_F32 accumulates into it) or bf16 (STORE_BF16)."""
+        large. out: fp32 [B*Ho*Wo, Npad] (epilogue STORE_F32 / RESID_F32 accumulates into it) or bf16 (STORE_BF16).
+        Precise mode: h is a _Pair, the rows are [hi taps | lo taps] and the GEMM takes them with k_segs = 2 | 3."""
         Wt, bias = self.w[name + ".w"], self.w[name + ".bias"]
-        Cin = h.shape[1]
         Ho, Wo = (H // 2, W // 2) if mode == 1 else ((2 * H, 2 * W) if mode == 2 else (H, W))
+        if self.precise:
+            segs = self.w[name + ".segs"]
+            Np, Kp = Wt.shape[0], Wt.shape[1] // (segs - 1)
+            if out is None:
+                out = torch.empty(B * Ho * Wo, Np, dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
+            cols = torch.empty(Ho * Wo, 2 * Kp, dtype=torch.bfloat16, device=self.device)
+            hv = h.t.view(B, H, W, h.t.shape[1])
+            for b in range(B):
+                ops.im2col3x3_split(hv[b:b + 1], h.C, h.lo, cols, mode)
+                ops.gemm([ops.gemm_desc(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp)])
+            return out, Ho, Wo
+        Cin = h.shape[1]
         Np, Kp = Wt.shape
         if out is None:
             out = torch.empty(B * Ho * Wo, Np, dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
@@ -109,25 +150,51 @@ class LxAutoencoderKL:
         return out, Ho, Wo
 
     def _lin(self, a: torch.Tensor, name: str, out: Optional[torch.Tensor] = None, epilogue: int = LX_EPI_STORE_BF16) -> torch.Tensor:
+        """Precise mode: a is a _Pair with lo = K (channel counts here are multiples of 64), and a bf16 store writes the output pair
+        [M, 2 Npad] (lo half Npad columns after the hi half)."""
         Wt, bias = self.w[name + ".w"], self.w[name + ".bias"]
+        if self.precise:
+            segs = self.w[name + ".segs"]
+            Np, Kp = Wt.shape[0], Wt.shape[1] // (segs - 1)
+            assert a.C == Kp and a.lo == Kp, (name, a.C, a.lo, Kp)
+            pair_out = epilogue == LX_EPI_STORE_BF16
+            if out is None:
+                out = torch.empty(a.t.shape[0], 2 * Np if pair_out else Np, dtype=torch.bfloat16 if pair_out else torch.float32, device=self.device)
+            ops.gemm([ops.gemm_desc(a.t, Wt, out, bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp, c_lo_off=Np if pair_out else 0)])
+            return out
         if out is None:
             out = torch.empty(a.shape[0], Wt.shape[0], dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
         ops.gemm([ops.gemm_desc(a, Wt, out, bias=bias, epilogue=epilogue)])
         return out
+
+    def _operand(self, x: torch.Tensor):
+        """The fp32 stream x [M, C] as a GEMM operand: bf16 [M, C], or in precise mode the pair [M, 2 * roundup(C, 8)] (`lx_split_bf16`; a
+        channel count that is no multiple of 4 -- the encoder's RGB input -- is zero-padded to one first, which is torch plumbing)."""
+        M, C = x.shape
+        if not self.precise:
+            xb = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
+            ops.convert(xb, x)
+            return xb
+        if C % 4:
+            x = torch.nn.functional.pad(x, (0, _pad_to(C, 4) - C))
+        lo = _pad_to(C, 8)
+        y = torch.empty(M, 2 * lo, dtype=torch.bfloat16, device=self.device)
+        ops.split_bf16(x, y, lo)
+        return _Pair(y, C, lo)
 
     def _resnet(self, x: torch.Tensor, B: int, H: int, W: int, p: str) -> torch.Tensor:
         h = self._gn(x, B, p + ".norm1")
         h1, _, _ = self._conv3(h, B, H, W, p + ".conv1")
         t = self._gn(h1, B, p + ".norm2")
         if (p + ".conv_shortcut.w") in self.w:
-            xb = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
-            ops.convert(xb, x)
-            x = self._lin(xb, p + ".conv_shortcut", epilogue=LX_EPI_STORE_F32)
+            x = self._lin(self._operand(x), p + ".conv_shortcut", epilogue=LX_EPI_STORE_F32)
         self._conv3(t, B, H, W, p + ".conv2", out=x, epilogue=LX_EPI_RESID_F32)          # x += conv2(t)
         return x
 
     def _attn(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
         """Single-head attention over the P = H*W tokens of each image (diffusers Attention, residual_connection=True)."""
+        if self.precise:
+            return self._attn_precise(x, B, P, p)
         if P % 64:
             return self._attn_ragged(x, B, P, p)
         C = x.shape[1]
@@ -175,6 +242,34 @@ class LxAutoencoderKL:
         self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
         return x
 
+    def _attn_precise(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
+        """_attn on pairs, one path for every token count: the key axis is padded to Ppad = roundup(P, 64) as in _attn_ragged (zero-tailed n
+        and k, both halves; Ppad == P when P is a multiple of 64). q, k, v^T, the probabilities and the attention output are pair images and
+        all three products are k_segs = 3 launches (hi hi + lo hi + hi lo); to_out accumulates into the fp32 stream."""
+        C = x.shape[1]
+        Pp = _pad_to(P, 64)
+        rows = (B - 1) * P + Pp
+        n = torch.zeros(rows, 2 * C, dtype=torch.bfloat16, device=self.device)
+        k = torch.zeros(rows, 2 * C, dtype=torch.bfloat16, device=self.device)
+        self._gn(x, B, p + ".group_norm", silu=False, out=n[: B * P])
+        np_ = _Pair(n[: B * P], C, C)
+        q = self._lin(np_, p + ".to_q")
+        self._lin(np_, p + ".to_k", out=k[: B * P])
+        Wv, bv = self.w[p + ".to_v.w"], self.w[p + ".to_v.bias"]                                      # [C, 2C] = [Wv_hi | Wv_lo]
+        assert Wv.shape == (C, 2 * C), (Wv.shape, C)
+        S = torch.empty(P, Pp, dtype=torch.float32, device=self.device)
+        Pm = torch.empty(P, 2 * Pp, dtype=torch.bfloat16, device=self.device)
+        vT = torch.empty(C, 2 * Pp, dtype=torch.bfloat16, device=self.device)
+        o = torch.empty(B * P, 2 * C, dtype=torch.bfloat16, device=self.device)
+        for b in range(B):
+            r, rp = slice(b * P, (b + 1) * P), slice(b * P, b * P + Pp)
+            ops.gemm([ops.gemm_desc(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32, N=Pp, K=C, k_segs=3, a_lo_off=C)])             # S[:, :P] = q k^T
+            ops.softmax_rows_split(S, Pm, 1.0 / math.sqrt(C), P, Pp, Pp)                                                     # Pm[:, P:Pp] = +0, both halves
+            ops.gemm([ops.gemm_desc(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16, N=Pp, K=C, k_segs=3, a_lo_off=C, c_lo_off=Pp)])  # v^T[:, :P] = Wv n^T
+            ops.gemm([ops.gemm_desc(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16, N=C, K=Pp, k_segs=3, a_lo_off=Pp, c_lo_off=C)])
+        self._lin(_Pair(o, C, C), p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
+        return x
+
     def _mid(self, x, B, H, W, p):
         x = self._resnet(x, B, H, W, p + ".resnets.0")
         x = self._attn(x, B, H * W, p + ".attentions.0")
@@ -183,22 +278,26 @@ class LxAutoencoderKL:
     def _nhwc_bf16(self, t: torch.Tensor) -> torch.Tensor:
         return t.to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
 
+    def _input(self, t: torch.Tensor):
+        """NCHW input -> the operand of conv_in: NHWC rows [B*H*W, C], bf16 or (precise mode) the pair of the fp32 values."""
+        if self.precise:
+            return self._operand(t.to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous())
+        return self._nhwc_bf16(t).view(-1, t.shape[1])
+
     # ---- public surface -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
         """z [B, latent, h, w] (any h, w >= 1) -> image [B, 3, 8h, 8w] fp32."""
         cfg = self.config
         B, _, H, W = z.shape
-        x, _, _ = self._conv3(self._nhwc_bf16(z).view(B * H * W, -1), B, H, W, "decoder.conv_in")
+        x, _, _ = self._conv3(self._input(z), B, H, W, "decoder.conv_in")
         x = self._mid(x, B, H, W, "decoder.mid_block")
         rev = list(reversed(cfg.block_out_channels))
         for i in range(len(rev)):
             for j in range(cfg.layers_per_block + 1):
                 x = self._resnet(x, B, H, W, f"decoder.up_blocks.{i}.resnets.{j}")
             if i < len(rev) - 1:
-                xb = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
-                ops.convert(xb, x)
-                x, H, W = self._conv3(xb, B, H, W, f"decoder.up_blocks.{i}.upsamplers.0.conv", mode=2)
+                x, H, W = self._conv3(self._operand(x), B, H, W, f"decoder.up_blocks.{i}.upsamplers.0.conv", mode=2)
         h = self._gn(x, B, "decoder.conv_norm_out")
         y, _, _ = self._conv3(h, B, H, W, "decoder.conv_out")
         img = y[:, : cfg.out_channels].reshape(B, H, W, cfg.out_channels).permute(0, 3, 1, 2).contiguous()
@@ -212,14 +311,12 @@ class LxAutoencoderKL:
         nd = len(cfg.block_out_channels) - 1
         if H % (1 << nd) or W % (1 << nd):
             raise ValueError(f"image {H}x{W}: sides must be multiples of {1 << nd} (the encoder halves them {nd} times)")
-        x, _, _ = self._conv3(self._nhwc_bf16(images).view(B * H * W, -1), B, H, W, "encoder.conv_in")
+        x, _, _ = self._conv3(self._input(images), B, H, W, "encoder.conv_in")
         for i in range(len(cfg.block_out_channels)):
             for j in range(cfg.layers_per_block):
                 x = self._resnet(x, B, H, W, f"encoder.down_blocks.{i}.resnets.{j}")
             if i < nd:
-                xb = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
-                ops.convert(xb, x)
-                x, H, W = self._conv3(xb, B, H, W, f"encoder.down_blocks.{i}.downsamplers.0.conv", mode=1)
+                x, H, W = self._conv3(self._operand(x), B, H, W, f"encoder.down_blocks.{i}.downsamplers.0.conv", mode=1)
         x = self._mid(x, B, H, W, "encoder.mid_block")
         h = self._gn(x, B, "encoder.conv_norm_out")
         y, _, _ = self._conv3(h, B, H, W, "encoder.conv_out")
