@@ -142,7 +142,11 @@ typedef struct lx_gemm_desc {
   const float* qkv_norm_k;   /* [128] */
   const float* qkv_rope;     /* [rows_per_batch, 128] fp32: (cos, sin) of rotary pair i at [2i, 2i+1] (identity: 1, 0) */
   void* qkv_vt;              /* bf16 [B * qkv_d/128, 128, qkv_vt_ld]: V^T image, key p of the stream at slot qkv_vt_pos0 + il(p), il =
-                              * the 16-key interleave of lx_qkv_prep */
+                              * the 16-key interleave of lx_qkv_prep. The epilogue writes exactly the slots of the keys that exist,
+                              * [qkv_vt_pos0, qkv_vt_pos0 + rows_per_batch) of every (batch, head, d) row (in qkv_vt8: the bytes of those
+                              * keys), under every launch plan. Unlike lx_qkv_prep it leaves the pad slots up to the next multiple of
+                              * 64 ALONE, and the attention kernels multiply them (by zero probabilities): the caller's image must
+                              * start zero-filled (once; nothing writes the pad slots afterwards). */
   void* qkv_k;               /* NULL: the k columns are stored in place in C. Otherwise bf16 [M, qkv_k_ld]: row m's k head h at column h*128 of
                               * a SEPARATE image (one per layer: a token stream whose queries see only its own keys -- model_config
                               * independent_condition / union_cond_attn = False -- then keeps its keys and values across denoise steps) */

@@ -299,3 +299,154 @@ def max_abs_score_log2(q, k, lens, bias):
             if bias[i][j] != float("-inf"):
                 worst = max(worst, float((s[..., e[i]:e[i + 1], e[j]:e[j + 1]] + bias[i][j] * 1.4426950408889634).abs().max()))
     return worst
+
+
+# ------------------------------------------------------------------------------------------------ LX_EPI_QKV, float64
+# The reference of tests/test_qkv_epilogue_tiles_gpu.py: what the q/k/v projection epilogue (csrc/gemm8.h gemm_epilogue_qkv, csrc/gemm4.h)
+# makes of the fp32 sums, restated in float64 (tests/test_qkv_epilogue_ref_cpu.py pins it to oracle.flux_modules on the CPU).
+U32 = 2.0 ** -23          # fp32 ulp at 1 (twice the unit roundoff: the error terms below are upper bounds)
+
+
+def rmsnorm_heads_ref(y, w, Ey=None, eps=1e-6):
+    """RMSNorm(128, w, eps) over every head of y [M, H * 128], float64. With Ey (a bound on the error of y as the kernel holds it) also a
+    bound on the error of the result: the propagated Ey -- |r w| Ey on the element itself, and through r = rsqrt(mean y^2 + eps):
+    |dr / r| <= sum_j |y_j| Ey_j / (128 (mean y^2 + eps)). (The fp32 roundings of the norm itself are added by qk_norm_rope_ref.)"""
+    M = y.shape[0]
+    x = y.double().view(M, -1, 128)
+    ms = x.pow(2).mean(-1, keepdim=True) + eps
+    out = x * torch.rsqrt(ms) * w.double()
+    if Ey is None:
+        return out.view(M, -1)
+    Ey = Ey.double().view(M, -1, 128)
+    E = (torch.rsqrt(ms) * w.double()).abs() * Ey + out.abs() * (x.abs() * Ey).sum(-1, keepdim=True) / (128.0 * ms)
+    return out.view(M, -1), E.view(M, -1)
+
+
+def rope_pairs_ref(x, cs, L, m_base=0):
+    """Interleaved-pair RoPE of x [M, H * 128] (float64): row m is position (m_base + m) % L of its batch element, cs [L, 128] holds
+    (cos, sin) of pair i at [2i, 2i + 1]. Returns (out, |x cos| + |x' sin|): the magnitude a rounding error of the rotation is relative to."""
+    M = x.shape[0]
+    x = x.double().view(M, -1, 64, 2)
+    pos = (m_base + torch.arange(M, device=x.device)) % L
+    c, s = cs.double()[pos, 0::2][:, None, :], cs.double()[pos, 1::2][:, None, :]          # [M, 1, 64]
+    e, o = x[..., 0], x[..., 1]
+    out = torch.stack([e * c - o * s, o * c + e * s], -1)
+    mag = torch.stack([(e * c).abs() + (o * s).abs(), (o * c).abs() + (e * s).abs()], -1)
+    return out.view(M, -1), mag.view(M, -1)
+
+
+def qk_norm_rope_ref(y, w, cs, L, m_base=0, Ey=None):
+    """k or q of LX_EPI_QKV in float64 from the projection y [M, H * 128] (rows m_base .. of a stream of L-row batch elements, row-major
+    [B * L, D]). With Ey also E, the fp32 error bound of the kernel's expression, built as tests/test_rowops_gpu.py::qk_ref builds it --
+    RMSNorm: 128 squares summed, rsqrtf and two products: relative <= 12 U32 on x r w; RoPE x c - x' s: two products and a difference,
+    <= 4 U32 (|x c| + |x' s|) on top -- plus Ey carried through both steps."""
+    if Ey is None:
+        return rope_pairs_ref(rmsnorm_heads_ref(y, w), cs, L, m_base)[0]
+    x, Ex = rmsnorm_heads_ref(y, w, Ey)
+    out, mag = rope_pairs_ref(x, cs, L, m_base)
+    Eo = rope_pairs_ref(Ex, cs, L, m_base)[1]                  # |c| Ex + |s| Ex': the magnitude of the rotation of the (non-negative) Ex
+    return out, Eo + 16 * U32 * mag
+
+
+def vt_slot_keys(n):
+    """key held by slot j of a 16-bit V^T image, j in [0, n): the 16-key order [0-3, 8-11, 4-7, 12-15] (an involution)"""
+    j = torch.arange(n)
+    return (j & ~15) + torch.tensor(VT_PERM16)[j & 15]
+
+
+def vt8_slot_keys(n):
+    """key held by byte j of an e4m3 V^T image row, j in [0, n), n % 64 == 0: within a 64-key tile byte g * 32 + p holds key
+    (p >> 4) * 32 + 8 ((p & 15) >> 2) + 4 g + (p & 3) (include/lx.h: the f8f6f4 MFMA's operand order)"""
+    j = torch.arange(n)
+    g, p = (j & 63) >> 5, j & 31
+    return (j & ~63) + (p >> 4) * 32 + 8 * ((p & 15) >> 2) + 4 * g + (p & 3)
+
+
+def vt_interleave(v, fp8=False):
+    """v [..., L, 128] in key order -> the V^T image rows [..., 128, pad64(L)] (slots of keys that do not exist: zero)"""
+    L = v.shape[-2]
+    n = (L + 63) // 64 * 64
+    keys = (vt8_slot_keys(n) if fp8 else vt_slot_keys(n)).to(v.device)
+    out = torch.zeros(*v.shape[:-2], n, 128, dtype=v.dtype, device=v.device)
+    ok = keys < L
+    out[..., ok, :] = v[..., keys[ok], :]
+    return out.transpose(-1, -2)
+
+
+def vt_stream_deinterleave(vt, L, pos0, fp8=False):
+    """One stream's slots [pos0, pos0 + pad64(L)) of a V^T image [..., 128, ld] -> (v [..., L, 128] in key order, written [pad64(L)] bool:
+    the slots that hold a key that exists)."""
+    n = (L + 63) // 64 * 64
+    keys = vt8_slot_keys(n) if fp8 else vt_slot_keys(n)
+    written = keys < L
+    slot_of_key = torch.argsort(keys)[:L]                      # keys is a permutation of [0, n)
+    return vt[..., (pos0 + slot_of_key).to(vt.device)].transpose(-1, -2), written
+
+
+def mixed_plan_keep_rows(shapes, ncu):
+    """The peel of the GEMM planner's mixed plan (csrc/gemm.hip, lx_gemm_bf16_ws): shapes = [(M, N)] in launch order. 256-row tile rows come
+    off the ends of the problems, last problem first, until the rest fits whole rounds of ncu tiles; problem i keeps rows [0, keep[i]) on
+    256-row tiles and its rows from m_base = keep[i] on go to the 128-row tail. None when the planner has no such candidate."""
+    t256 = sum(-(-M // 256) * -(-N // 256) for M, N in shapes)
+    full = t256 // ncu * ncu
+    if full == 0 or t256 == full:
+        return None
+    remain, keep = t256, [M for M, _ in shapes]
+    for i in range(len(shapes) - 1, -1, -1):
+        tn = -(-shapes[i][1] // 256)
+        while remain > full and keep[i] > 0:
+            keep[i] -= keep[i] % 256 or 256
+            remain -= tn
+    return keep
+
+
+# launch shapes of tests/test_qkv_epilogue_tiles_gpu.py (H = 2 heads, D = 256): rows per batch element and column counts
+QKV_D = 256
+QKV_DOUBLE = dict(L=(416, 96, 160), B=(None, 9, 5), N=(768, 768, 512), M3=300, N3=264)      # p0's batch count follows from the CU count
+QKV_SINGLE = dict(L=160, N=3 * 256 + 520)
+
+
+def qkv_double_shapes(ncu):
+    """[(M, N)] of the double-block launch: NCU + tail tiles of 256 x 256, tail in [17, 24] and at most a sixth of a round (the three-way
+    split form's limit), p0 = B0 batch elements of 416 rows. None when no B0 gives such a launch."""
+    d = QKV_DOUBLE
+    rest = [(d["B"][i] * d["L"][i], d["N"][i]) for i in (1, 2)] + [(d["M3"], d["N3"])]
+    t_rest = sum(-(-M // 256) * -(-N // 256) for M, N in rest)
+    for B0 in range(1, 4096):
+        tail = 3 * -(-B0 * d["L"][0] // 256) + t_rest - ncu
+        if 17 <= tail <= 24 and tail * 6 <= ncu:
+            return [(B0 * d["L"][0], d["N"][0])] + rest
+        if tail > 24:
+            return None
+    return None
+
+
+def qkv_single_shape(ncu):
+    """[(M, N)] of the single-block launch: one [k | v | q | mlp] problem of 160-row batch elements, sized like qkv_double_shapes"""
+    d = QKV_SINGLE
+    tn = -(-d["N"] // 256)
+    for B in range(1, 4096):
+        tail = tn * -(-B * d["L"] // 256) - ncu
+        if 17 <= tail <= 24 and tail * 6 <= ncu:
+            return [(B * d["L"], d["N"])]
+        if tail > 24:
+            return None
+    return None
+
+
+def qkv_epilogue_emulate_f32(A, W, bias, wk, wq, cs, L, D=QKV_D):
+    """The whole epilogue in fp32 on the CPU, one operation at a time as the kernels write it (fp32 product sums, + bias, sum of squares,
+    rsqrt, x r w, the rotation): (k, v, q) fp32 [M, D] before the single rounding. A, W hold bf16-representable values."""
+    f = torch.float32
+    y = A.to(f) @ W.to(f).T + bias.to(f)
+    M = y.shape[0]
+    pos = torch.arange(M) % L
+    c, s = cs.to(f)[pos, 0::2][:, None, :], cs.to(f)[pos, 1::2][:, None, :]
+
+    def nr(x, w):
+        x = x.reshape(M, -1, 128)
+        r = torch.rsqrt((x * x).sum(-1, keepdim=True) * (1.0 / 128.0) + 1e-6)
+        x = (x * r * w.to(f)).view(M, -1, 64, 2)
+        e, o = x[..., 0], x[..., 1]
+        return torch.stack([e * c - o * s, o * c + e * s], -1).reshape(M, -1)
+    return nr(y[:, :D], wk), y[:, D:2 * D].contiguous(), nr(y[:, 2 * D:3 * D], wq)
