@@ -226,6 +226,15 @@ int lx_lora_down_f16(const void* X, int ldx, const void* Adown, float* T, int ld
  * (lora_nsplit = n_terms). Same arithmetic per slab as lx_lora_down(X[s], ldx[s], Adown[s], T + s * slab_stride, ..., n_split = 1). */
 int lx_lora_down_terms(const void* const* X, const int* ldx, const void* const* Adown, int n_terms, float* T, int ldt, int M, int K, int R,
                        int slab_stride, void* stream);
+/* Adapter weights on the down-projection scratch, one value per image and adapter column (DiTEngine.set_adapter_weights; the table
+ * also carries lora_scale): T_s[row, c] *= W[b, c % period] for every slab s < n_slab (slab_stride floats apart), c < R, and every row
+ * of every segment (1..3 token streams); b = ((row - row0) / rows_per_batch) % n_batches. T fp32 (ldt), W fp32 [n_batches, w_ld].
+ * period = the stacked rank of one module: the fused GEMMs keep their modules' columns side by side, all weighted alike. One IEEE
+ * fp32 multiply per element; rows outside the segments and columns >= R keep their bits. 1 <= R <= 16384, ldt >= R,
+ * w_ld >= min(period, R). 16-byte accesses when T is 16-byte aligned and ldt (and slab_stride, for n_slab > 1) are multiples of 4. */
+typedef struct lx_rowscale_seg { int32_t row0, n_rows, rows_per_batch, _pad; } lx_rowscale_seg;
+int lx_lora_scale_rows(float* T, int ldt, int R, int n_slab, int slab_stride, const lx_rowscale_seg* seg, int n_seg,
+                       const float* W, int w_ld, int n_batches, int period, void* stream);
 
 /* Skinny linear for a few rows (AdaLayerNorm modulation linears, time/text embedders:
  * block.py:192-207,301,305; transformer.py:102-114,243).  Weight-streaming, HBM bound; rows are processed four at a

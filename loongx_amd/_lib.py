@@ -74,6 +74,10 @@ class LnSeg(C.Structure):
                 ("shift", C.c_void_p), ("scale", C.c_void_p)]
 
 
+class RowScaleSeg(C.Structure):
+    _fields_ = [("row0", C.c_int32), ("n_rows", C.c_int32), ("rows_per_batch", C.c_int32), ("_pad", C.c_int32)]
+
+
 class QkvSeg(C.Structure):
     _fields_ = [("row0", C.c_int32), ("rows_per_batch", C.c_int32), ("vt_pos0", C.c_int32), ("_pad", C.c_int32),
                 ("wq", C.c_void_p), ("wk", C.c_void_p), ("cos_tab", C.c_void_p), ("sin_tab", C.c_void_p)]
@@ -93,6 +97,7 @@ _SIGS = {
     "lx_lora_down": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lx_lora_down_f16": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lx_lora_down_terms": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p), _I, _P, _I, _I, _I, _I, _I, _P]),
+    "lx_lora_scale_rows": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(RowScaleSeg), _I, _P, _I, _I, _I, _P]),
     "lx_linear_skinny": (C.c_int, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "lx_timestep_embed": (C.c_int, [_P, _P, _I, _I, _P]),
     "lx_rope_table": (C.c_int, [_P, _I, _I, _I, _I, C.c_double, _P, _P, _P]),

@@ -646,6 +646,47 @@ __global__ void convert_kernel(void* __restrict__ dst, int dst_bf16, const void*
   }
 }
 
+// ---- per-image adapter weights on the LoRA scratch: T_s[row, c] *= W[b, c % period] (lx_lora_scale_rows) ----------------------------
+// One IEEE fp32 multiply per element. A work item is VEC columns of one row of one slab (VEC = 4: 16-byte accesses, taken when T, ldt,
+// slab_stride allow it; a row's last chunk may be partial and goes by elements), items run slab-major over the segments' rows in launch
+// order; grid-stride loop under a capped grid. No LDS: nothing is shared between items.
+struct ScaleSegs {   // up to 3 row segments (token streams)
+  int n;
+  int row0[3], n_rows[3], rows_per_batch[3];
+};
+
+template <int VEC>
+__global__ __launch_bounds__(256) void lora_scale_rows_kernel(float* __restrict__ T, int ldt, int R, int n_slab, int slab_stride, ScaleSegs segs,
+                                                              int M, const float* __restrict__ W, int w_ld, int n_batches, int period) {
+  const int cpr = (R + VEC - 1) / VEC;                       // chunks per row
+  const size_t per_slab = (size_t)M * cpr, total = per_slab * n_slab;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int s = (int)(i / per_slab);
+    const size_t in_slab = i - (size_t)s * per_slab;
+    int rin = (int)(in_slab / cpr);
+    const int c = (int)(in_slab - (size_t)rin * cpr) * VEC;
+    int sg = 0;
+    while (sg < segs.n - 1 && rin >= segs.n_rows[sg]) { rin -= segs.n_rows[sg]; ++sg; }
+    const int b = (rin / segs.rows_per_batch[sg]) % n_batches;
+    float* t = T + (size_t)s * slab_stride + (size_t)(segs.row0[sg] + rin) * ldt + c;
+    const float* w = W + (size_t)b * w_ld;
+    if (VEC == 4 && c + 4 <= R) {
+      f32x4 v = *(const f32x4*)t;
+      int p = c % period;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = v[j] * w[p];
+        if (++p == period) p = 0;
+      }
+      *(f32x4*)t = v;
+    } else {
+      const int n = R - c < VEC ? R - c : VEC;
+      for (int j = 0; j < n; ++j) t[j] = t[j] * w[(c + j) % period];
+    }
+  }
+}
+
 }  // namespace
 
 // The five lx_ln_modulate* entry points. `name` is the one that was called: it reports the segment count and f16_ovf; everything else
@@ -882,6 +923,36 @@ extern "C" int lx_lora_down_terms(const void* const* X, const int* ldx, const vo
   }
   hipLaunchKernelGGL(lora_down_mfma_kernel<false>, dim3((M + 15) / 16, n_terms), dim3(512), 0, (hipStream_t)stream, lt, T, ldt, M, K, R, K, slab_stride);
   LX_LAUNCH_CHECK("lx_lora_down_terms");
+  return LX_OK;
+}
+
+extern "C" int lx_lora_scale_rows(float* T, int ldt, int R, int n_slab, int slab_stride, const lx_rowscale_seg* seg, int n_seg,
+                                  const float* W, int w_ld, int n_batches, int period, void* stream) {
+  LX_CHECK_ARG(T && W && seg, "lx_lora_scale_rows: NULL operand");
+  LX_CHECK_ARG(R >= 1 && R <= 16384, "lx_lora_scale_rows: R=%d must be in [1,16384]", R);
+  LX_CHECK_ARG(period >= 1 && n_batches >= 1 && n_slab >= 1, "lx_lora_scale_rows: period=%d, n_batches=%d and n_slab=%d must be >= 1", period,
+               n_batches, n_slab);
+  LX_CHECK_ARG(n_seg >= 1 && n_seg <= 3, "lx_lora_scale_rows: 1..3 segments");
+  LX_CHECK_ARG(w_ld >= (period < R ? period : R), "lx_lora_scale_rows: w_ld=%d must be >= min(period, R)", w_ld);
+  LX_CHECK_ARG(ldt >= R, "lx_lora_scale_rows: ldt=%d must be >= R=%d", ldt, R);
+  LX_CHECK_ARG(n_slab == 1 || slab_stride > 0, "lx_lora_scale_rows: bad slab_stride=%d", slab_stride);
+  LX_CHECK_ARG((((uintptr_t)T | (uintptr_t)W) & 3) == 0, "lx_lora_scale_rows: operands must be 4-byte aligned");
+  ScaleSegs segs = {};
+  segs.n = n_seg;
+  long long M = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    LX_CHECK_ARG(seg[i].row0 >= 0 && seg[i].n_rows > 0 && seg[i].rows_per_batch >= 1, "lx_lora_scale_rows: bad segment %d", i);
+    segs.row0[i] = seg[i].row0; segs.n_rows[i] = seg[i].n_rows; segs.rows_per_batch[i] = seg[i].rows_per_batch;
+    M += seg[i].n_rows;
+  }
+  LX_CHECK_ARG(M <= 0x7fffffffLL, "lx_lora_scale_rows: too many rows");
+  // 16-byte accesses where every chunk of every row of every slab starts on a 16-byte boundary; elements otherwise (ldt = 22)
+  const bool vec = ((uintptr_t)T & 15) == 0 && ldt % 4 == 0 && (n_slab == 1 || slab_stride % 4 == 0);
+  const size_t items = (size_t)M * (size_t)(vec ? (R + 3) / 4 : R) * (size_t)n_slab;
+  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  if (vec) hipLaunchKernelGGL(lora_scale_rows_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, T, ldt, R, n_slab, slab_stride, segs, (int)M, W, w_ld, n_batches, period);
+  else hipLaunchKernelGGL(lora_scale_rows_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, T, ldt, R, n_slab, slab_stride, segs, (int)M, W, w_ld, n_batches, period);
+  LX_LAUNCH_CHECK("lx_lora_scale_rows");
   return LX_OK;
 }
 

@@ -93,13 +93,20 @@ def broadcast_tensors(tensors: Dict[str, torch.Tensor], src: int = 0, bucket_byt
 
 def broadcast_packed_weights(pw, src: int = 0) -> int:
     """RCCL broadcast of a PackedWeights (flux/weights.py) from rank `src` to all ranks: every tensor the engine dereferences
-    (`pw.t`, and per adapter `down`, `up` and -- models packed for precise mode -- `down_lo`). The receiving ranks hold tensors of
+    (`pw.t`, and per adapter `down`, `up` and -- models packed for precise mode -- `down_lo`: the stacked image of the active adapters;
+    with more than one named adapter loaded, the registry's own tensors as well). The receiving ranks hold tensors of
     the same names and shapes (e.g. synthetic_weights(fill=False), or the same packing of an uninitialised state dict)."""
     flat = dict(pw.t)
     for k, lo in pw.lora.items():
         flat[f"{k}::lora_down"], flat[f"{k}::lora_up"] = lo.down, lo.up
         if lo.down_lo is not None:
             flat[f"{k}::lora_down_lo"] = lo.down_lo
+    # more than one named adapter loaded: the registry's own tensors too (every rank holds the same names and ranks), so a receiving rank
+    # can switch adapters -- set_active_adapters restacks from them. A single adapter shares its storage with the stacked image above.
+    if len(getattr(pw, "adapters", None) or {}) > 1:
+        for name, ad in pw.adapters.items():
+            for k, v in ad.tensors().items():
+                flat[f"adapter::{name}::{k}"] = v
     n = broadcast_tensors(flat, src)
     # everything an engine derived from the overwritten tensors is stale: the version moves UNCONDITIONALLY (the q_log2 table below exists
     # only when bounded-score attention has been set up; the fp16 weight images of DiTEngine._setup_f16 and the step graphs key on this)

@@ -134,6 +134,14 @@ class DiTEngine:
         # that do not depend on the batch size, i.e. data-parallel shards equal the single-GPU batch bit for bit.
         self.pair_plan = os.environ.get("LX_PAIR_PLAN", "1") != "0"
         self.lora_scale = 1.0            # lora_controller.enable_lora / set_lora_scale drive this (0 = adapters off everywhere)
+        # Per-adapter weights (set_adapter_weights): name -> float, or one float per image of the conditioning. set_conditioning turns them
+        # and lora_scale into `lora_w`, fp32 [B, cfg.lora_r]: the factor of every column of the stacked adapter's down-projection, which
+        # lx_lora_scale_rows applies to the adapter scratch (TLs / tmod) right after it is written. None = every factor is 1: no such
+        # launch anywhere. `lora_w_ns`: the same without lora_scale (the e4m3 down-projection takes lora_scale as its scalar argument).
+        self.adapter_weights: Dict[str, object] = {}
+        self.lora_w: Optional[torch.Tensor] = None
+        self.lora_w_ns: Optional[torch.Tensor] = None
+        self._lora_w_bufs: Dict = {}     # (B, R, which) -> the table's buffer: one address per shape, so step graphs can hold it
         # Precise mode (model_config["precise"], default `precise_default`): fp32-class arithmetic for the reference's shipped
         # fp32 configuration -- split-bf16 MFMA GEMMs (2 or 3 K-segments), fp32 q/k/v, fp32 attention (csrc/precise.hip).
         self.precise_default = False
@@ -155,6 +163,7 @@ class DiTEngine:
         self.w16: Dict[str, torch.Tensor] = {}         # name -> fp16 image of the (tiled) weight / name + ".down" -> fp16 LoRA down-projection
         self.w16_inexact_share, self.w16_clipped = 0.0, 0
         self._w16_key, self._w16_gen = None, 0
+        self._w16_wstat = (0, 0, 0)      # (values that lost bits, values clipped, values) of the weight images, without the adapters'
         self.f16_ovf: Optional[torch.Tensor] = None
         self._ovf_word, self._ovf_seen = HostWord(), 0         # f16_overflow_poll(sync=False)
         self._gemm_ws: Optional[torch.Tensor] = None
@@ -279,34 +288,44 @@ class DiTEngine:
         saturation counter, so the product's f16_overflow policy sees it. One host synchronisation per weight set."""
         if self.f16_ovf is None:
             self.f16_ovf = torch.zeros(1, dtype=torch.int32, device=self.device)
-        key = (id(self.w), getattr(self.w, "weights_version", 0), getattr(self.w, "lora_version", 0), len(self.w.lora))
+        # Only the adapter set moved (another active set, a new adapter: lora_version): the weight images stay where they are and only the
+        # adapters' `.down` images are rebuilt -- switching adapters from image to image must not re-convert 17 GB.
+        key = ((id(self.w), getattr(self.w, "weights_version", 0)), (getattr(self.w, "lora_version", 0), len(self.w.lora)))
         if self.w16 and self._w16_key == key:
             return
-        self.w16 = {}
+        full = not self.w16 or self._w16_key is None or self._w16_key[0] != key[0]
         self._w16_gen += 1                                         # part of the step graphs' key: they hold the images' addresses
-        stat = torch.zeros(2, dtype=torch.int64, device=self.device)      # [values that lost bits, values clipped]
-        total = 0
+        stat = torch.zeros(2, 2, dtype=torch.int64, device=self.device)      # weights, adapters: [values that lost bits, values clipped]
 
-        def image(W):
+        def image(W, st):
             h = W.float().clamp_(-65504.0, 65504.0).to(torch.float16)
             back = h.to(W.dtype)
-            stat[0] += (back != W).sum()
-            stat[1] += (W.float().abs() > 65504.0).sum()
+            st[0] += (back != W).sum()
+            st[1] += (W.float().abs() > 65504.0).sum()
             return h
 
-        for name, W in self.w.t.items():
-            if not name.endswith(".w") or name.startswith("mod.") or name.startswith("tte.") or W.dtype != torch.bfloat16:
-                continue
-            h = image(W)
-            if getattr(W, "lx_tiled", False):
-                h.lx_tiled = True                          # an elementwise conversion keeps the tiled image
-            total += W.numel()
-            self.w16[name[:-2]] = h
+        if full:
+            self.w16 = {}
+            total = 0
+            for name, W in self.w.t.items():
+                if not name.endswith(".w") or name.startswith("mod.") or name.startswith("tte.") or W.dtype != torch.bfloat16:
+                    continue
+                h = image(W, stat[0])
+                if getattr(W, "lx_tiled", False):
+                    h.lx_tiled = True                          # an elementwise conversion keeps the tiled image
+                total += W.numel()
+                self.w16[name[:-2]] = h
+        else:
+            for name in [n for n in self.w16 if n.endswith(".down")]:
+                del self.w16[name]
         for name, lo in self.w.lora.items():
-            self.w16[name + ".down"] = image(lo.down)
-        lost, clipped = (int(v) for v in stat.tolist())
-        self.w16_inexact_share = lost / max(total, 1)
-        self.w16_clipped = clipped
+            self.w16[name + ".down"] = image(lo.down, stat[1])
+        (w_lost, w_clipped), (a_lost, a_clipped) = ([int(v) for v in row] for row in stat.tolist())
+        if full:
+            self._w16_wstat = (w_lost, w_clipped, total)
+        w_lost, w_clipped, total = self._w16_wstat
+        self.w16_inexact_share = (w_lost + a_lost) / max(total, 1)
+        self.w16_clipped = w_clipped + a_clipped
         self._w16_key = key
 
     def f16_overflow_count(self, reset: bool = True) -> int:
@@ -348,9 +367,96 @@ class DiTEngine:
         s = float(s)
         if s != self.lora_scale:
             self.lora_scale = s
-            self.graphs = {}
-            self.cond_ready = False
-            self.sched = None
+            self._adapters_changed()
+
+    def _adapters_changed(self) -> None:
+        """What the adapter terms contribute has changed: the captured step graphs, the prepared schedule and the conditioning (with its
+        cached condition stream) go."""
+        self.graphs = {}
+        self.cond_ready = False
+        self.sched = None
+
+    def set_adapter_weights(self, weights: Optional[Dict]) -> None:
+        """{adapter name: w}: w a float, or one float per image of the conditioning (a sequence or 1-D tensor of length B, checked by
+        set_conditioning). Adapters not named weigh 1; engine.lora_scale multiplies on top. None / {}: every adapter at 1."""
+        new = self._checked_adapter_weights(weights)
+        if new != self.adapter_weights:
+            self.adapter_weights = new
+            self._adapters_changed()
+
+    def _checked_adapter_weights(self, weights: Optional[Dict]) -> Dict[str, object]:
+        """set_adapter_weights' argument as {name: float | tuple of floats}; ValueError for a name that is not loaded."""
+        from .weights import list_adapters
+        new = {}
+        for name, w in (weights or {}).items():
+            if isinstance(w, torch.Tensor):
+                w = w.detach().reshape(-1).tolist() if w.dim() else float(w)
+            new[str(name)] = tuple(float(v) for v in w) if isinstance(w, (list, tuple)) else float(w)
+        unknown = [n for n in new if n not in list_adapters(self.w)]
+        if unknown:
+            raise ValueError(f"unknown adapter{'s' if len(unknown) > 1 else ''} {', '.join(map(repr, unknown))}: loaded adapters are "
+                             f"{list_adapters(self.w)}")
+        return new
+
+    def set_adapters(self, names, weights: Optional[Dict] = None) -> None:
+        """Run with the loaded adapters `names` (weights.set_active_adapters: a name or a list, stacked in this order) at `weights`
+        (set_adapter_weights). A call that raises leaves the active set, the weights and the engine's state as they were."""
+        from .weights import active_adapters, set_active_adapters
+        names = [names] if isinstance(names, str) else list(names)
+        new = self._checked_adapter_weights(weights)
+        if names != active_adapters(self.w):
+            set_active_adapters(self.w, names)            # (atomic: raises before it changes anything)
+            self._adapters_changed()
+        if new != self.adapter_weights:
+            self.adapter_weights = new
+            self._adapters_changed()
+
+    def adapter_weights_key(self):
+        """What the adapter weights contribute to a conditioning's identity (tranformer_forward's cache key)."""
+        return tuple(sorted(self.adapter_weights.items()))
+
+    def _lora_tables(self, B: int) -> None:
+        """lora_w / lora_w_ns of a conditioning with B images (see __init__), in engine-owned buffers whose address depends on the
+        table's shape alone. Raises ValueError for a per-image weight whose length is not B."""
+        from .weights import _registry
+        self.lora_w = self.lora_w_ns = None
+        reg = _registry(self.w)
+        rows, ones = [[] for _ in range(B)], True
+        for name in self.w.active:
+            w = self.adapter_weights.get(name, 1.0)
+            if isinstance(w, tuple) and len(w) != B:
+                raise ValueError(f"adapter {name!r}: {len(w)} per-image weights for a batch of {B} images")
+            for b in range(B):
+                v = w[b] if isinstance(w, tuple) else w
+                ones = ones and v == 1.0
+                rows[b] += [v] * reg[name].rank
+        if not self.w.active or self.lora_scale == 0.0 or (ones and self.lora_scale == 1.0):
+            return
+        R = len(rows[0])
+        for which, s in (("w", self.lora_scale), ("ns", 1.0)):
+            if ones and s == 1.0:
+                continue
+            buf = self._lora_w_bufs.get((B, R, which))
+            if buf is None:
+                buf = self._lora_w_bufs[(B, R, which)] = torch.zeros(B, R, dtype=torch.float32, device=self.device)
+            buf.copy_(torch.tensor([[s * v for v in row] for row in rows], dtype=torch.float32))
+            setattr(self, "lora_w" if which == "w" else "lora_w_ns", buf)
+
+    def _scale_lora(self, T: torch.Tensor, segs, n_slab: int = 1, table: Optional[torch.Tensor] = None) -> None:
+        """The adapter weights on freshly written adapter scratch: T [rows, columns] (slab 0; n_slab slabs TLs.stride(0) apart), segs =
+        [(first row, rows, rows per image), ...] relative to T's first row. Nothing is launched while every factor is 1."""
+        table = self.lora_w if table is None else table
+        if table is not None:
+            assert table.shape[1] == self.cfg.lora_r and n_slab <= self.TLs.shape[0], (table.shape, self.cfg.lora_r, n_slab)
+            ops.lora_scale_rows(T, segs, table, self.cfg.lora_r, n_slab=n_slab, slab_stride=self.TLs.stride(0) if n_slab > 1 else 0)
+
+    def _embed_segs(self, rows: int):
+        """An embedder's input rows (B images x tokens, image-major) as the one lx_lora_scale_rows segment they are."""
+        return [(0, rows, max(rows // self.B, 1))]
+
+    def _lora_segs(self, r0: int, n: int):
+        """The token streams inside rows [r0, r0 + n) of the adapter scratch as lx_lora_scale_rows segments (rows relative to r0)."""
+        return [(s.row0 - r0, self.B * s.len, s.len) for s in self.streams if s.len > 0 and r0 <= s.row0 < r0 + n]
 
     def gemm_ws(self) -> Optional[torch.Tensor]:
         """The caller-owned GEMM workspace of lx_gemm_bf16_ws (what selects the default launch plans: lx_gemm4_kernel and its split form).
@@ -440,8 +546,7 @@ class DiTEngine:
             ops.linear_skinny(temb, w.t["mod.lora_down"], None, tm, act_in=1)
             if self.precise and "mod.lora_down_lo" in w.t:
                 ops.linear_skinny(temb, w.t["mod.lora_down_lo"], None, tm, act_in=1, accumulate=True)
-            if self.lora_scale != 1.0:
-                tm.mul_(self.lora_scale)
+            self._scale_lora(tm, [(0, rows, 1)])          # (rows of a whole schedule are step * B + sample: the table's rows wrap)
             for idx in range(nb):
                 if idx < cfg.num_layers:
                     base, width = cfg.mod_base_double(idx), 6 * D
@@ -628,6 +733,7 @@ class DiTEngine:
         C = 0 if condition_latents is None else condition_latents.shape[1]
         self.cond_mask, self.cond_ready = None, False
         refuse_wide_lora_modes(w, model_config, self.precise_default)
+        self._lora_tables(B)             # (a per-image adapter weight of another length than B: ValueError)
         mask = None
         if attention_mask is not None:
             mask_argument(attention_mask)
@@ -738,7 +844,7 @@ class DiTEngine:
         segs = self._ln_segs(base_by_stream, shift_off, scale_off)
         lora, ready = None, None
         lo = self.w.lora.get(lora_for) if lora_for is not None else None
-        if (lo is not None and self.ln_lora and self.lora_scale == 1.0 and lo.down.shape[0] <= 16
+        if (lo is not None and self.ln_lora and self.lora_scale == 1.0 and self.lora_w is None and lo.down.shape[0] <= 16
                 and self.cfg.inner_dim in (3072, 256) and self._lora_rows(include_txt) is not None):      # (the widths the kernel is built for)
             r0, n = self._lora_rows(include_txt)
             lora = (self._down(lora_for, lo), self.TL[r0:r0 + n, : lo.down.shape[0]], r0, n)       # slab 0 of TLs: the consumer sums one slab
@@ -772,8 +878,7 @@ class DiTEngine:
         r0, n = self._lora_rows(include_txt)
         t = self.TL[r0:r0 + n, : lo.down.shape[0]]
         ops.lora_down(self._op(A[r0:r0 + n]), self._down(name, lo), t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
-        if self.lora_scale != 1.0:
-            self.TLs[:, r0:r0 + n, : lo.down.shape[0]].mul_(self.lora_scale)
+        self._scale_lora(t, self._lora_segs(r0, n), n_slab=self.TL_SPLIT)
         return lo, self.TL_SPLIT, r0
 
     def _launch_streams(self, desc, workspace, main: str, txt: Optional[str], *, epilogue: int, w_rows: Optional[Dict[str, slice]] = None,
@@ -1046,6 +1151,8 @@ class DiTEngine:
         r0, n = self._lora_rows(include_txt)
         t = self.TL[r0:r0 + n, : lo.down.shape[0]]
         ops.lora_down_fp8(X8[r0:r0 + n], self.lora_scale / act_scale, lo.down, t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
+        if self.lora_w_ns is not None:                 # (lora_scale went in with the descale above: the table without it)
+            self._scale_lora(t, self._lora_segs(r0, n), n_slab=self.TL_SPLIT, table=self.lora_w_ns)
         return lo, self.TL_SPLIT, r0
 
     def _ln8(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
@@ -1104,9 +1211,10 @@ class DiTEngine:
         W = self._w_rows(w2 if w2 is not None else self.w.t[name + ".w"], w_rows)
         return ops.gemm_desc(A2, W, Cbuf, K=K, N=W.shape[0], k_segs=3 if w2 is not None else 2, a_lo_off=a_lo_off, **kw)
 
-    def _lora_t_p(self, A2: torch.Tensor, name: str, K: int, a_lo_off: int, r0: int, n: int):
+    def _lora_t_p(self, A2: torch.Tensor, name: str, K: int, a_lo_off: int, r0: int, n: int, segs=None):
         """t = x A_down^T for rows [r0, r0+n) with x = hi + lo: one slab per cross term (the consumer GEMM adds them).
-        Returns the `lora` of the launch that consumes them (NO_LORA: no adapter on this Linear)."""
+        Returns the `lora` of the launch that consumes them (NO_LORA: no adapter on this Linear). segs: how the rows map to images where
+        they are not the token streams' (_lora_segs)."""
         lo = self.w.lora.get(name)
         if lo is None or self.lora_scale == 0.0:
             return self.NO_LORA
@@ -1116,8 +1224,7 @@ class DiTEngine:
             terms.append((A2[r0:r0 + n, :K], lo.down_lo))
         # one launch for the cross terms (slab s = term s; the consumer GEMM adds the slabs)
         ops.lora_down_terms(terms, self.TLs[0, r0:r0 + n, :R], self.TLs.stride(0))
-        if self.lora_scale != 1.0:
-            self.TLs[: len(terms), r0:r0 + n, :R].mul_(self.lora_scale)
+        self._scale_lora(self.TLs[0, r0:r0 + n, :R], self._lora_segs(r0, n) if segs is None else segs, n_slab=len(terms))
         return lo, len(terms), r0
 
     def _embed_p(self, x32: torch.Tensor, name: str, out: torch.Tensor, lora: bool, pair: Optional[torch.Tensor] = None) -> None:
@@ -1129,7 +1236,7 @@ class DiTEngine:
         ops.split_bf16(x32, pair, K)
         kw = {}
         if lora:
-            lo, ns, _ = self._lora_t_p(pair, name, K, K, 0, rows) if rows <= self.TLs.shape[1] else self.NO_LORA
+            lo, ns, _ = self._lora_t_p(pair, name, K, K, 0, rows, segs=self._embed_segs(rows)) if rows <= self.TLs.shape[1] else self.NO_LORA
             if lo is not None:
                 kw = dict(lora_t=self.TL[:rows], lora_up=lo.up, lora_nsplit=ns, lora_split_stride=self.TLs.stride(0))
         ops.gemm([self._desc_p(pair, name, out, K=K, a_lo_off=K, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, **kw)], self.gemm_ws())
@@ -1143,8 +1250,7 @@ class DiTEngine:
         if lo is not None:
             tl = self.TL[: x.shape[0], : self.cfg.lora_r]
             ops.lora_down(x, self._down(name, lo), tl)
-            if self.lora_scale != 1.0:
-                tl.mul_(self.lora_scale)
+            self._scale_lora(tl, self._embed_segs(x.shape[0]))
         ops.gemm([ops.gemm_desc(x, self._W(name), out, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, lora_t=tl,
                                 lora_up=lo.up if lo is not None else None, **self._f16_kw())])
 
@@ -1341,12 +1447,15 @@ class DiTEngine:
                getattr(self.w, "q_log2_version", 0),      # (a weight broadcast refreshes the scaled norm_q tensors and the per-layer bounds)
                getattr(self.w, "weights_version", 0),     # (... and moves this one unconditionally: dist.broadcast_packed_weights)
                self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, self._w16_gen if self.f16 else 0,
+               # the adapter set (its tensors' addresses are in the launches) and whether the adapter-weight tables exist (their launches)
+               getattr(self.w, "lora_version", 0), tuple(None if t is None else t.data_ptr() for t in (self.lora_w, self.lora_w_ns)),
                # the masked launches hold the workspace's address and the mask's tile geometry (dtype, broadcast dims), never the mask itself:
                # a new mask of the same form is a new prep into the same workspace (set_conditioning), which the same graph then reads
                None if self.cond_mask is None else (self._mask_ws.data_ptr(), self.cond_mask.dtype, tuple(self.cond_mask.shape[:3])))
         g = self.graphs.get(key)
         if g is None:
             mode = (self.precise, self.gemm_fp8, self.f16, bool(self.model_config.get("attn_fp8", False)), self.latent_lora, self.C > 0, skip,
+                    self.lora_w is not None or self.lora_w_ns is not None,
                     None if self.cond_mask is None else self.cond_mask.dtype == torch.bool)      # (the bit and the bias form of the masked kernel)
             self.cond_skip = skip
             try:
@@ -1417,13 +1526,13 @@ class DiTEngine:
             if lora and "mod.lora_down" in w.t and self.lora_scale != 0.0:
                 tm = self.tmod[:, :r]
                 ops.linear_skinny(vec, w.t["mod.lora_down"][li * r:(li + 1) * r], None, tm, act_in=1)
-                if self.lora_scale != 1.0:
-                    tm.mul_(self.lora_scale)
+                self._scale_lora(tm, [(0, self.B, 1)])
                 ops.linear_f32(tm, w.t[f"mod.lora_up.{li}"], None, out[:, base:], M=self.B, N=lw, K=r, ldx=tm.stride(0),
                                ldy=out.stride(0), accumulate=True)
 
     def configure(self, B, T, N, C, model_config=None, c_factor=None, rope_main=None, rope_cond=None) -> None:
         """Shape + config + RoPE tables without the prompt/condition embedders (block-level use)."""
+        self._lora_tables(B)
         self.setup(B, T, N, C)
         self.gemm_ws()
         self.graphs = {}

@@ -74,6 +74,24 @@ def _signal(x, device, dtype, fixed_len, model):
     return model.spatial_pyramid_pooling(x.to(device).to(dtype), fixed_len)
 
 
+_UNNAMED_ADAPTER_WARNED = False
+
+
+def _select_adapter(pipeline, name: str) -> None:
+    """generate(default_lora=False): run with the adapter named after the condition type (generate.py:279). One compatibility rule: a
+    pipeline whose only adapter is the unnamed "default" (packed with the checkpoint, or loaded without an adapter_name) keeps it,
+    with one RuntimeWarning per process; any other unknown name is set_adapters' ValueError."""
+    global _UNNAMED_ADAPTER_WARNED
+    loaded = pipeline.get_list_adapters()["transformer"]
+    if name not in loaded and loaded == ["default"]:
+        if not _UNNAMED_ADAPTER_WARNED:
+            _UNNAMED_ADAPTER_WARNED = True
+            warnings.warn(f'generate(default_lora=False): no adapter named {name!r} is loaded; keeping the only adapter, the unnamed '
+                          '"default" (load it with adapter_name=... to select by condition type)', RuntimeWarning, stacklevel=3)
+        return
+    pipeline.set_adapters(name)
+
+
 @torch.no_grad()
 def generate(model, pipeline, conditions: List[Condition] = None, config_path: str = None,
              model_config: Optional[Dict[str, Any]] = {}, condition_scale: float = 1.0, default_lora: bool = False,
@@ -154,7 +172,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     if use_condition:
         assert len(conditions) <= 1, "Only one condition is supported for now."
         if not default_lora:
-            pipeline.set_adapters(conditions[0].condition_type)
+            _select_adapter(pipeline, conditions[0].condition_type)
         for condition in conditions:
             tokens, ids, type_id = condition.encode(self)
             condition_latents.append(tokens)

@@ -166,10 +166,13 @@ class LxFluxPipeline:
             text = FluxTextEncoders.from_pretrained(path, device, dtype)
         return cls(tr, vae=vae, text_encoder=text)
 
-    def load_lora_weights(self, path: str, weight_name: str = "pytorch_lora_weights.safetensors", lora_scale: float = 1.0, **kwargs):
+    def load_lora_weights(self, path: str, weight_name: str = "pytorch_lora_weights.safetensors", lora_scale: float = 1.0,
+                          adapter_name: Optional[str] = None, **kwargs):
         """diffusers `FluxPipeline.load_lora_weights` for the transformer (model.py:472): `path` is the directory the
-        reference saves with `save_lora` (model.py:526-531) or the .safetensors file itself. Replaces the adapters of the
-        packed model in place and drops every cached graph / conditioning that baked the old ones in."""
+        reference saves with `save_lora` (model.py:526-531) or the .safetensors file itself. Without `adapter_name` it replaces the
+        adapters of the packed model in place (one adapter, "default", active). With a name it adds or replaces that adapter and leaves
+        the others -- and a non-empty active set -- as they are: set_adapters selects. Either way every cached graph / conditioning
+        that baked the old ones in is dropped."""
         import os
         from .weights import install_lora
         f = os.path.join(path, weight_name) if os.path.isdir(path) else path
@@ -181,14 +184,54 @@ class LxFluxPipeline:
         else:
             sd = torch.load(f, map_location="cpu")
         eng = self.transformer.engine
-        n = install_lora(eng.w, sd, lora_scale=lora_scale)
+        n = install_lora(eng.w, sd, lora_scale=lora_scale, adapter_name=adapter_name)
+        if adapter_name is None:
+            eng.adapter_weights = {}
+        self._adapters_changed()
+        return n
+
+    def _adapters_changed(self) -> None:
+        eng = self.transformer.engine
         eng.graphs = {}
         eng.shape = None               # the adapter rank sizes the modulation scratch: re-run setup()
         self.transformer.invalidate_conditioning()
-        return n
 
-    def set_adapters(self, *a, **k):
-        """Adapters are baked into the packed weights (one LoRA per checkpoint, inference.py:114 default_lora=True)."""
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """diffusers `set_adapters`: run with the loaded adapters `adapter_names` (a name or a list; stacked in this order) at
+        `adapter_weights`: a float for all of them, or one item per name, each a float or a sequence / tensor with one value per image
+        of the batch (checked against the batch when the next image is conditioned). Default 1. engine.lora_scale (lora_controller)
+        multiplies on top. An unknown name is a ValueError that lists the loaded ones and changes nothing."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None:
+            weights = {}
+        elif isinstance(adapter_weights, (list, tuple)):
+            if len(adapter_weights) != len(names):
+                raise ValueError(f"{len(adapter_weights)} adapter weights for {len(names)} adapters")
+            weights = dict(zip(names, adapter_weights))
+        else:
+            weights = {n: adapter_weights for n in names}
+        eng = self.transformer.engine
+        before = (eng.w.lora_version, eng.adapter_weights_key())
+        eng.set_adapters(names, weights)
+        if (eng.w.lora_version, eng.adapter_weights_key()) != before:       # (selecting what is selected keeps the step graphs)
+            self._adapters_changed()
+
+    def get_active_adapters(self):
+        from .weights import active_adapters
+        return active_adapters(self.transformer.engine.w)
+
+    def get_list_adapters(self):
+        """diffusers returns {component: [names]}; the transformer is the one component that carries adapters here."""
+        from .weights import list_adapters
+        return {"transformer": list_adapters(self.transformer.engine.w)}
+
+    def delete_adapters(self, adapter_names):
+        from .weights import delete_adapters
+        eng = self.transformer.engine
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        delete_adapters(eng.w, names)
+        eng.adapter_weights = {k: v for k, v in eng.adapter_weights.items() if k not in names}
+        self._adapters_changed()
 
     def maybe_free_model_hooks(self):
         pass

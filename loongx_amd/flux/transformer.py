@@ -148,7 +148,8 @@ def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.
            _tkey(condition_latents), _tkey(condition_ids), float(c_t), tuple(sorted(mc.items())), transformer.c_factor,
            hidden_states.shape[0], getattr(eng.w, "weights_version", 0), getattr(eng.w, "lora_version", 0),      # (a weight broadcast or a new
            # adapter after the conditioning: the cached embedder outputs and modulations were computed from the old weights)
-           _mkey(attention_mask))           # (the mask is prepared once per conditioning: a changed mask must never meet a stale prep)
+           _mkey(attention_mask),           # (the mask is prepared once per conditioning: a changed mask must never meet a stale prep)
+           eng.adapter_weights_key())       # (the adapter weights are in the condition stream's cached rows and modulations)
     if key != transformer._cond_key or not eng.cond_ready:
         transformer._cond_key = transformer._cond_refs = None          # (a conditioning that raises leaves none behind)
         eng.set_conditioning(encoder_hidden_states, pooled_projections, guidance, txt_ids, img_ids,

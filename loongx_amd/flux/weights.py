@@ -99,6 +99,25 @@ class Lora:
         self.down, self.up, self.down_lo = down, up, down_lo
 
 
+class Adapter:
+    """One named adapter of the registry (PackedWeights.adapters): `lora` = fused GEMM name -> Lora of this adapter alone (down rows
+    stacked per fused module, up already times alpha / r and lora_scale), `t` = its "mod.lora_down"[, "mod.lora_down_lo"] rows and
+    "mod.lora_up.<idx>" columns, `rank` = its one rank. Plain containers, no tensor attributes: what an engine dereferences is the stacked
+    image of the active set in PackedWeights.lora / .t, which shares this storage while exactly one adapter is active."""
+    __slots__ = ("rank", "lora", "t")
+
+    def __init__(self, rank: int, lora: Dict[str, "Lora"], t: Dict[str, torch.Tensor]):
+        self.rank, self.lora, self.t = rank, lora, t
+
+    def tensors(self) -> Dict[str, torch.Tensor]:
+        out = dict(self.t)
+        for k, lo in self.lora.items():
+            out[k + "::down"], out[k + "::up"] = lo.down, lo.up
+            if lo.down_lo is not None:
+                out[k + "::down_lo"] = lo.down_lo
+        return out
+
+
 def _hi_lo(w32: torch.Tensor):
     """fp32 -> (bf16 hi, bf16 lo or None): w = hi + lo to 16 mantissa bits; lo is None when w is bf16-representable."""
     hi = w32.to(torch.bfloat16)
@@ -116,7 +135,12 @@ class PackedWeights:
     t: Dict[str, torch.Tensor] = field(default_factory=dict)     # name -> tensor
     lora: Dict[str, Lora] = field(default_factory=dict)          # name -> Lora (absent => no adapter)
     precise_ready: bool = False                                   # every weight is bf16-exact or carries its residual
-    lora_version: int = 0                                         # bumped by install_lora
+    lora_version: int = 0                                         # bumped whenever the stacked adapter image (lora, t["mod.lora_*"]) changes
+    # Named adapters (install_lora(adapter_name=...), set_active_adapters). `lora` and t["mod.lora_*"] above are the STACKED image of
+    # the active ones, in `active` order: per module the down rows [a1 | a2 | ...] and the up columns likewise, cfg.lora_r the sum of
+    # their ranks. None until a name is first used; a model packed or installed the old way is adopted as "default" (_registry).
+    adapters: Optional[Dict[str, Adapter]] = None
+    active: List[str] = field(default_factory=list)
 
     def nbytes(self) -> int:
         n = sum(v.numel() * v.element_size() for v in self.t.values())
@@ -133,8 +157,15 @@ def _check_lora_ranks(cfg: FluxConfig, ranks: Dict[str, int], group_sizes: Dict[
     proj_mlp, from one slab, so r <= 4 there), or an even r <= 64 (the wide down-projection and the 8-wave GEMMs' rank walk, bf16 and
     fp16 operand modes only: refused for weights packed for precise mode here, and by set_conditioning under gemm_fp8).
     Sets cfg.lora_r, which sizes the engine's adapter scratch."""
+    r = _one_lora_rank(ranks, group_sizes, precise)
+    if r is not None:
+        cfg.lora_r = r
+
+
+def _one_lora_rank(ranks: Dict[str, int], group_sizes: Dict[str, int], precise: bool = False) -> Optional[int]:
+    """_check_lora_ranks without the side effect: the one rank of `ranks` (None: no adapter), or the ValueError."""
     if not ranks:
-        return
+        return None
     rs = sorted(set(ranks.values()))
     if len(rs) != 1:
         bad = {k: v for k, v in ranks.items() if v != rs[0]}
@@ -148,7 +179,7 @@ def _check_lora_ranks(cfg: FluxConfig, ranks: Dict[str, int], group_sizes: Dict[
         if r > LORA_MAX_RANK or r % 2:
             raise ValueError(f"LoRA rank {r} is not supported: the fused GEMM '{name}' evaluates {n} adapters, which takes "
                              f"r <= {16 // n} or an even r <= {LORA_MAX_RANK}")
-    cfg.lora_r = r
+    return r
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -296,12 +327,16 @@ def lora_layout(cfg: FluxConfig):
     return fused, mods
 
 
-def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale: float = 1.0, prefix: str = "transformer.") -> int:
-    """Install (replace) the LoRA adapters of an already packed model from a LoRA-only state dict -- the content of the
+def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale: float = 1.0, prefix: str = "transformer.",
+                 adapter_name: Optional[str] = None) -> int:
+    """Install the LoRA adapters of an already packed model from a LoRA-only state dict -- the content of the
     `pytorch_lora_weights.safetensors` the reference loads through `flux_pipe.load_lora_weights` (model.py:463-477):
     keys `[transformer.]<module>.lora_A[.<adapter>].weight` / `lora_B...`, optional `<module>.alpha` (then the up matrix is
     scaled by alpha / r, as diffusers / peft do). Returns the number of adapted Linear modules. Adapters that the fused GEMMs
-    evaluate together (q/k/v[/proj_mlp] of one block) must be given for all of them or none."""
+    evaluate together (q/k/v[/proj_mlp] of one block) must be given for all of them or none.
+    adapter_name = None: replace every adapter by this one, named "default" and active. With a name: add (or replace) that entry of the
+    registry and leave the others alone; it becomes active only if nothing was (set_active_adapters selects). One rank per adapter;
+    different adapters may differ. A call that raises leaves the model as it was."""
     sd = {}
     for k, v in lora_sd.items():
         if prefix and k.startswith(prefix):
@@ -359,14 +394,128 @@ def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale
         raise KeyError(f"LoRA keys that match no module of this transformer: {unknown[:4]}{' ...' if len(unknown) > 4 else ''}")
     if n == 0:
         raise ValueError("no LoRA adapter found in the state dict")
-    _check_lora_ranks(pw.cfg, ranks, groups, precise=pw.precise_ready)
+    ad = Adapter(_one_lora_rank(ranks, groups, precise=pw.precise_ready), new_lora, new_t)
+    if adapter_name is None:
+        _commit_adapters(pw, {"default": ad}, ["default"])
+        return n
+    adapters = dict(_registry(pw))
+    adapters[adapter_name] = ad
+    active = list(pw.active) if pw.active else [adapter_name]
+    if adapter_name in active:
+        _commit_adapters(pw, adapters, active)       # (restacks: the new entry is part of the image the engine reads)
+    else:
+        pw.adapters = adapters
+    return n
+
+
+def _registry(pw: PackedWeights) -> Dict[str, Adapter]:
+    """The registry, created on first use: a model that was only ever packed (pack_state_dict, synthetic_weights) or installed without a
+    name adopts its adapter as "default", active, sharing storage with pw.lora / pw.t."""
+    if pw.adapters is None:
+        pw.adapters, pw.active = {}, []
+        mod = {k: v for k, v in pw.t.items() if k.startswith("mod.lora_")}
+        if pw.lora or mod:
+            pw.adapters["default"] = Adapter(pw.cfg.lora_r, dict(pw.lora), mod)
+            pw.active = ["default"]
+    return pw.adapters
+
+
+def _stack_adapters(pw: PackedWeights, adapters: Dict[str, Adapter], names: List[str]):
+    """(lora, mod tensors, stacked rank) of the active set `names`: per module the down rows [a1 rows | a2 rows | ...] and the up columns
+    likewise; an adapter without a module another one covers contributes zero rows and columns there. One adapter: its own tensors.
+    Raises the rank limits' ValueError (_check_lora_ranks' rules on the stacked rank), naming the adapters and the total."""
+    ads = [adapters[n] for n in names]
+    if not ads:
+        return {}, {}, None
+    R = sum(a.rank for a in ads)
+    fused, mods = lora_layout(pw.cfg)
+    groups = {f: len(m) for f, m in fused if any(f in a.lora for a in ads)}
+    ranks = {m: R for f, ms in fused if f in groups for m in ms}
+    try:
+        _one_lora_rank(ranks or {"mod": R}, groups, precise=pw.precise_ready)
+    except ValueError as e:
+        if len(ads) == 1:
+            raise
+        raise ValueError(f"adapters {', '.join(f'{n!r} (rank {a.rank})' for n, a in zip(names, ads))} stack to rank {R}: {e}") from None
+    if len(ads) == 1:
+        return dict(ads[0].lora), dict(ads[0].t), R
+
+    def rows(parts, j, like):          # module / block j's rows of every adapter, zeros where an adapter has none
+        return torch.cat([p[j * a.rank:(j + 1) * a.rank] if p is not None else like.new_zeros(a.rank, like.shape[1]) for p, a in zip(parts, ads)], 0)
+
+    def cols(parts, like):
+        return torch.cat([p if p is not None else like.new_zeros(like.shape[0], a.rank) for p, a in zip(parts, ads)], 1).contiguous()
+
+    lora, t = {}, {}
+    for f, n_mod in groups.items():
+        los = [a.lora.get(f) for a in ads]
+        one = next(lo for lo in los if lo is not None)
+        down = torch.cat([rows([lo.down if lo is not None else None for lo in los], j, one.down) for j in range(n_mod)], 0).contiguous()
+        down_lo = None
+        if any(lo is not None and lo.down_lo is not None for lo in los):
+            down_lo = torch.cat([rows([lo.down_lo if lo is not None else None for lo in los], j, one.down) for j in range(n_mod)], 0).contiguous()
+        lora[f] = Lora(down, cols([lo.up if lo is not None else None for lo in los], one.up), down_lo)
+    for key in ("mod.lora_down", "mod.lora_down_lo"):
+        parts = [a.t.get(key) for a in ads]
+        if any(p is not None for p in parts):
+            one = next(p for p in parts if p is not None)
+            t[key] = torch.cat([rows(parts, idx, one) for idx in range(len(mods))], 0).contiguous()
+    if "mod.lora_down" in t:
+        for idx in range(len(mods)):
+            parts = [a.t.get(f"mod.lora_up.{idx}") for a in ads]
+            t[f"mod.lora_up.{idx}"] = cols(parts, next(p for p in parts if p is not None))
+    return lora, t, R
+
+
+def _commit_adapters(pw: PackedWeights, adapters: Dict[str, Adapter], active: List[str]) -> None:
+    """Make `adapters` the registry and the stack of `active` the image the engines read. Everything that can raise happens first."""
+    lora, t, R = _stack_adapters(pw, adapters, active)
+    pw.adapters, pw.active = adapters, list(active)
     pw.lora.clear()
-    pw.lora.update(new_lora)
+    pw.lora.update(lora)
     for k in [k for k in pw.t if k.startswith("mod.lora_")]:
         del pw.t[k]
-    pw.t.update(new_t)
+    pw.t.update(t)
+    if R is not None:
+        pw.cfg.lora_r = R
     pw.lora_version += 1                 # engines rebuild what they derived from the adapters (the fp16 images: DiTEngine._setup_f16)
-    return n
+
+
+def set_active_adapters(pw: PackedWeights, names) -> None:
+    """Select the adapters the model runs with, in this order (a name or a list of loaded names). Restacks pw.lora / pw.t["mod.lora_*"],
+    sets cfg.lora_r to the sum of their ranks and moves lora_version. The stacked rank obeys the limits of one adapter's rank
+    (_check_lora_ranks). Atomic: an unknown name or a refused rank leaves the active set and the stacked tensors as they were."""
+    names = [names] if isinstance(names, str) else list(names)
+    reg = _registry(pw)
+    unknown = [n for n in names if n not in reg]
+    if unknown:
+        raise ValueError(f"unknown adapter{'s' if len(unknown) > 1 else ''} {', '.join(map(repr, unknown))}: loaded adapters are {list(reg)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"adapter named twice in {names}")
+    _commit_adapters(pw, reg, names)
+
+
+def delete_adapters(pw: PackedWeights, names) -> None:
+    """Drop adapters from the registry; active ones leave the active set (and the stacked image) too."""
+    names = [names] if isinstance(names, str) else list(names)
+    reg = _registry(pw)
+    unknown = [n for n in names if n not in reg]
+    if unknown:
+        raise ValueError(f"unknown adapter{'s' if len(unknown) > 1 else ''} {', '.join(map(repr, unknown))}: loaded adapters are {list(reg)}")
+    left = {k: v for k, v in reg.items() if k not in names}
+    if any(n in pw.active for n in names):
+        _commit_adapters(pw, left, [n for n in pw.active if n not in names])
+    else:
+        pw.adapters = left
+
+
+def list_adapters(pw: PackedWeights) -> List[str]:
+    return list(_registry(pw))
+
+
+def active_adapters(pw: PackedWeights) -> List[str]:
+    _registry(pw)
+    return list(pw.active)
 
 
 @torch.no_grad()

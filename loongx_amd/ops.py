@@ -252,6 +252,21 @@ def lora_down_terms(terms, T: torch.Tensor, slab_stride: int) -> None:
     check(lib.lx_lora_down_terms(xs, ls, as_, n, T.data_ptr(), T.stride(0), M, K, R, slab_stride, _stream()), "lx_lora_down_terms")
 
 
+def lora_scale_rows(T: torch.Tensor, segs, W: torch.Tensor, period: int, n_slab: int = 1, slab_stride: int = 0) -> None:
+    """T[row, c] *= W[b, c % period] on every slab of the adapter scratch (slab 0 = T [rows, R] fp32, row stride T.stride(0); slab s lives
+    slab_stride floats further), for the rows of segs = [(row0, n_rows, rows_per_batch), ...] (<= 3), b = ((row - row0) // rows_per_batch)
+    % W.shape[0]. W fp32 [n_batches, >= min(period, R)]: the engine's per-image adapter-weight table. One launch."""
+    _req(T, torch.float32, "T"); _req(W, torch.float32, "W")
+    assert T.dim() == 2 and W.dim() == 2 and T.stride(1) == 1 and W.stride(1) == 1
+    arr = (L.RowScaleSeg * max(len(segs), 1))()
+    for i, (row0, n_rows, rpb) in enumerate(segs):
+        arr[i].row0, arr[i].n_rows, arr[i].rows_per_batch = row0, n_rows, rpb
+    R, rows = T.shape[1], sum(s[1] for s in segs)
+    _timed("lora_scale", lambda: (float(rows * R * n_slab), 8.0 * rows * R * n_slab),
+           lambda: check(lib.lx_lora_scale_rows(T.data_ptr(), T.stride(0), R, n_slab, slab_stride, arr, len(segs), W.data_ptr(), W.stride(0),
+                                                W.shape[0], period, _stream()), "lx_lora_scale_rows"))
+
+
 def linear_skinny(X, W, bias, Y, act_in=0, act_out=0, accumulate=False) -> None:
     _req(X, torch.float32, "X"); _req(W, torch.bfloat16, "W"); _req(Y, torch.float32, "Y")
     check(lib.lx_linear_skinny(X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), _p(bias), Y.data_ptr(), Y.stride(0),

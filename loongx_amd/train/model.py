@@ -506,9 +506,10 @@ class OminiModel(CS3DGF):
                                          operands="fp16" if dtype == torch.float16 else "bf16")
         return cls.from_pipe(LxFluxPipeline(tr), synthetic_cs3_state_dict(seed), model_config, device, dtype=dtype)
 
-    def load_lora(self, checkpoint_path: str):
-        """model.py:463-477: load LoRA weights from a checkpoint directory into the pipeline's transformer."""
-        self.flux_pipe.load_lora_weights(checkpoint_path, lora_scale=self.lora_scale)
+    def load_lora(self, checkpoint_path: str, adapter_name: Optional[str] = None):
+        """model.py:463-477: load LoRA weights from a checkpoint directory into the pipeline's transformer (adapter_name: as a named
+        adapter beside the loaded ones, LxFluxPipeline.load_lora_weights)."""
+        self.flux_pipe.load_lora_weights(checkpoint_path, lora_scale=self.lora_scale, adapter_name=adapter_name)
         return self
 
     @property
