@@ -105,7 +105,7 @@ class DiTEngine:
         if self.cfg.attention_head_dim != 128:
             raise ValueError("the gfx950 attention kernel is specialised for head_dim 128 (FLUX.1)")
         self.shape = None
-        self.cond_ready = False
+        self.cond_ready = False          # set_conditioning() completed and nothing has replaced what it set up since (configure() unsets it)
         self.sched = None
         self.graphs: Dict = {}
         self._warmed = set()             # kernel sets (modes) that have run eagerly once: first launches must not happen inside a capture
@@ -152,6 +152,7 @@ class DiTEngine:
         # fp8 GEMM path (model_config["gemm_fp8"]; BASELINE configs[4]): e4m3 operand images on the 64-deep f8f6f4 MFMA
         self.gemm_fp8 = False
         self.w8: Dict[str, torch.Tensor] = {}          # name -> tiled e4m3 weight / name + ".rs" -> row de-scale, built on first use
+        self._w8_key = None                            # (weights, weights_version) the images were quantised from
         # fp16 operand mode (model_config["operands"] = "fp16", default `operands_default`; OminiModel(dtype=torch.float16)): every GEMM of
         # the forward multiplies IEEE fp16 images (11 significand bits) instead of bf16 ones (8) on v_mfma_f32_*_f16, same rate, same
         # layouts; fp32 accumulation, residual stream and everything between the GEMMs as in the bf16 mode; attention operands (q, k, V^T)
@@ -1104,14 +1105,20 @@ class DiTEngine:
 
     def _setup_fp8(self) -> None:
         """XN8 u8 [M, D]: e4m3(XN * S_X8);  Y8 u8 [M, 5D] = [attn | mlp]: e4m3(attention output | MLP hidden, * S_Y8) -- again ONE
-        contiguous K = 5D operand for the single block's proj_out. Block weights are quantised once (per-output-row scale) from
+        contiguous K = 5D operand for the single block's proj_out. Block weights are quantised once per weight set (per-output-row scale) from
         the packed bf16 weights and kept as tiled e4m3 images (+11.9 GB)."""
         if self.XN8 is None:
             D = self.cfg.inner_dim
             self.XN8 = torch.zeros(self.M, D, dtype=torch.uint8, device=self.device)
             self.Y8 = torch.zeros(self.M, 5 * D, dtype=torch.uint8, device=self.device)
-        if self.w8:
+        # (the images are quantised from the packed weights: a weight set overwritten in place -- dist.broadcast_packed_weights, which
+        # moves weights_version -- gets new ones, like the fp16 images of _setup_f16; the graphs that hold the old ones' addresses go)
+        key = (id(self.w), getattr(self.w, "weights_version", 0))
+        if self.w8 and self._w8_key == key:
             return
+        if self.w8:
+            self.w8, self.graphs = {}, {}
+        self._w8_key = key
         names = []
         for i in range(self.cfg.num_layers):
             names += [f"d{i}.{n}" for n in ("qkv", "qkv_txt", "out", "out_txt", "ff1", "ff1_txt", "ff2", "ff2_txt")]
@@ -1551,7 +1558,11 @@ class DiTEngine:
         else:
             self.cos_cond = self.sin_cond = None
         self._rope_pairs(check=True)
-        self.cond_ready = True
+        # A block-level configuration is NOT a conditioning: it replaced model_config, c_factor, the attention bias and the RoPE tables of
+        # whatever set_conditioning() left, and block_mods() overwrites slices of mods / cmods. forward() and prepare_schedule() must not
+        # run on that, and tranformer_forward -- whose key of conditioning tensors cannot see a block-level call on the same engine in
+        # between -- conditions again when it finds cond_ready unset. (The block-level entry points themselves never look at it.)
+        self.cond_ready = False
 
     def attention_module(self, kind: str, idx: int, project_out: bool) -> None:
         """attn_forward (block.py:7-176) on the normalised activations already in XN: QKV projections, QK-RMSNorm,

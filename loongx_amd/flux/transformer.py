@@ -150,6 +150,9 @@ def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.
            # adapter after the conditioning: the cached embedder outputs and modulations were computed from the old weights)
            _mkey(attention_mask),           # (the mask is prepared once per conditioning: a changed mask must never meet a stale prep)
            eng.adapter_weights_key())       # (the adapter weights are in the condition stream's cached rows and modulations)
+    # What the key cannot see is the engine itself being reconfigured between two calls: an adapter change (_adapters_changed), a refused
+    # conditioning, or a block-level call on a block of this transformer (attn_forward / block_forward / single_block_forward configure
+    # the same engine under their own model_config). Each of those leaves eng.cond_ready unset.
     if key != transformer._cond_key or not eng.cond_ready:
         transformer._cond_key = transformer._cond_refs = None          # (a conditioning that raises leaves none behind)
         eng.set_conditioning(encoder_hidden_states, pooled_projections, guidance, txt_ids, img_ids,
