@@ -22,7 +22,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 import torch
 
 from .. import ops
-from ..ops import LX_EPI_GELU, LX_EPI_RESID_F32, LX_EPI_STORE_BF16, LX_EPI_STORE_F32
+from ..ops import LX_EPI_RESID_F32, LX_EPI_STORE_F32
+from .modes import E4M3Mode, Mode16, SplitMode
 from .weights import FluxConfig, PackedWeights
 
 NEG_INF = float("-inf")
@@ -169,6 +170,9 @@ class DiTEngine:
         self._ovf_word, self._ovf_seen = HostWord(), 0         # f16_overflow_poll(sync=False)
         self._gemm_ws: Optional[torch.Tensor] = None
         self._err_word = HostWord()                            # check_status(sync=False)
+        # the operand modes of the block GEMMs (modes.py; stateless). _select_mode picks `mode`; attention_module always runs mode16
+        self.mode16, self.mode8, self.mode_split = Mode16(self), E4M3Mode(self), SplitMode(self)
+        self.mode = self.mode16
         # Step-invariant condition stream (model_config independent_condition / union_cond_attn = False: the condition queries see
         # only condition keys, its timestep c_t is fixed, so its hidden states, keys and values are the same at every denoise step):
         # the first forward after set_conditioning() computes all three streams and leaves the condition keys / V^T of every layer in
@@ -249,9 +253,8 @@ class DiTEngine:
         self.XN8 = self.Y8 = None                                  # fp8-GEMM operand images, allocated by _setup_fp8()
 
     def _setup_precise(self) -> None:
-        """XN2 bf16 [M, 2D] = [hi | lo] of the AdaLN-normalised stream;  Y32 fp32 [M, 3D] = [k | v | q];
-        YA bf16 [M, 10D] = [attn_hi | mlp_hi | attn_lo | mlp_lo]: the attention output / MLP hidden pairs ([attn | mlp] stays
-        ONE contiguous K = 5D operand, its lo image 5D columns further)."""
+        """The split mode's operand buffers -- XN2 bf16 [M, 2D], Y32 fp32 [M, 3D], YA bf16 [M, 10D], lat2 for the step's latents -- and the
+        precise attention's images; what lives where in them: DESIGN.md section 8.2."""
         if self.XN2 is not None:
             return
         if not self.w.precise_ready:
@@ -376,6 +379,16 @@ class DiTEngine:
         self.graphs = {}
         self.cond_ready = False
         self.sched = None
+
+    # What the layers above drop by hand: no other file assigns an engine cache field. (Neither group occurs among
+    # the engine's own events: _adapters_changed keeps the conditioning's mask, configure() keeps `sched` and the shape.)
+    def drop_graphs_and_shape(self) -> None:
+        """The pipeline installed or removed an adapter set: setup() must run again, the adapter rank sizes the modulation scratch."""
+        self.graphs, self.shape = {}, None
+
+    def drop_conditioning(self) -> None:
+        """LxFluxTransformer.invalidate_conditioning: the conditioning is over, its mask and its prepared schedule go with it."""
+        self.cond_ready, self.cond_mask, self.sched = False, None, None
 
     def set_adapter_weights(self, weights: Optional[Dict]) -> None:
         """{adapter name: w}: w a float, or one float per image of the conditioning (a sequence or 1-D tensor of length B, checked by
@@ -747,10 +760,9 @@ class DiTEngine:
             raise ValueError("add_cond_attn adds the condition attention output onto the image stream: needs C == N")
         f32 = torch.float32
         # context_embedder(prompt_embeds) -> cached text rows; x_embedder(condition_latents) with LoRA active -> cached condition rows
-        embed = self._embed_p if self.precise else self._embed
-        embed(prompt_embeds.reshape(B * T, -1), "context_embedder", self.X_txt_init, lora=False)
+        self.mode.embed(prompt_embeds.reshape(B * T, -1), "context_embedder", self.X_txt_init, lora=False)
         if C:
-            embed(condition_latents.reshape(B * C, -1), "x_embedder", self.X_cond_init, lora=True)
+            self.mode.embed(condition_latents.reshape(B * C, -1), "x_embedder", self.X_cond_init, lora=True)
         # RoPE tables: [text; image] and condition (transformer.py:130-134)
         ids = torch.cat([txt_ids.to(dev, f32).reshape(-1, 3), img_ids.to(dev, f32).reshape(-1, 3)], 0)
         # tables live in persistent buffers: the captured step graph holds their addresses
@@ -786,9 +798,9 @@ class DiTEngine:
 
     # ------------------------------------------------------------------------------------------ arithmetic mode
     def _select_mode(self, model_config: Optional[Dict], c_factor: Optional[float], gemm_fp8: bool = True) -> None:
-        """model_config -> latent_lora / precise / gemm_fp8 / the operand format, and the buffers and weight images those modes need: all
-        of them allocated here, by set_conditioning() or configure(), never first inside a capture. gemm_fp8 = False: the caller has no
-        e4m3 GEMM path (the block-level entry points)."""
+        """model_config -> latent_lora / precise / gemm_fp8 / the operand format, the operand mode object (`mode`, modes.py) and the
+        buffers and weight images those modes need: all of them allocated here, by set_conditioning() or configure(), never first inside
+        a capture. gemm_fp8 = False: the caller has no e4m3 GEMM path (the block-level entry points)."""
         self.model_config = dict(model_config or {})
         self.c_factor = c_factor
         self.latent_lora = bool(self.model_config.get("latent_lora", False))
@@ -798,6 +810,7 @@ class DiTEngine:
         self.gemm_fp8 = gemm_fp8 and bool(self.model_config.get("gemm_fp8", False)) and not self.precise
         if self.gemm_fp8:
             self._setup_fp8()
+        self.mode = self.mode_split if self.precise else self.mode8 if self.gemm_fp8 else self.mode16
         self._pick_operands()
         if self.model_config.get("attn_fp8", False) and not self.precise:
             self._fp8_images()
@@ -812,9 +825,6 @@ class DiTEngine:
             self._setup_f16()
         elif self.w16:
             self.w16, self.graphs = {}, {}                 # leaving the fp16 operand mode: its 17 GB of weight images (and the graphs that read them) go
-
-    def _op_dtype(self):
-        return torch.float16 if self.f16 else torch.bfloat16
 
     def _op(self, t: torch.Tensor) -> torch.Tensor:
         """a (slice of a) 16-bit operand buffer in the format the GEMMs of this forward read"""
@@ -836,26 +846,6 @@ class DiTEngine:
         return [(s.row0, self.B * s.len, s.len, s.mods[:, base_by_stream[s.name] + shift_off:], s.mods[:, base_by_stream[s.name] + scale_off:])
                 for s in self._streams()]
 
-    def _ln(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int, lora_for: Optional[str] = None,
-            include_txt: bool = False):
-        """AdaLN LayerNorm + modulation of every stream of this forward into XN (the 16-bit operand image of this mode).
-        lora_for: the Linear that reads XN next (its adapter's down-projection of the adapter rows is computed by the same launch, on the
-        matrix pipe, while the normalised rows are at hand: 76 of the 132 lx_lora_down launches of a denoise step sit behind a LayerNorm).
-        Returns what _gemm_streams takes as `lora` ((adapter, 1 slab, first adapter row), or None when there is nothing to hand over)."""
-        segs = self._ln_segs(base_by_stream, shift_off, scale_off)
-        lora, ready = None, None
-        lo = self.w.lora.get(lora_for) if lora_for is not None else None
-        if (lo is not None and self.ln_lora and self.lora_scale == 1.0 and self.lora_w is None and lo.down.shape[0] <= 16
-                and self.cfg.inner_dim in (3072, 256) and self._lora_rows(include_txt) is not None):      # (the widths the kernel is built for)
-            r0, n = self._lora_rows(include_txt)
-            lora = (self._down(lora_for, lo), self.TL[r0:r0 + n, : lo.down.shape[0]], r0, n)       # slab 0 of TLs: the consumer sums one slab
-            ready = (lo, 1, r0)
-        if self.f16:
-            ops.ln_modulate_segs(self.X, segs, self.XN16, self.mods.stride(0), f16_ovf=self.f16_ovf, lora=lora)
-        else:
-            ops.ln_modulate_segs(self.X, segs, self.XN, self.mods.stride(0), lora=lora)
-        return ready
-
     def _lora_rows(self, include_txt: bool):
         """(first row, row count) of the rows that run with the adapter on: the condition stream always; with
         model_config["latent_lora"] also the image stream and, where text shares the module (single blocks), text.
@@ -869,18 +859,8 @@ class DiTEngine:
         return self.r_cond, self.M - self.r_cond
 
     # An adapter term is handed to a grouped launch as (adapter, slabs of TLs that hold its down-projection, first row they hold), under the
-    # keyword `lora`, in all three modes. (None, 0, 0): nothing to add. The three _lora_t* below compute it from this mode's operand image.
+    # keyword `lora`, in all three modes. (None, 0, 0): nothing to add. Each operand mode (modes.py) computes it from its operand image.
     NO_LORA = (None, 0, 0)
-
-    def _lora_t(self, A: torch.Tensor, name: str, include_txt: bool = False):
-        lo = self.w.lora.get(name)
-        if lo is None or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
-            return self.NO_LORA
-        r0, n = self._lora_rows(include_txt)
-        t = self.TL[r0:r0 + n, : lo.down.shape[0]]
-        ops.lora_down(self._op(A[r0:r0 + n]), self._down(name, lo), t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
-        self._scale_lora(t, self._lora_segs(r0, n), n_slab=self.TL_SPLIT)
-        return lo, self.TL_SPLIT, r0
 
     def _launch_streams(self, desc, workspace, main: str, txt: Optional[str], *, epilogue: int, w_rows: Optional[Dict[str, slice]] = None,
                         t_col0: int = 0, gate_off: Optional[Dict[str, int]] = None, lora_mod_cols: int = 0, lora_toff_max: int = 0,
@@ -909,30 +889,9 @@ class DiTEngine:
             probs.append(desc(s, name, rows, **kw))
         ops.gemm(probs, workspace)
 
-    @staticmethod
-    def _every_stream(rows: slice) -> Dict[str, slice]:
-        return {"txt": rows, "img": rows, "cond": rows}
-
     def _lora_wanted(self, only: Optional[Sequence[str]]) -> bool:
         """Can a launch over `only` have adapter rows at all? (Which rows: _lora_rows.)"""
         return only is None or "cond" in only or self.latent_lora
-
-    def _gemm_streams(self, A: torch.Tensor, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, epilogue: int, gelu_col_start: int = 0,
-                      qkv=None, only: Optional[Sequence[str]] = None, lora=None, **kw) -> None:
-        """The grouped launch (_launch_streams) on the 16-bit operand images of this mode (bf16 or fp16). lora = None: the adapter's
-        down-projection is computed here, from A. qkv = (wq, wk, wq_txt, wk_txt[, layer]): RMSNorm + RoPE + V^T in the launch's epilogue."""
-        if lora is None:
-            lora = self._lora_t(A, main, include_txt=txt is None) if self._lora_wanted(only) else self.NO_LORA
-
-        def desc(s: Stream, name: str, rows: Optional[slice], **k):
-            a, c = self._op(self.rows(A, s.name)), self.rows(Cbuf, s.name)
-            if self.f16 and (epilogue & 0xff) == LX_EPI_STORE_BF16 and qkv is None:
-                c = c.view(torch.float16)               # a 16-bit store of this mode is the next GEMM's fp16 operand
-            if qkv is not None:
-                k["qkv"] = self._qkv_kw(s, qkv)
-            return ops.gemm_desc(a, self._w_rows(self._W(name), rows), c, gelu_col_start=gelu_col_start, **k, **self._f16_kw())
-
-        self._launch_streams(desc, self.gemm_ws(), main, txt, epilogue=epilogue, only=only, lora=lora, **kw)
 
     def _qkv_kw(self, s: Stream, qkv) -> Dict:
         """What the projection launch's fused epilogue (LX_EPI_QKV) needs for stream s: norm weights, the stream's (cos, sin) pairs and
@@ -977,136 +936,56 @@ class DiTEngine:
             return False
         return True
 
-    def _attention(self, wq, wk, wq_txt, wk_txt, prepped: bool = False, layer: Optional[int] = None, img_only: bool = False) -> None:
-        """img_only: only the image segment has queries (the last single block of a forward: the text / condition rows serve keys and values,
-        their q columns were not computed and hold whatever the previous layer left there)."""
-        cfg = self.cfg
-        D, H, B = cfg.inner_dim, cfg.num_attention_heads, self.B
-        Y = self.Y
-        cached = self.cond_cache and layer is not None
-        streams = self._all_streams() if cached else self._streams()      # key / value segments (queries: the streams of this forward)
-        seg_row0, seg_len, seg_vt0, bias, _ = self._attn_segments(streams)
-        # the separate q / k / v pass: the streams with rows in this forward (a cond_skip forward leaves the condition stream's part of the
-        # per-layer images as the first forward of the conditioning wrote it)
-        qsegs = [] if prepped else self._qsegs(self._streams(), wq, wk, wq_txt, wk_txt)
-        # cached, in a cond_skip forward: only the text / image segments have queries (img_only: qseg_mask, which wins)
-        nq = len(self._streams()) if cached and self.cond_skip and not img_only else 0
-        flags = (ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0
-        if not self.pair_plan:             # the batch-size-invariant plans: the attention kernel must not depend on the batch size either
-            flags |= ops.ATTN_INVARIANT
-        okw = dict(f16_ovf=self.f16_ovf) if self.f16 else {}      # O is the output projection's A operand: fp16 in the fp16 operand mode
-        if img_only:
-            okw["qseg_mask"] = 1 << [s.name for s in streams].index("img")
-        if self.f16:
-            flags |= ops.ATTN_O_F16
-        # the caller's mask: a block-level call's (prepared inside the call) or the conditioning's (prepared by set_conditioning)
-        mask, mask_ws = (self.attn_mask, None) if self.attn_mask is not None else (self.cond_mask, self._mask_ws)
-        if mask is not None:
-            # lx_attn_fwd_masked: always a running maximum -- BOUNDED / INVARIANT do not apply to it
-            if self.model_config.get("attn_fp8", False):
-                raise NotImplementedError("attention_mask is not supported in attn_fp8 mode")
-            if cached:        # (unreachable through the public surface: condition caching exists only under rules that replace the mask)
-                raise NotImplementedError("attention_mask is not supported on condition-cached forwards")
-            if not prepped:
-                ops.qkv_prep_segs(Y, 2 * D, 0, D, qsegs, B, H, self.VT, in_f16=self.f16)
-            mflags = (ops.ATTN_Q_LOG2 if self._layer_nomax(wq) else 0) | (ops.ATTN_O_F16 if self.f16 else 0)
-            ops.attn_fwd_masked(Y, Y, self.VT, Y, mask, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
-                                seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, flags=mflags, workspace=mask_ws, prepped=mask_ws is not None,
-                                **okw)
-            return
-        if self.model_config.get("attn_fp8", False):
-            # opt-in fp8 (e4m3) attention (BASELINE configs[4]): q / k / v^T go to byte images, both attention products run on
-            # the 64-deep f8f6f4 MFMA; softmax statistics and the output accumulators stay fp32 (include/lx.h, lx_attn_fwd_fp8)
-            self._fp8_images()
-            # cached: keys / V^T of this forward's streams into the layer's e4m3 images, where the attention reads all streams' from
-            K8, VT8 = (self.KC8[layer], self.VTC8[layer]) if cached else (self.K8, self.VT8)
-            if not prepped:                # otherwise the projection epilogue already wrote the three byte images
-                ops.qkv_prep_fp8_segs(Y, 2 * D, 0, D, qsegs, B, H, self.Q8, K8, VT8, in_f16=self.f16)
-            f8 = (ops.ATTN_O_F16 if self.f16 else 0) | (ops.ATTN_P_EXP2 if self.model_config.get("attn_fp8_exp2", False) else 0)
-            if cached:
-                okw["n_qseg"] = nq
-            ops.attn_fwd_fp8(self.Q8, K8, VT8, Y, o_col=2 * D, B=B, H=H, seg_row0=seg_row0, seg_len=seg_len,
-                             seg_vt0=seg_vt0, bias=bias, flags=f8, **okw)
-            return
-        if cached:
-            # keys from the layer's key image, V^T from the layer's V^T image (the condition stream's part written by the first
-            # forward of this conditioning); in a cond_skip forward only the text / image segments have queries
-            if not prepped:                # no fused epilogue (stream lengths it does not take, or switched off): the separate pass writes them
-                ops.qkv_prep_kv_segs(Y, 2 * D, 0, D, qsegs, B, H, self.KC[layer], 0, self.VTC[layer], in_f16=self.f16)
-            ops.attn_fwd(Y, self.KC[layer], self.VTC[layer], Y, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0,
-                         seg_len=seg_len, seg_vt0=seg_vt0, bias=bias, n_qseg=nq, flags=flags, **okw)
-            return
-        if not prepped:                    # otherwise the projection launch already normalised / rotated k and q and wrote V^T
-            # (fp16 operand mode: an unfused projection stored k | v | q as fp16 -- the pass reads them as such and leaves bf16 k / q, bf16 V^T)
-            ops.qkv_prep_segs(Y, 2 * D, 0, D, qsegs, B, H, self.VT, in_f16=self.f16)
-        ops.attn_fwd(Y, Y, self.VT, Y, q_col=2 * D, k_col=0, o_col=2 * D, B=B, H=H, seg_row0=seg_row0, seg_len=seg_len,
-                     seg_vt0=seg_vt0, bias=bias, flags=flags, **okw)
-
-    # ------------------------------------------------------------------------------------------ blocks
+    # ------------------------------ blocks: written once, against the operand mode's logical operands (modes.py: xn, attn, mlp, attn_mlp)
     def double_block(self, i: int) -> None:
-        if self.precise:
-            return self._double_block_p(i)
-        if self.gemm_fp8:
-            return self._double_block_8(i)
-        cfg, w = self.cfg, self.w
+        cfg, w, m = self.cfg, self.w, self.mode
         D = cfg.inner_dim
         b = cfg.mod_base_double(i)
         base = {"img": b, "cond": b, "txt": b + 6 * D}
         p = f"d{i}"
-        Yq, Ya, Yf = self.Y[:, : 3 * D], self.Y[:, 2 * D: 3 * D], self.Y[:, 3 * D:]
-        ready = self._ln(base, 0, D, lora_for=p + ".qkv")                                   # norm1 / norm1_context (+ the q/k/v adapters' down-projection)
+        ready = m.ln(base, 0, D, lora_for=p + ".qkv")                                       # norm1 / norm1_context (+ the q/k/v adapters' down-projection)
         nw = (w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
         fused = self._qkv_epilogue()
-        self._gemm_streams(self.XN, Yq, p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_BF16, lora_mod_cols=D, lora_toff_max=2,
-                           qkv=nw + (i,) if fused else None, lora=ready)
-        self._attention(*nw, prepped=fused, layer=i)
+        m.gemm("xn", "qkv", p + ".qkv", p + ".qkv_txt", lora_mod_cols=D, lora_toff_max=2, lora=ready, **(dict(qkv=nw + (i,)) if fused else {}))
+        m.attention(*nw, prepped=fused, layer=i)
         gate = {s: base[s] + 2 * D for s in base}
-        self._gemm_streams(Ya, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
+        lo, n_slabs, _ = m.gemm("attn", "x", p + ".out", p + ".out_txt", gate_off=gate)
         if self.C and self.model_config.get("add_cond_attn", False):                          # block.py:233-234
-            lo = w.lora.get(p + ".out") if self.lora_scale != 0.0 else None
-            a = self.rows(Ya, "cond")
-            kw = dict(lora_t=self.rows(self.TL, "cond"), lora_up=lo.up, lora_nsplit=self.TL_SPLIT,
-                      lora_split_stride=self.TLs.stride(0)) if lo is not None else {}
-            ops.gemm([ops.gemm_desc(self._op(a), self._W(p + ".out"), self.rows(self.X, "img"), bias=w.t[p + ".out.b"], epilogue=LX_EPI_RESID_F32,
-                                    rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw, **self._f16_kw())])
-        ready = self._ln(base, 3 * D, 4 * D, lora_for=p + ".ff1")                           # norm2 + (scale_mlp, shift_mlp)
-        self._gemm_streams(self.XN, Yf, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, lora=ready)
+            if self.gemm_fp8:      # known gap: refused here, after the output projection above has been enqueued
+                raise NotImplementedError("add_cond_attn is not wired into the fp8 GEMM path (use the bf16 or the precise mode)")
+            kw = dict(lora_t=self.rows(self.TL, "cond"), lora_up=lo.up, lora_nsplit=n_slabs, lora_split_stride=self.TLs.stride(0)) if lo is not None else {}
+            m.single("attn", "cond", p + ".out", self.rows(self.X, "img"), bias=w.t[p + ".out.b"], epilogue=LX_EPI_RESID_F32,
+                     rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw)
+        ready = m.ln(base, 3 * D, 4 * D, lora_for=p + ".ff1")                               # norm2 + (scale_mlp, shift_mlp)
+        # known gap: the e4m3 ff1 launch evaluates no adapter term, though lora_layout lists d{i}.ff1
+        m.gemm("xn", "mlp", p + ".ff1", p + ".ff1_txt", lora=self.NO_LORA if self.gemm_fp8 else ready)
         gate = {s: base[s] + 5 * D for s in base}
-        self._gemm_streams(Yf, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
+        m.gemm("mlp", "x", p + ".ff2", p + ".ff2_txt", gate_off=gate)
 
     def single_block(self, j: int, image_out_only: bool = False) -> None:
         """image_out_only: the caller reads nothing but the image rows of X afterwards (the LAST block of a forward: norm_out /
         proj_out run on the image tokens, transformer.py:243-252). The text and condition rows then still need their keys and
         values (the image queries attend to them) but neither queries, MLP branch nor output projection: 145 + 145 of the
-        block's 580 GFLOP of GEMM work are skipped, with bit-identical image rows."""
-        if self.precise:
-            return self._single_block_p(j, image_out_only)
-        if self.gemm_fp8:
-            return self._single_block_8(j, image_out_only)
-        cfg, w = self.cfg, self.w
+        block's 580 GFLOP of GEMM work are skipped, with bit-identical image rows (how much a mode skips: its fused() / attention())."""
+        cfg, w, m = self.cfg, self.w, self.mode
         D = cfg.inner_dim
         b = cfg.mod_base_single(j)
         base = {"img": b, "cond": b, "txt": b}
-        p = f"s{j}"
-        ready = self._ln(base, 0, D, lora_for=p + ".fused", include_txt=True)
-        kv_only = {"txt": slice(0, 2 * D), "cond": slice(0, 2 * D)} if image_out_only else None      # fused columns are [k | v | q | mlp]
+        p, layer = f"s{j}", cfg.num_layers + j
+        ready = m.ln(base, 0, D, lora_for=p + ".fused", include_txt=True)
         nw = (w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
         fused = self._qkv_epilogue()
-        self._gemm_streams(self.XN, self.Y, p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, gelu_col_start=3 * D,
-                           lora_mod_cols=D, lora_toff_max=3, w_rows=kv_only, qkv=nw + (cfg.num_layers + j,) if fused else None,
-                           lora=ready)
-        self._attention(*nw, prepped=fused, layer=cfg.num_layers + j, img_only=image_out_only)
+        m.fused(p, ready, image_out_only, nw + (layer,) if fused else None)                 # [k | v | q | mlp] of xn
+        m.attention(*nw, prepped=fused, layer=layer, img_only=image_out_only)
         gate = {s: b + 2 * D for s in base}
-        self._gemm_streams(self.Y[:, 2 * D:], self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate,
-                           only=("img",) if image_out_only else None)
+        m.gemm("attn_mlp", "x", p + ".out", None, gate_off=gate, only=("img",) if image_out_only else None)
 
     # ------------------------------------------------------------------------------------------ fp8 GEMM path
     S_X8, S_Y8 = 16.0, 16.0      # fixed activation scales of the e4m3 images: AdaLN-normalised operand / attention output + MLP hidden
 
     def _setup_fp8(self) -> None:
-        """XN8 u8 [M, D]: e4m3(XN * S_X8);  Y8 u8 [M, 5D] = [attn | mlp]: e4m3(attention output | MLP hidden, * S_Y8) -- again ONE
-        contiguous K = 5D operand for the single block's proj_out. Block weights are quantised once per weight set (per-output-row scale) from
-        the packed bf16 weights and kept as tiled e4m3 images (+11.9 GB)."""
+        """The e4m3 mode's operand images XN8 u8 [M, D] and Y8 u8 [M, 5D] (what lives where: DESIGN.md section 8.2). Block weights are
+        quantised once per weight set (per-output-row scale) from the packed bf16 weights and kept as tiled e4m3 images (+11.9 GB)."""
         if self.XN8 is None:
             D = self.cfg.inner_dim
             self.XN8 = torch.zeros(self.M, D, dtype=torch.uint8, device=self.device)
@@ -1139,230 +1018,10 @@ class DiTEngine:
             t = self.w8[key] = (self.w8[name + ".rs"] / act_scale).contiguous()
         return t if rows is None else t[rows]
 
-    def _gemm_streams_8(self, A8: torch.Tensor, act_scale: float, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, out_scale: float = 0.0,
-                        **kw) -> None:
-        """The grouped launch (_launch_streams) on e4m3 operand images: A8 = e4m3(activation * act_scale), per-output-row weight scales.
-        The caller brings the adapter's down-projection (`lora`), computed from whichever image of the operand it has. No workspace:
-        lx_gemm_fp8_kernel has no pair plan."""
-        def desc(s: Stream, name: str, rows: Optional[slice], **k):
-            return ops.gemm_desc(self.rows(A8, s.name), self._w_rows(self.w8[name], rows), self.rows(Cbuf, s.name), fp8=True,
-                                 col_scale=self._cs(name, act_scale, rows), out_scale=out_scale, **k)
-
-        self._launch_streams(desc, None, main, txt, **kw)
-
-    def _lora_t8(self, X8: torch.Tensor, act_scale: float, name: str, include_txt: bool = False):
-        """LoRA down-projection from an e4m3 operand image (the MLP hidden / [attn | mlp] exist only as fp8 in this mode)."""
-        lo = self.w.lora.get(name)
-        if lo is None or self.lora_scale == 0.0 or self._lora_rows(include_txt) is None:
-            return self.NO_LORA
-        r0, n = self._lora_rows(include_txt)
-        t = self.TL[r0:r0 + n, : lo.down.shape[0]]
-        ops.lora_down_fp8(X8[r0:r0 + n], self.lora_scale / act_scale, lo.down, t, n_split=self.TL_SPLIT, split_stride=self.TLs.stride(0))
-        if self.lora_w_ns is not None:                 # (lora_scale went in with the descale above: the table without it)
-            self._scale_lora(t, self._lora_segs(r0, n), n_slab=self.TL_SPLIT, table=self.lora_w_ns)
-        return lo, self.TL_SPLIT, r0
-
-    def _ln8(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
-        ops.ln_modulate_fp8_segs(self.X, self._ln_segs(base_by_stream, shift_off, scale_off), self.XN, self.XN8, self.mods.stride(0), self.S_X8)
-
-    def _double_block_8(self, i: int) -> None:
-        cfg, w = self.cfg, self.w
-        D = cfg.inner_dim
-        b = cfg.mod_base_double(i)
-        base = {"img": b, "cond": b, "txt": b + 6 * D}
-        p = f"d{i}"
-        Y, Y8 = self.Y, self.Y8
-        self._ln8(base, 0, D)                                                             # XN (bf16, for the LoRA down) + XN8
-        self._gemm_streams_8(self.XN8, self.S_X8, Y[:, : 3 * D], p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_BF16, lora_mod_cols=D,
-                             lora_toff_max=2, lora=self._lora_t(self.XN, p + ".qkv"))
-        self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
-        Ya = Y[:, 2 * D: 3 * D]
-        ops.convert_fp8(Ya, Y8[:, :D], self.S_Y8)                                          # attention output -> e4m3 image
-        gate = {s_: base[s_] + 2 * D for s_ in base}
-        self._gemm_streams_8(Y8[:, :D], self.S_Y8, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate,
-                             lora=self._lora_t(Ya, p + ".out"))
-        if self.C and self.model_config.get("add_cond_attn", False):
-            raise NotImplementedError("add_cond_attn is not wired into the fp8 GEMM path (use the bf16 or the precise mode)")
-        self._ln8(base, 3 * D, 4 * D)
-        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".ff1", p + ".ff1_txt", epilogue=ops.LX_EPI_STORE_FP8 | LX_EPI_GELU, out_scale=self.S_Y8)
-        gate = {s_: base[s_] + 5 * D for s_ in base}
-        self._gemm_streams_8(Y8[:, D:], self.S_Y8, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate,
-                             lora=self._lora_t8(Y8[:, D:], self.S_Y8, p + ".ff2"))
-
-    def _single_block_8(self, j: int, image_out_only: bool = False) -> None:
-        cfg, w = self.cfg, self.w
-        D, r = cfg.inner_dim, cfg.lora_r
-        b = cfg.mod_base_single(j)
-        base = {"img": b, "cond": b, "txt": b}
-        p = f"s{j}"
-        Y, Y8 = self.Y, self.Y8
-        self._ln8(base, 0, D)
-        lora = self._lora_t(self.XN, p + ".fused", include_txt=True)
-        only = ("img",) if image_out_only else None
-        # the fused [k | v | q | mlp] weight in two launches: q/k/v as bf16 for the attention prep, the MLP hidden straight to e4m3
-        self._gemm_streams_8(self.XN8, self.S_X8, Y[:, : 3 * D], p + ".fused", None, epilogue=LX_EPI_STORE_BF16,
-                             w_rows=self._every_stream(slice(0, 3 * D)), lora_mod_cols=D, lora_toff_max=2, lora=lora)
-        self._gemm_streams_8(self.XN8, self.S_X8, Y8[:, D:], p + ".fused", None, epilogue=ops.LX_EPI_STORE_FP8 | LX_EPI_GELU,
-                             out_scale=self.S_Y8, w_rows=self._every_stream(slice(3 * D, 7 * D)), t_col0=3 * r, only=only, lora=lora)
-        self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
-        ops.convert_fp8(Y[:, 2 * D: 3 * D], Y8[:, :D], self.S_Y8)
-        gate = {s_: b + 2 * D for s_ in base}
-        self._gemm_streams_8(Y8, self.S_Y8, self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate, only=only,
-                             lora=self._lora_t8(Y8, self.S_Y8, p + ".out", include_txt=True))
-
-    # ------------------------------------------------------------------------------------------ precise mode
-    def _desc_p(self, A2: torch.Tensor, name: str, Cbuf: torch.Tensor, *, K: int, a_lo_off: int, w_rows: Optional[slice] = None, **kw):
-        """GEMM descriptor of a split-bf16 launch: A2 holds the hi image in columns [0, K) and the lo image a_lo_off columns
-        further; the weight is [W_hi | W_lo] (3 K-segments) when it has a rounding residual, else W (2 segments)."""
-        w2 = self.w.t.get(name + ".w2")
-        W = self._w_rows(w2 if w2 is not None else self.w.t[name + ".w"], w_rows)
-        return ops.gemm_desc(A2, W, Cbuf, K=K, N=W.shape[0], k_segs=3 if w2 is not None else 2, a_lo_off=a_lo_off, **kw)
-
-    def _lora_t_p(self, A2: torch.Tensor, name: str, K: int, a_lo_off: int, r0: int, n: int, segs=None):
-        """t = x A_down^T for rows [r0, r0+n) with x = hi + lo: one slab per cross term (the consumer GEMM adds them).
-        Returns the `lora` of the launch that consumes them (NO_LORA: no adapter on this Linear). segs: how the rows map to images where
-        they are not the token streams' (_lora_segs)."""
-        lo = self.w.lora.get(name)
-        if lo is None or self.lora_scale == 0.0:
-            return self.NO_LORA
-        R = lo.down.shape[0]
-        terms = [(A2[r0:r0 + n, :K], lo.down), (A2[r0:r0 + n, a_lo_off:a_lo_off + K], lo.down)]
-        if lo.down_lo is not None:
-            terms.append((A2[r0:r0 + n, :K], lo.down_lo))
-        # one launch for the cross terms (slab s = term s; the consumer GEMM adds the slabs)
-        ops.lora_down_terms(terms, self.TLs[0, r0:r0 + n, :R], self.TLs.stride(0))
-        self._scale_lora(self.TLs[0, r0:r0 + n, :R], self._lora_segs(r0, n) if segs is None else segs, n_slab=len(terms))
-        return lo, len(terms), r0
-
-    def _embed_p(self, x32: torch.Tensor, name: str, out: torch.Tensor, lora: bool, pair: Optional[torch.Tensor] = None) -> None:
-        """out(fp32) = Linear_name(x32) with x as a hi/lo pair (context_embedder / x_embedder)."""
-        x32 = x32.to(device=self.device, dtype=torch.float32).contiguous()
-        rows, K = x32.shape
-        if pair is None:
-            pair = torch.empty(rows, 2 * K, dtype=torch.bfloat16, device=self.device)
-        ops.split_bf16(x32, pair, K)
-        kw = {}
-        if lora:
-            lo, ns, _ = self._lora_t_p(pair, name, K, K, 0, rows, segs=self._embed_segs(rows)) if rows <= self.TLs.shape[1] else self.NO_LORA
-            if lo is not None:
-                kw = dict(lora_t=self.TL[:rows], lora_up=lo.up, lora_nsplit=ns, lora_split_stride=self.TLs.stride(0))
-        ops.gemm([self._desc_p(pair, name, out, K=K, a_lo_off=K, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, **kw)], self.gemm_ws())
-
-    def _embed(self, x: torch.Tensor, name: str, out: torch.Tensor, lora: bool) -> None:
-        """out(fp32) = Linear_name(x) on the 16-bit operand image of x in this mode (context_embedder / x_embedder): _embed_p's twin for
-        the bf16 / fp16 / e4m3 modes (whose embedders run on 16-bit operands alike)."""
-        x = x.to(device=self.device, dtype=self._op_dtype()).contiguous()
-        lo = self.w.lora.get(name) if (lora and self.lora_scale != 0.0) else None
-        tl = None
-        if lo is not None:
-            tl = self.TL[: x.shape[0], : self.cfg.lora_r]
-            ops.lora_down(x, self._down(name, lo), tl)
-            self._scale_lora(tl, self._embed_segs(x.shape[0]))
-        ops.gemm([ops.gemm_desc(x, self._W(name), out, bias=self.w.t[name + ".b"], epilogue=LX_EPI_STORE_F32, lora_t=tl,
-                                lora_up=lo.up if lo is not None else None, **self._f16_kw())])
-
-    def _ln_p(self, base_by_stream: Dict[str, int], shift_off: int, scale_off: int) -> None:
-        ops.ln_modulate_split_segs(self.X, self._ln_segs(base_by_stream, shift_off, scale_off), self.XN2, self.mods.stride(0), self.cfg.inner_dim)
-
-    def _gemm_streams_p(self, A2: torch.Tensor, K: int, a_lo_off: int, Cbuf: torch.Tensor, main: str, txt: Optional[str], *, c_lo_off: int = 0,
-                        only: Optional[Sequence[str]] = None, lora=None, **kw):
-        """The grouped launch (_launch_streams) on split-bf16 operands (_desc_p). lora = None: the adapter's down-projection is computed
-        here, from A2. Returns the `lora` it launched with, for a sibling launch over the same operand (the two halves of the single
-        blocks' fused weight) or the add_cond_attn launch."""
-        if lora is None:
-            lora = self.NO_LORA
-            if self._lora_wanted(only) and self._lora_rows(txt is None) is not None:
-                lora = self._lora_t_p(A2, main, K, a_lo_off, *self._lora_rows(txt is None))
-
-        def desc(s: Stream, name: str, rows: Optional[slice], **k):
-            return self._desc_p(self.rows(A2, s.name), name, self.rows(Cbuf, s.name), K=K, a_lo_off=a_lo_off, w_rows=rows, c_lo_off=c_lo_off, **k)
-
-        # (the workspace admits lx_gemm4_kernel<true> and its split form; None under LX_PAIR_PLAN=0)
-        self._launch_streams(desc, self.gemm_ws(), main, txt, only=only, lora=lora, **kw)
-        return lora
-
-    def _attention_p(self, wq, wk, wq_txt, wk_txt, layer: Optional[int] = None, img_only: bool = False) -> None:
-        """fp32 q / k / v in Y32 = [k | v | q]: per-head RMSNorm + RoPE in fp32, fp32 attention, output pair into YA's attn columns.
-        layer: the block's index among all blocks, for the per-layer images of the condition cache. img_only: only the image segment has
-        queries (the last single block of a forward; split-bf16 attention only -- the exact-fp32 kernel has no query-segment subset)."""
-        D, H, B = self.cfg.inner_dim, self.cfg.num_attention_heads, self.B
-        if self.precise_attn_split:
-            # split-bf16 attention: hi.hi + hi.lo + lo.hi on the bf16 MFMA (3/16 of the fp32-MFMA cost), fp32 softmax
-            cached = self.cond_cache and layer is not None
-            qsegs = self._qsegs(self._streams(), wq, wk, wq_txt, wk_txt)          # the prep pass: the streams with rows in this forward
-            streams = self._all_streams() if cached else self._streams()      # key / value segments
-            seg_row0, seg_len, seg_vt0, bias, _ = self._attn_segments(streams)
-            kw, vt = {}, self.VT2
-            if cached:
-                # k and V^T pairs of this forward's streams into the layer's images (q into the shared QK2): the condition stream's part is
-                # written by the first forward of a conditioning and left alone by the cond_skip forwards, which read it from there
-                vt = self.VTC2[layer]
-                ops.qkv_prep_split_kv_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, 2 * D, self.KC2[layer], 0, D, vt)
-                kw["K"] = self.KC2[layer]
-            else:
-                ops.qkv_prep_split_segs(self.Y32, 2 * D, 0, D, qsegs, B, H, self.QK2, q2_col=2 * D, k2_col=0, lo_off=D, VT2=vt)
-            if img_only:
-                kw["qseg_mask"] = 1 << [s.name for s in streams].index("img")
-            elif cached and self.cond_skip:
-                kw["n_qseg"] = len(self._streams())
-            ops.attn_fwd_split(self.QK2, vt, self.YA, q_col=2 * D, k_col=0, qk_lo_off=D, o_col=0, o_lo_off=5 * D, B=B, H=H,
-                               seg_row0=seg_row0, seg_len=seg_len, seg_vt0=seg_vt0, bias=bias,
-                               flags=(ops.ATTN_Q_LOG2 | ops.ATTN_BOUNDED) if self._layer_nomax(wq) else 0, **kw)
-            return
-        seg_row0, seg_len, seg_vt0, bias, qsegs = self._attn_segments(self._streams(), (wq, wk, wq_txt, wk_txt))
-        ops.qkv_prep_f32_segs(self.Y32, 2 * D, 0, qsegs, B, H)
-        ops.attn_fwd_f32(self.Y32, self.YA, q_col=2 * D, k_col=0, v_col=D, o_col=0, o_lo_off=5 * D, B=B, H=H, seg_row0=seg_row0,
-                         seg_len=seg_len, bias=bias)
-
-    def _double_block_p(self, i: int) -> None:
-        cfg, w = self.cfg, self.w
-        D = cfg.inner_dim
-        b = cfg.mod_base_double(i)
-        base = {"img": b, "cond": b, "txt": b + 6 * D}
-        p = f"d{i}"
-        self._ln_p(base, 0, D)
-        self._gemm_streams_p(self.XN2, D, D, self.Y32, p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_F32, lora_mod_cols=D, lora_toff_max=2)
-        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"], layer=i)
-        gate = {s_: base[s_] + 2 * D for s_ in base}
-        lora = self._gemm_streams_p(self.YA, D, 5 * D, self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
-        if self.C and self.model_config.get("add_cond_attn", False):                          # block.py:233-234
-            lo, ns, _ = lora
-            a = self.rows(self.YA, "cond")
-            kw = dict(lora_t=self.rows(self.TL, "cond"), lora_up=lo.up, lora_nsplit=ns, lora_split_stride=self.TLs.stride(0)) if lo is not None else {}
-            ops.gemm([self._desc_p(a, p + ".out", self.rows(self.X, "img"), K=D, a_lo_off=5 * D, bias=w.t[p + ".out.b"],
-                                   epilogue=LX_EPI_RESID_F32, rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw)], self.gemm_ws())
-        self._ln_p(base, 3 * D, 4 * D)
-        Ym = self.YA[:, D:]                                                                   # mlp hidden pair: hi at [D, 5D), lo 5D further
-        self._gemm_streams_p(self.XN2, D, D, Ym, p + ".ff1", p + ".ff1_txt", epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, c_lo_off=5 * D)
-        gate = {s_: base[s_] + 5 * D for s_ in base}
-        self._gemm_streams_p(Ym, 4 * D, 5 * D, self.X, p + ".ff2", p + ".ff2_txt", epilogue=LX_EPI_RESID_F32, gate_off=gate)
-
-    def _single_block_p(self, j: int, image_out_only: bool = False) -> None:
-        cfg, w = self.cfg, self.w
-        D, r = cfg.inner_dim, cfg.lora_r
-        b = cfg.mod_base_single(j)
-        base = {"img": b, "cond": b, "txt": b}
-        p = f"s{j}"
-        self._ln_p(base, 0, D)
-        # the fused [k | v | q | mlp] weight in two launches: q/k/v stay fp32 (Y32), the MLP hidden becomes a GELU'd bf16 pair
-        lora = self._gemm_streams_p(self.XN2, D, D, self.Y32, p + ".fused", None, epilogue=LX_EPI_STORE_F32,
-                                    w_rows=self._every_stream(slice(0, 3 * D)), lora_mod_cols=D, lora_toff_max=2)
-        only = ("img",) if image_out_only else None
-        self._gemm_streams_p(self.XN2, D, D, self.YA[:, D:], p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, c_lo_off=5 * D,
-                             w_rows=self._every_stream(slice(3 * D, 7 * D)), t_col0=3 * r, only=only, lora=lora)
-        self._attention_p(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"], layer=cfg.num_layers + j, img_only=image_out_only)
-        gate = {s_: b + 2 * D for s_ in base}
-        self._gemm_streams_p(self.YA, 5 * D, 5 * D, self.X, p + ".out", None, epilogue=LX_EPI_RESID_F32, gate_off=gate, only=only)
-
     # ------------------------------------------------------------------------------------------ one step
     def embed_step_inputs(self, latents: torch.Tensor, timestep: torch.Tensor, mods_ready: bool = False) -> None:
         """x_embedder(latents), reset text/condition rows, temb(t) and every image/text modulation vector."""
-        if self.precise:
-            self._embed_p(latents.reshape(self.B * self.N, -1), "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora, pair=self.lat2)
-        else:
-            lat = self._op(self.lat16)
-            ops.convert(lat, latents.reshape(self.B * self.N, -1).contiguous())
-            self._embed(lat, "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora)
+        self.mode.embed(latents.reshape(self.B * self.N, -1), "x_embedder", self.rows(self.X, "img"), lora=self.latent_lora, step=True)
         self.rows(self.X, "txt").copy_(self.X_txt_init)
         if self.C and not self.cond_skip:
             self.rows(self.X, "cond").copy_(self.X_cond_init)
@@ -1376,17 +1035,14 @@ class DiTEngine:
         """norm_out (AdaLayerNormContinuous: chunk order scale, shift) + proj_out on the image rows."""
         cfg, w = self.cfg, self.w
         D, o = cfg.inner_dim, cfg.mod_base_out
+        shift, scale = self.mods[:, o + D:], self.mods[:, o:]
+        # the one LayerNorm that stays mode-specific: 16-bit operands get the plain one-segment kernel, which the modes' ln() does not describe
         if self.precise:
-            ops.ln_modulate_split_segs(self.X, [(self.r_img, self.B * self.N, self.N, self.mods[:, o + D:], self.mods[:, o:])], self.XN2,
-                                       self.mods.stride(0), D)
-            ops.gemm([self._desc_p(self.rows(self.XN2, "img"), "proj_out", self.out, K=D, a_lo_off=D, bias=w.t["proj_out.b"],
-                                   epilogue=LX_EPI_STORE_F32)], self.gemm_ws())
-            return self.out.view(self.B, self.N, cfg.in_channels)
-        xn = self._op(self.rows(self.XN, "img"))
-        ops.ln_modulate(self.rows(self.X, "img"), self.mods[:, o + D:], self.mods[:, o:], xn,
-                        rows_per_batch=self.N, mod_ld=self.mods.stride(0), **(dict(f16_ovf=self.f16_ovf) if self.f16 else {}))
-        ops.gemm([ops.gemm_desc(xn, self._W("proj_out"), self.out, bias=w.t["proj_out.b"],
-                                epilogue=LX_EPI_STORE_F32, **self._f16_kw())])
+            ops.ln_modulate_split_segs(self.X, [(self.r_img, self.B * self.N, self.N, shift, scale)], self.XN2, self.mods.stride(0), D)
+        else:
+            ops.ln_modulate(self.rows(self.X, "img"), shift, scale, self._op(self.rows(self.XN, "img")),
+                            rows_per_batch=self.N, mod_ld=self.mods.stride(0), **(dict(f16_ovf=self.f16_ovf) if self.f16 else {}))
+        self.mode.single("xn", "img", "proj_out", self.out, bias=w.t["proj_out.b"], epilogue=LX_EPI_STORE_F32)
         return self.out.view(self.B, self.N, cfg.in_channels)
 
     def _forward_eager(self, latents: torch.Tensor, timestep: torch.Tensor, mods_ready: bool = False) -> torch.Tensor:
@@ -1567,17 +1223,15 @@ class DiTEngine:
     def attention_module(self, kind: str, idx: int, project_out: bool) -> None:
         """attn_forward (block.py:7-176) on the normalised activations already in XN: QKV projections, QK-RMSNorm,
         RoPE, joint attention; double blocks also apply to_out / to_add_out into X (plain store)."""
-        cfg, w, D = self.cfg, self.w, self.cfg.inner_dim
+        w, D, m = self.w, self.cfg.inner_dim, self.mode16          # (the 16-bit kernels whatever the mode: attn_forward has no other path)
         self.block_level_entry()
         if kind == "double":
             p = f"d{idx}"
-            self._gemm_streams(self.XN, self.Y[:, : 3 * D], p + ".qkv", p + ".qkv_txt", epilogue=LX_EPI_STORE_BF16,
-                               lora_mod_cols=D, lora_toff_max=2)
-            self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
+            m.gemm("xn", "qkv", p + ".qkv", p + ".qkv_txt", lora_mod_cols=D, lora_toff_max=2)
+            m.attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq_txt"], w.t[p + ".wk_txt"])
             if project_out:
-                self._gemm_streams(self.Y[:, 2 * D: 3 * D], self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_STORE_F32)
+                m.launch(m.operand("attn"), self.X, p + ".out", p + ".out_txt", epilogue=LX_EPI_STORE_F32)      # a plain store, no gate
         else:
             p = f"s{idx}"
-            self._gemm_streams(self.XN, self.Y, p + ".fused", None, epilogue=LX_EPI_STORE_BF16 | LX_EPI_GELU, gelu_col_start=3 * D,
-                               lora_mod_cols=D, lora_toff_max=3)
-            self._attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])
+            m.fused(p, None, False, None)
+            m.attention(w.t[p + ".wq"], w.t[p + ".wk"], w.t[p + ".wq"], w.t[p + ".wk"])

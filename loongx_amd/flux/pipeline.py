@@ -191,9 +191,7 @@ class LxFluxPipeline:
         return n
 
     def _adapters_changed(self) -> None:
-        eng = self.transformer.engine
-        eng.graphs = {}
-        eng.shape = None               # the adapter rank sizes the modulation scratch: re-run setup()
+        self.transformer.engine.drop_graphs_and_shape()
         self.transformer.invalidate_conditioning()
 
     def set_adapters(self, adapter_names, adapter_weights=None):

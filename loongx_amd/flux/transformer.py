@@ -61,9 +61,7 @@ class LxFluxTransformer:
     def invalidate_conditioning(self) -> None:
         """Forget the step-invariant conditioning cache (generate() calls this at the start and end of every image)."""
         self._cond_key = self._cond_refs = None
-        self.engine.cond_ready = False
-        self.engine.cond_mask = None
-        self.engine.sched = None
+        self.engine.drop_conditioning()
 
     @classmethod
     def from_state_dict(cls, sd, cfg: FluxConfig, device="cuda", lora_scale: float = 1.0, prefix: str = "", precise: bool = False,

@@ -384,7 +384,7 @@ def test_last_block_attention_for_image_queries_only(ops, monkeypatch, mc):
     """The last single block's attention runs the image queries only (qseg_mask): the forward's output is bit-identical to the one with
     that launch forced to all queries, with and without the condition cache."""
     monkeypatch.setenv("LX_COND_CACHE", "1")
-    from loongx_amd.flux.engine import DiTEngine
+    from loongx_amd.flux.modes import SplitMode
     s = setup()
     assert s["tr"].config.num_single_layers >= 1
     seen = []
@@ -398,8 +398,8 @@ def test_last_block_attention_for_image_queries_only(ops, monkeypatch, mc):
     for forced in (False, True):
         with monkeypatch.context() as m:
             if forced:
-                orig = DiTEngine._attention_p
-                m.setattr(DiTEngine, "_attention_p", lambda self, *a, **kw: orig(self, *a, **dict(kw, img_only=False)))
+                orig = SplitMode.attention
+                m.setattr(SplitMode, "attention", lambda self, *a, **kw: orig(self, *a, **dict(kw, img_only=False)))
             eng = _engine(s["tr"])
             eng.use_graph = False
             _condition(eng, s, 0, mc)

@@ -134,7 +134,7 @@ def _status(ops, ws):
 
 @pytest.mark.parametrize("plan", ["w8", "g4", "g4sk"])
 def test_gemm_split_bf16_lora_gate_residual(ops, plan, gemm_plan):
-    """The precise mode's gated-residual launch with the LoRA term as cross-term slabs (engine._gemm_streams_p): two problems (one with
+    """The precise mode's gated-residual launch with the LoRA term as cross-term slabs (modes.SplitMode.gemm): two problems (one with
     the adapter, rank 4, three slabs), three K segments, 12 + 12 tiles, against fp64."""
     ws = gemm_plan(plan)
     M, N, K, r, B = 512, 768, 1024, 4, 2

@@ -6,7 +6,8 @@
 
 The other file is loaded as a sibling module inside the loongx_amd.flux package, so its relative imports resolve against the same ops and
 the same library. One DiTEngine of each module is built on the same PackedWeights; every case runs set_conditioning and two forwards on
-identical inputs and requires torch.equal on both velocities and on the final X, and equal f16_overflow_count(). Weights:
+identical inputs and requires torch.equal on both velocities and on the final X, and equal f16_overflow_count(); a case both modules
+must refuse requires the same exception from both. Weights:
 tests/helpers.tiny_transformer() (2 + 2 blocks, 2 heads, D = 256). Inputs: tests/golden/flux_tiny.npz (16 / 16 / 16 tokens, which no
 stream of 32 divides: the separate q / k / v pass) and a seeded 32 / 64 / 64 set (the fused projection epilogue and, with
 independent_condition, the cached condition stream in the second forward). One line per case; exits non-zero on the first difference."""
@@ -121,6 +122,17 @@ def block_case(mod, W, kind, mc=None):
     return out + [eng.f16_overflow_count()]
 
 
+def outcome(fn, *a, raises=None, **kw):
+    """fn's result; for a case that must be refused, the exception's text (exits if nothing was raised)."""
+    if raises is None:
+        return fn(*a, **kw)
+    try:
+        fn(*a, **kw)
+    except raises as e:
+        return [f"{type(e).__name__}: {e}"]
+    sys.exit(f"{fn.__name__}{kw}: expected {raises.__name__}, nothing was raised")
+
+
 def same(a, b):
     return len(a) == len(b) and all(torch.equal(x, y) if isinstance(x, torch.Tensor) else x == y for x, y in zip(a, b))
 
@@ -144,7 +156,15 @@ def main():
             ("precise latent_lora add_cond_attn", dict(W=Wp, mc={"precise": True, "latent_lora": True, "add_cond_attn": True})),
             ("attn_fp8", dict(mc={"attn_fp8": True})), ("gemm_fp8", dict(mc={"gemm_fp8": True})),
             ("gemm_fp8 latent_lora", dict(mc={"gemm_fp8": True, "latent_lora": True})),
-            ("gemm_fp8 + attn_fp8", dict(mc={"gemm_fp8": True, "attn_fp8": True}))]
+            ("gemm_fp8 + attn_fp8", dict(mc={"gemm_fp8": True, "attn_fp8": True})),
+            # the mode and path combinations that meet in the blocks written once for all operand modes: the per-layer condition cache
+            # through the shared block's layer index, the masked-off condition stream on split operands, the refusal, a wide adapter
+            ("precise independent_condition", dict(W=Wp, mc={"precise": True, "independent_condition": True})),
+            ("attn_fp8 independent_condition", dict(mc={"attn_fp8": True, "independent_condition": True})),
+            ("operands fp16 independent_condition", dict(mc={"operands": "fp16", "independent_condition": True})),
+            ("precise union_cond_attn False", dict(W=Wp, mc={"precise": True, "union_cond_attn": False})),
+            ("gemm_fp8 add_cond_attn (refused)", dict(mc={"gemm_fp8": True, "add_cond_attn": True}, raises=NotImplementedError)),
+            ("rank-16 adapters add_cond_attn", dict(W=W16, mc={"add_cond_attn": True}))]
     cases = [(f"{name}, graph {'on' if g else 'off'}", dict(kw, graph=g)) for name, kw in core for g in (True, False)]
     cases += [("default, unfused", dict(attrs=unfused)), ("operands fp16, unfused", dict(mc={"operands": "fp16"}, attrs=unfused)),
               ("latent_lora, unfused", dict(mc={"latent_lora": True}, attrs=unfused)),
@@ -159,7 +179,7 @@ def main():
         for name, kw in cases:
             kw = dict(kw)
             Wc = kw.pop("W", W)
-            ok = same(forward_case(engine_here, Wc, I, **kw), forward_case(other, Wc, I, **kw))
+            ok = same(outcome(forward_case, engine_here, Wc, I, **kw), outcome(forward_case, other, Wc, I, **kw))
             print(f"{'equal' if ok else 'DIFFERENT':9s} {inputs_name}: {name}", flush=True)
             if not ok:
                 sys.exit(1)

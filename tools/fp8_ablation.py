@@ -82,9 +82,9 @@ class Hooks:
         self.kinds, self.recipe = set(), "fixed"
         self.attn_qk = self.attn_v = False
         self.wcache = {}
-        self._orig_gemm_streams = eng._gemm_streams
+        self._orig_gemm_streams = eng.mode16.launch          # the 16-bit operand mode's grouped launch (flux/modes.py)
         self._orig_attn = ops.attn_fwd
-        eng._gemm_streams = self.gemm_streams
+        eng.mode16.launch = self.gemm_streams
         ops.attn_fwd = self.attn_fwd
 
     def _wq(self, name: str) -> torch.Tensor:
@@ -104,7 +104,7 @@ class Hooks:
             return self._orig_gemm_streams(A, Cbuf, main, txt, **kw)
         eng = self.eng
         if kw.get("lora") is None and eng._lora_wanted(kw.get("only")):      # the adapters' down-projection reads the unquantised operand, as the fp8 engine path does for q/k/v
-            kw["lora"] = eng._lora_t(A, main, include_txt=txt is None)
+            kw["lora"] = eng.mode16.lora_t(A, main, include_txt=txt is None)
         Aq = ACT[self.recipe](A.float()).to(torch.bfloat16)
         names = [main] + ([txt] if txt is not None else [])
         saved = {n: eng.w.t[n + ".w"] for n in names}
