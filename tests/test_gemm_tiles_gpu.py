@@ -5,6 +5,8 @@ the mixed plan's peeled tail and its m_base) has edges, against a float64 produc
   * each problem is cut into 128 x 256 tiles and the worst tile's relative L2 error is held to the format's bound;
   * C lives inside a sentinel-filled buffer (rows above and below, ldc = N + 24): everything outside [M, N] keeps its bits, everything
     inside is finite (a tile the decode never reached stays NaN);
+  * the LoRA slabs (an input; rank, slab count, row stride and first column per problem: Prob.set_lora, defaults r = 4 and 2 slabs) lie
+    inside NaN sentinels too -- a row or rank read out of range makes the output non-finite -- and keep their bits;
   * the same launch twice gives the same bits; the plans without a workspace give the same bits whichever of them runs, for a problem
     alone, inside its group, or as a row slice (include/lx.h: a data-parallel shard reproduces the batch bit for bit); lx_gemm4_kernel
     and its split forms agree with the 8-wave kernels within one fp32 rounding per element.
@@ -151,14 +153,27 @@ def tile_worst(got, ref):
 
 
 # ------------------------------------------------------------------------------------------------ problems
+def lora_term64(slabs, up, R, mod_cols, toff_max):
+    """float64 adapter term of a GEMM: out[m, n] = sum_r t[m, toff(n) + r] up[n, r] with t the sum of the slabs [nsplit, M, >= (toff_max
+    + 1) R] and toff(n) = R min(n // mod_cols, toff_max) -- the module a column belongs to picks its R columns of t."""
+    t = slabs.double().sum(0)
+    N = up.shape[0]
+    out = torch.zeros(t.shape[0], N, dtype=torch.float64, device=t.device)
+    for b in range(-(-N // mod_cols)):
+        m = min(b, toff_max) * R
+        c = slice(b * mod_cols, min(N, (b + 1) * mod_cols))
+        out[:, c] = t[:, m:m + R] @ up[c].double().T
+    return out
+
+
 class Prob:
     """One GEMM problem: operands in the launch's format, its output block, and its float64 reference.
     fmt: bf16 | f16 | fp8 | split2 | split3.  epi: store (16-bit store + GELU) | f32 | lora (fp32 store + LoRA) | res (gated residual) |
     fp8out (e4m3 store + GELU) | pair (LX_EPI_SPLIT_BF16 + GELU)."""
     R, NSPLIT, MOD_COLS, TOFF_MAX, GELU_COL = 4, 2, 256, 1, 200
 
-    def __init__(self, fmt, M, N, K, epi, seed, rpb=None, lora=False):
-        self.fmt, self.M, self.N, self.K, self.epi, self.rpb = fmt, M, N, K, epi, rpb
+    def __init__(self, fmt, M, N, K, epi, seed, rpb=None, lora=False, R=None, nsplit=None, ldt=None, t_col0=0):
+        self.fmt, self.M, self.N, self.K, self.epi, self.rpb, self.seed = fmt, M, N, K, epi, rpb, seed
         self.lora = lora or epi == "lora"
         g = seed * 10
         A = randn(M, K, seed=g + 1)
@@ -192,11 +207,32 @@ class Prob:
             nb = -(-M // rpb)
             self.gate = randn(nb, N, seed=g + 4)
             self.X0 = randn(M, N, seed=g + 5)
+        self._main = self._ref = None
         if self.lora:
-            ldt = 2 * self.R
-            self.slabs = randn(self.NSPLIT, M, ldt, seed=g + 6, scale=0.5).contiguous()
-            self.up = randn(N, self.R, seed=g + 7, scale=0.1).contiguous()
+            self.set_lora(R, nsplit, ldt, t_col0)
+
+    def set_lora(self, R=None, nsplit=None, ldt=None, t_col0=0):
+        """(Re)draw the adapter inputs -- rank R, nsplit slabs, row stride ldt (default 2 R), lora_t at column t_col0 of the slab rows --
+        and drop the cached reference (the operands' float64 product is kept). Each slab lies inside sentinels: PAD NaN rows above and
+        below it and NaN in the columns the step never reads (ldt > t_col0 + (TOFF_MAX + 1) R), so a row or rank read out of range
+        shows as a non-finite output, and the whole buffer must keep its bits."""
+        assert self.lora
+        self.R, self.NSPLIT, self.t_col0 = R or Prob.R, nsplit or Prob.NSPLIT, t_col0
+        w = (self.TOFF_MAX + 1) * self.R
+        self.ldt = 2 * self.R if ldt is None else ldt
+        assert self.ldt >= t_col0 + w, (self.ldt, t_col0, w)
+        g = self.seed * 10
+        self.tbuf = torch.empty(self.NSPLIT, self.M + 2 * PAD, self.ldt, dtype=torch.float32, device=DEV)
+        self.tbuf.view(torch.int32).fill_(SENT[torch.float32])
+        self.slabs = self.tbuf[:, PAD:PAD + self.M, t_col0:t_col0 + w]
+        self.slabs.copy_(randn(self.NSPLIT, self.M, w, seed=g + 6, scale=0.5))
+        self.up = randn(self.N, self.R, seed=g + 7, scale=0.1).contiguous()
+        self.tinit = self.tbuf.clone()
         self._ref = None
+
+    def check_inputs(self, what):
+        if self.lora:
+            assert torch.equal(self.tbuf.view(torch.int32), self.tinit.view(torch.int32)), f"{what}: the launch changed its input lora_t"
 
     @staticmethod
     def _wq(W):
@@ -206,16 +242,14 @@ class Prob:
     # -- reference (float64, from the operands the kernel reads), rows [r0, r1) --
     def y(self):
         if self._ref is None:
-            y = self.A64 @ self.W64.T
-            if self.fmt == "fp8":
-                y = y * self.cs.double()
-            y = y + self.bias.double()
+            if self._main is None:
+                y = self.A64 @ self.W64.T
+                if self.fmt == "fp8":
+                    y = y * self.cs.double()
+                self._main = y + self.bias.double()
+            y = self._main.clone()
             if self.lora:
-                t = self.slabs.double().sum(0)
-                for b in range(-(-self.N // 256)):
-                    m = min(b, self.TOFF_MAX) * self.R
-                    c = slice(b * 256, min(self.N, (b + 1) * 256))
-                    y[:, c] += t[:, m:m + self.R] @ self.up[c].double().T
+                y += lora_term64(self.slabs, self.up, self.R, self.MOD_COLS, self.TOFF_MAX)
             if self.epi in ("store", "fp8out", "pair"):
                 c = self.GELU_COL
                 y[:, c:] = torch.nn.functional.gelu(y[:, c:], approximate="tanh")
@@ -262,7 +296,7 @@ class Prob:
             assert r0 % self.rpb == 0
             kw.update(gate=self.gate[r0 // self.rpb:], rows_per_batch=self.rpb)
         if self.lora:
-            kw.update(lora_t=self.slabs[0, r0:], lora_up=self.up, lora_nsplit=self.NSPLIT, lora_split_stride=self.slabs.stride(0),
+            kw.update(lora_t=self.tbuf[0, PAD + r0:, self.t_col0:], lora_up=self.up, lora_nsplit=self.NSPLIT, lora_split_stride=self.tbuf.stride(0),
                       lora_mod_cols=self.MOD_COLS, lora_toff_max=self.TOFF_MAX)
         if self.fmt == "fp8":
             kw.update(fp8=True, col_scale=self.cs)
@@ -306,17 +340,18 @@ class Prob:
 
 
 # ------------------------------------------------------------------------------------------------ the four-problem launch
-def group(fmt, K, rows0, seed=0):
+def group(fmt, K, rows0, seed=0, lora_p3=False, **lora):
     """Four problems of one K, different M and N, mixed epilogues:
       p0  M = 256 (rows0 - 1) + 1 (or 20 for rows0 = 1), N = 2040: a 16-bit / e4m3 / hi-lo store with GELU from column 200 (inside a tile)
       p1  M = 2303 (9 tile rows, M % 256 = 255), N = 776 (3 x 256 + 8): fp32 store + LoRA (2 slabs, modules of 256 columns, toff_max 1)
       p2  M = 1055 (5 tile rows, M % 256 = 31), N = 264: fp32 store
       p3  M = 641 (M % 256 = 129), N = 64 (proj_out): gated fp32 residual, 100 rows per batch
-    49 + 8 rows0 tiles of 256 x 256; the last ones in launch order are p3, p2 and p1's ragged last tile row."""
+    49 + 8 rows0 tiles of 256 x 256; the last ones in launch order are p3, p2 and p1's ragged last tile row.
+    lora = R, nsplit, ldt, t_col0 of p1's adapter inputs (Prob.set_lora); lora_p3 gives p3 the adapter term with the same parameters."""
     store = {"fp8": "fp8out", "split2": "pair", "split3": "pair"}.get(fmt, "store")
     M0 = 20 if rows0 == 1 else 256 * (rows0 - 1) + 1
-    return [Prob(fmt, M0, 2040, K, store, seed + 1), Prob(fmt, 2303, 776, K, "lora", seed + 2), Prob(fmt, 1055, 264, K, "f32", seed + 3),
-            Prob(fmt, 641, 64, K, "res", seed + 4, rpb=100)]
+    return [Prob(fmt, M0, 2040, K, store, seed + 1), Prob(fmt, 2303, 776, K, "lora", seed + 2, **lora), Prob(fmt, 1055, 264, K, "f32", seed + 3),
+            Prob(fmt, 641, 64, K, "res", seed + 4, rpb=100, lora=lora_p3, **(lora if lora_p3 else {}))]
 
 
 def tiles256(probs):
@@ -326,23 +361,29 @@ def tiles256(probs):
 SLICES = [(100, None), (1000, None), (520, 1000), (300, None)]      # per problem of group(): r0 % 32 != 0 (p3: whole batches)
 
 
+def descs_of(ops, probs, bufs):
+    return [p.desc(ops, b.buf[b.blocks[0][0]:b.blocks[0][0] + p.M, :b.buf.shape[1]] if p.epi == "pair" else
+                   b.buf[b.blocks[0][0]:b.blocks[0][0] + p.M, :p.N]) for p, b in zip(probs, bufs)]
+
+
 def run(ops, probs, ws, plan, arm, bufs=None, check=True):
     """Launch the problems (each in its own sentinel buffer unless given) twice; check plan, footprint, tiles and run-to-run bits.
+    plan: the plan the planner must choose, or a tuple of them where the choice between the two 8-wave tile heights is the planner's.
     Returns the buffers (contents of the first run)."""
     if bufs is None:
         bufs = [p.own_buf() for p in probs]
     for p in probs:
         if p.fmt == "f16":
             p.ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    descs = [p.desc(ops, b.buf[b.blocks[0][0]:b.blocks[0][0] + p.M, :b.buf.shape[1]] if p.epi == "pair" else
-                     b.buf[b.blocks[0][0]:b.blocks[0][0] + p.M, :p.N]) for p, b in zip(probs, bufs)]
+    descs = descs_of(ops, probs, bufs)
     first = None
     for rep in range(2):
         for b in {id(b): b for b in bufs}.values():
             b.reset()
         ops.gemm(descs, ws)
         got = ops.gemm_last_plan()
-        assert got == plan, f"{arm}: the planner chose plan {got}, not {plan} ({tiles256(probs)} tiles of 256 x 256, {ncu()} CUs)"
+        assert got in (plan if isinstance(plan, tuple) else (plan,)), \
+            f"{arm}: the planner chose plan {got}, not {plan} ({tiles256(probs)} tiles of 256 x 256, {ncu()} CUs)"
         if ws is not None:
             assert ops.lib.lx_gemm_workspace_status(ws.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
         torch.cuda.synchronize()
@@ -350,11 +391,13 @@ def run(ops, probs, ws, plan, arm, bufs=None, check=True):
             first = [b.buf.clone() for b in bufs]
     for b, f in zip(bufs, first):
         assert torch.equal(b.buf.view(b.iv), f.view(b.iv)), f"{arm}: two runs of the same launch differ"
+    for p in probs:
+        p.check_inputs(arm)
     if check:
         for b in {id(b): b for b in bufs}.values():
             b.check_footprint(arm)
         for p, b in zip(probs, bufs):
-            p.check(b, b.blocks[0][0], arm, plan)
+            p.check(b, b.blocks[0][0], arm, got)
             if p.ovf is not None:
                 assert int(p.ovf) == 0
     return bufs
@@ -441,9 +484,9 @@ def test_gemm_tiles_16bit_operands(ops, monkeypatch, fmt, arm):
         run(ops, small, ws, _p(plan), arm + "/small")
 
 
-def _no_ws_bits(ops, monkeypatch, fmt, K, arms):
+def _no_ws_bits(ops, monkeypatch, fmt, K, arms, **lora):
     """The no-workspace plans agree bit for bit: each arm's group launch, each problem launched alone, and a row slice of each."""
-    probs = group(fmt, K, main_rows0(), seed=40)
+    probs = group(fmt, K, main_rows0(), seed=40, **lora)
     res = {}
     for arm, env, plan in arms:
         set_env(ops, monkeypatch, env)
@@ -468,6 +511,7 @@ def _no_ws_bits(ops, monkeypatch, fmt, K, arms):
         assert ops.gemm_last_plan() in no_ws
         torch.cuda.synchronize()
         s.check_footprint(f"{fmt} p{i} rows [{r0}, {r1})")
+        p.check_inputs(f"{fmt} p{i} alone / rows [{r0}, {r1})")
         p.check(s, PAD, "slice", ops.gemm_last_plan(), r0, r1)
         sl = s.buf[PAD:PAD + r1 - r0, :p.ldc()]
         iv = IVIEW[alone.dtype]
@@ -529,20 +573,25 @@ def test_gemm_tiles_split_bf16(ops, monkeypatch, segs, arm):
 # ------------------------------------------------------------------------------------------------ the mixed plan's peel
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_gemm_mixed_plan_peel_into_a_shared_buffer(ops, monkeypatch, fmt):
+    peel_into_a_shared_buffer(ops, monkeypatch, fmt)
+
+
+def peel_into_a_shared_buffer(ops, monkeypatch, fmt, **lora):
     """Four gated-residual problems with LoRA in ONE fp32 buffer (GAP sentinel rows between them), NCU + 11 tiles: the mixed plan peels
     q3 (641 rows) entirely and q2's last two tile rows (287 of 1055 rows) into its 128-row tail, so q2's tail starts at m_base = 768,
     inside batch 7 of 100-row batches -- the gate's batch index and the LoRA rows there come from m_base. Against float64 tile by tile,
-    the footprint, and bit for bit against the 8-wave plans and each problem alone."""
+    the footprint, and bit for bit against the 8-wave plans and each problem alone. lora = the adapter inputs of all four (Prob.set_lora).
+    Returns the problems and the shared buffer's contents."""
     n = ncu()
     r1 = next((r for r in range(6, 10) if (n - 12 - 2 * r) % 8 == 0 and n - 12 - 2 * r > 0), None)
     if r1 is None:
         pytest.skip(f"no peel shape for {n} CUs")
     K = 128
     rows0 = (n - 12 - 2 * r1) // 8
-    probs = [Prob(fmt, 256 * (rows0 - 1) + 255, 2040, K, "res", 81, rpb=700, lora=True),
-             Prob(fmt, 256 * (r1 - 1) + 129, 264, K, "res", 82, rpb=300, lora=True),
-             Prob(fmt, 1055, 776, K, "res", 83, rpb=100, lora=True),
-             Prob(fmt, 641, 64, K, "res", 84, rpb=160, lora=True)]
+    probs = [Prob(fmt, 256 * (rows0 - 1) + 255, 2040, K, "res", 81, rpb=700, lora=True, **lora),
+             Prob(fmt, 256 * (r1 - 1) + 129, 264, K, "res", 82, rpb=300, lora=True, **lora),
+             Prob(fmt, 1055, 776, K, "res", 83, rpb=100, lora=True, **lora),
+             Prob(fmt, 641, 64, K, "res", 84, rpb=160, lora=True, **lora)]
     assert tiles256(probs) == n + 11
     rows = sum(p.M for p in probs) + GAP * (len(probs) + 1)
     b = Buf(torch.float32, rows, 2040 + XCOLS, resid=True)
@@ -575,3 +624,6 @@ def test_gemm_mixed_plan_peel_into_a_shared_buffer(ops, monkeypatch, fmt):
         torch.cuda.synchronize()
         r = v.blocks[0][0]
         assert torch.equal(a.buf[PAD:PAD + p.M, :p.N].view(torch.int32), out["mixed"][r:r + p.M, :p.N].view(torch.int32))
+        a.check_footprint("peel/alone")
+        p.check_inputs("peel/alone")
+    return probs, views, out["mixed"]
