@@ -957,8 +957,7 @@ class DiTEngine:
             m.single("attn", "cond", p + ".out", self.rows(self.X, "img"), bias=w.t[p + ".out.b"], epilogue=LX_EPI_RESID_F32,
                      rows_per_batch=self.C, gate=self.cmods[:, gate["cond"]:], **kw)
         ready = m.ln(base, 3 * D, 4 * D, lora_for=p + ".ff1")                               # norm2 + (scale_mlp, shift_mlp)
-        # known gap: the e4m3 ff1 launch evaluates no adapter term, though lora_layout lists d{i}.ff1
-        m.gemm("xn", "mlp", p + ".ff1", p + ".ff1_txt", lora=self.NO_LORA if self.gemm_fp8 else ready)
+        m.gemm("xn", "mlp", p + ".ff1", p + ".ff1_txt", lora=ready)                       # (ff.net.0.proj carries no adapter: the loaders refuse one)
         gate = {s: base[s] + 5 * D for s in base}
         m.gemm("mlp", "x", p + ".ff2", p + ".ff2_txt", gate_off=gate)
 
@@ -1186,9 +1185,13 @@ class DiTEngine:
                 continue
             vec = vec.to(device=self.device, dtype=torch.float32).contiguous()
             ops.linear_skinny(vec, w.t["mod.w"][base:base + width], w.t["mod.b"][base:base + width], out[:, base:], act_in=1)
+            if self.precise and "mod.w_lo" in w.t:          # the weights' rounding residual, as _compute_mods adds it
+                ops.linear_skinny(vec, w.t["mod.w_lo"][base:base + width], None, out[:, base:], act_in=1, accumulate=True)
             if lora and "mod.lora_down" in w.t and self.lora_scale != 0.0:
                 tm = self.tmod[:, :r]
                 ops.linear_skinny(vec, w.t["mod.lora_down"][li * r:(li + 1) * r], None, tm, act_in=1)
+                if self.precise and "mod.lora_down_lo" in w.t:
+                    ops.linear_skinny(vec, w.t["mod.lora_down_lo"][li * r:(li + 1) * r], None, tm, act_in=1, accumulate=True)
                 self._scale_lora(tm, [(0, self.B, 1)])
                 ops.linear_f32(tm, w.t[f"mod.lora_up.{li}"], None, out[:, base:], M=self.B, N=lw, K=r, ldx=tm.stride(0),
                                ldy=out.stride(0), accumulate=True)

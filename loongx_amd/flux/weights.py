@@ -207,6 +207,7 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: FluxConfig, device, lora_s
     precise=True keeps the bf16 rounding residual of every weight that has one (see PackedWeights)."""
     if prefix:
         sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    _refuse_unevaluated_lora(cfg, sd)
     pw = PackedWeights(cfg)
     pw.precise_ready = bool(precise)
     D = cfg.inner_dim
@@ -308,23 +309,50 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: FluxConfig, device, lora_s
 
 
 def lora_layout(cfg: FluxConfig):
-    """(fused name, [diffusers module names]) of every GEMM that may carry a LoRA adapter, and the per-block modulation
-    Linear names in packed order (mod.lora_down / mod.lora_up.<idx>) -- the same grouping pack_state_dict uses."""
+    """(fused name, [diffusers module names]) of every GEMM whose LoRA adapter the engine evaluates, and the per-block modulation
+    Linear names in packed order (mod.lora_down / mod.lora_up.<idx>) -- the same grouping pack_state_dict uses. These are the modules
+    the reference switches per stream (its enable_lora lists): on for the condition rows, on for the image rows (and the single blocks'
+    text rows) with model_config["latent_lora"]. Every other Linear is in unevaluated_lora_modules: the loaders refuse adapters there."""
     fused, mods = [], []
     for i in range(cfg.num_layers):
         p = f"transformer_blocks.{i}."
-        fused += [(f"d{i}.qkv", [p + "attn.to_k", p + "attn.to_v", p + "attn.to_q"]),
-                  (f"d{i}.qkv_txt", [p + "attn.add_k_proj", p + "attn.add_v_proj", p + "attn.add_q_proj"]),
-                  (f"d{i}.out", [p + "attn.to_out.0"]), (f"d{i}.out_txt", [p + "attn.to_add_out"]),
-                  (f"d{i}.ff1", [p + "ff.net.0.proj"]), (f"d{i}.ff1_txt", [p + "ff_context.net.0.proj"]),
-                  (f"d{i}.ff2", [p + "ff.net.2"]), (f"d{i}.ff2_txt", [p + "ff_context.net.2"])]
+        fused += [(f"d{i}.qkv", [p + "attn.to_k", p + "attn.to_v", p + "attn.to_q"]), (f"d{i}.out", [p + "attn.to_out.0"]),
+                  (f"d{i}.ff2", [p + "ff.net.2"])]
         mods.append(p + "norm1.linear")
     for j in range(cfg.num_single_layers):
         p = f"single_transformer_blocks.{j}."
         fused += [(f"s{j}.fused", [p + "attn.to_k", p + "attn.to_v", p + "attn.to_q", p + "proj_mlp"]), (f"s{j}.out", [p + "proj_out"])]
         mods.append(p + "norm.linear")
-    fused += [("x_embedder", ["x_embedder"]), ("context_embedder", ["context_embedder"]), ("proj_out", ["proj_out"])]
+    fused += [("x_embedder", ["x_embedder"])]
     return fused, mods
+
+
+def unevaluated_lora_modules(cfg: FluxConfig) -> List[str]:
+    """The Linears of the transformer that are in none of the reference's enable_lora lists: an adapter there is on for every row that
+    passes through the module (text rows, the image rows without latent_lora), which the engine's one row rule (engine._lora_rows) cannot
+    express. The engine evaluates no adapter on them, so the loaders refuse a checkpoint that carries one (_refuse_unevaluated_lora)."""
+    out = []
+    for i in range(cfg.num_layers):
+        p = f"transformer_blocks.{i}."
+        out += [p + n for n in ("attn.add_k_proj", "attn.add_v_proj", "attn.add_q_proj", "attn.to_add_out", "ff.net.0.proj",
+                                "ff_context.net.0.proj", "ff_context.net.2", "norm1_context.linear")]
+    out += ["context_embedder", "proj_out", "norm_out.linear"]
+    out += [f"time_text_embed.{e}.{l}" for e in ("timestep_embedder", "text_embedder", "guidance_embedder") for l in ("linear_1", "linear_2")]
+    return out
+
+
+_LORA_KEY = re.compile(r"^(.+)\.lora_[AB](?:\.[^.]+)?\.weight$")
+
+
+def _refuse_unevaluated_lora(cfg: FluxConfig, keys) -> None:
+    """The one accepted-module rule of both loaders (pack_state_dict, install_lora), applied before either changes anything: `keys` are
+    state-dict keys without the transformer prefix. One ValueError that lists every offending module."""
+    carried = {m.group(1) for m in map(_LORA_KEY.match, keys) if m}
+    bad = [n for n in unevaluated_lora_modules(cfg) if n in carried]
+    if bad:
+        raise ValueError(f"LoRA adapters on modules the engine does not evaluate: {', '.join(bad)}. Accepted are the modules the reference "
+                         "switches per stream: x_embedder; per double block attn.to_q/k/v, attn.to_out.0, ff.net.2, norm1.linear; per "
+                         "single block attn.to_q/k/v, proj_mlp, proj_out, norm.linear")
 
 
 def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale: float = 1.0, prefix: str = "transformer.",
@@ -336,12 +364,14 @@ def install_lora(pw: PackedWeights, lora_sd: Dict[str, torch.Tensor], lora_scale
     evaluate together (q/k/v[/proj_mlp] of one block) must be given for all of them or none.
     adapter_name = None: replace every adapter by this one, named "default" and active. With a name: add (or replace) that entry of the
     registry and leave the others alone; it becomes active only if nothing was (set_active_adapters selects). One rank per adapter;
-    different adapters may differ. A call that raises leaves the model as it was."""
+    different adapters may differ. Adapters on a module outside lora_layout (unevaluated_lora_modules) are refused with a ValueError
+    that lists them. A call that raises leaves the model as it was."""
     sd = {}
     for k, v in lora_sd.items():
         if prefix and k.startswith(prefix):
             k = k[len(prefix):]
         sd[re.sub(r"\.lora_([AB])\.[^.]+\.weight$", r".lora_\1.weight", k)] = v
+    _refuse_unevaluated_lora(pw.cfg, sd)
     dev = pw.t["mod.w"].device
     used = set()
 

@@ -135,7 +135,7 @@ def block_forward(block, hidden_states, encoder_hidden_states, condition_latents
     ll = bool(model_config.get("latent_lora", False))
     use_cond = condition_latents is not None
     nh, g_a, sh_m, sc_m, g_m = _ada_zero(block.norm1, hidden_states, temb, ll)
-    ne, cg_a, csh_m, csc_m, cg_m = _ada_zero(block.norm1_context, encoder_hidden_states, temb, False)
+    ne, cg_a, csh_m, csc_m, cg_m = _ada_zero(block.norm1_context, encoder_hidden_states, temb, True)    # (in no enable_lora list: an adapter there is always on)
     nc = None
     if use_cond:
         nc, kg_a, ksh_m, ksc_m, kg_m = _ada_zero(block.norm1, condition_latents, cond_temb, True)
@@ -151,7 +151,7 @@ def block_forward(block, hidden_states, encoder_hidden_states, condition_latents
     nh = block.norm2(hidden_states) * (1 + sc_m[:, None]) + sh_m[:, None]
     ne = block.norm2_context(encoder_hidden_states) * (1 + csc_m[:, None]) + csh_m[:, None]
     hidden_states = hidden_states + g_m[:, None] * _ff(block.ff, nh, ll)
-    encoder_hidden_states = encoder_hidden_states + cg_m[:, None] * _ff(block.ff_context, ne, False)
+    encoder_hidden_states = encoder_hidden_states + cg_m[:, None] * _ff(block.ff_context, ne, True)
     if use_cond:
         nc = block.norm2(condition_latents) * (1 + ksc_m[:, None]) + ksh_m[:, None]
         condition_latents = condition_latents + kg_m[:, None] * _ff(block.ff, nc, True)
