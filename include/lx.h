@@ -330,6 +330,21 @@ int lx_qkv_prep_kv_f16in_segs(void* QKV, int ld, int q_col, int k_col, int v_col
  *   at VT positions seg_vt0[s].. (64-aligned, zero padded).
  *   bias[3][3]: additive score bias (natural-log units) for (query segment, key segment); -INFINITY masks
  *   the pair entirely; NULL => all zero.  scale = 1/sqrt(dh).
+ *   What every entry point that launches on this descriptor (lx_attn_fwd, lx_attn_fwd_fp8, lx_attn_fwd_split,
+ *   lx_attn_fwd_masked) checks, with one routine and the same messages under its own name; a violation is
+ *   LX_ERR_INVALID before anything is launched:
+ *     Q, K, VT, O non-NULL; n_seg 1..3; B, H >= 1; every seg_len >= 1;
+ *     ldq, ldk, q_col, k_col multiples of 16 bytes (8 elements; 16 for the e4m3 operands of lx_attn_fwd_fp8),
+ *     ldo, o_col multiples of 4, vt_ld a multiple of 64;
+ *     n_qseg in 0..n_seg, qseg_mask in 0..2^n_seg - 1;
+ *     seg_vt0[s] >= 0, a multiple of 64, and seg_vt0[s] + seg_len[s] rounded up to 64 <= vt_ld: the kernels stage
+ *     whole 64-key tiles of K (from the segment's last row past its end) and of V^T, which must lie inside a V^T row;
+ *     a segment without queries (n_qseg / qseg_mask) shares no row [seg_row0, seg_row0 + B*seg_len) of O with a
+ *     segment that has them: its rows are promised untouched;
+ *     every query segment attends to at least one key segment (a bias row of -INFINITY only is refused) -- except in
+ *     lx_attn_fwd_masked, where a mask can empty a row anyway and such rows are written as zeros.
+ *   The flag bits and their combinations are each entry point's own (below). lx_attn_mask_workspace and
+ *   lx_attn_mask_prep read n_seg, B, H, seg_len and seg_vt0 only and check those.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct lx_attn_desc {
   const void* Q; const void* K; const void* VT; void* O;

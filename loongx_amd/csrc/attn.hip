@@ -924,47 +924,77 @@ __global__ __launch_bounds__(512, 1) void lx_attn_fp8_pipe_kernel(const AttnArgs
 
 }  // namespace
 
-// 16-byte epilogue stores need 16-byte aligned output rows and head columns
-static int lx_attn_wide_store(const lx_attn_desc* d) { return d->ldo % 8 == 0 && d->o_col % 8 == 0 && ((uintptr_t)d->O & 15) == 0; }
-
-// which segments have queries: qseg_mask when given, else the first n_qseg (0: all)
-static int lx_attn_qmask(const lx_attn_desc* d) {
-  if (d->qseg_mask != 0) return d->qseg_mask;
-  const int nq = d->n_qseg > 0 ? d->n_qseg : d->n_seg;
-  return (1 << nq) - 1;
+// The one place an lx_attn_desc is checked (attn_common.h says what `operands` and `rules` select). Order: operands, n_seg, B / H,
+// alignment, the query-segment set, then each segment, then the pairs of segments.
+int lx_attn_plan(const char* who, const lx_attn_desc* d, int operands, int rules, AttnPlan& p) {
+  const bool launch = operands != LX_ATTN_SEGMENTS_ONLY;
+  LX_CHECK_ARG(d && (!launch || (d->Q && d->K && d->VT && d->O)), "%s: NULL operand", who);
+  LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "%s: n_seg=%d must be 1..3", who, d->n_seg);
+  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "%s: bad B/H", who);
+  p.qmask = (1 << d->n_seg) - 1;
+  if (launch) {
+    const int al = operands == LX_ATTN_OPERANDS_E4M3 ? 16 : 8;   // 16 bytes of the operand format
+    if (al == 16) LX_CHECK_ARG(d->ldq % 16 == 0 && d->ldk % 16 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "%s: ldq/ldk %% 16 (bytes), ldo %% 4, vt_ld %% 64 required", who);
+    else LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "%s: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required", who);
+    LX_CHECK_ARG(d->q_col % al == 0 && d->k_col % al == 0 && d->o_col % 4 == 0, "%s: column offsets must be 16-byte aligned", who);
+    LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "%s: n_qseg=%d must be 0..n_seg", who, d->n_qseg);
+    LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "%s: qseg_mask=%d names a segment >= n_seg", who, d->qseg_mask);
+    // which segments have queries: qseg_mask when given, else the first n_qseg (0: all)
+    if (d->qseg_mask != 0) p.qmask = d->qseg_mask;
+    else if (d->n_qseg > 0) p.qmask = (1 << d->n_qseg) - 1;
+  }
+  // 16-byte epilogue stores need 16-byte aligned output rows and head columns
+  p.wide_store = launch && d->ldo % 8 == 0 && d->o_col % 8 == 0 && ((uintptr_t)d->O & 15) == 0;
+  int qt = 0, qq = 0, kt = 0;
+  for (int s = 0; s < 3; ++s) {
+    p.qt_start[s] = qt;
+    p.qq_start[s] = qq;
+    p.kt_start[s] = kt;
+    if (s >= d->n_seg) continue;
+    LX_CHECK_ARG(d->seg_len[s] >= 1, "%s: empty segment %d", who, s);
+    // the K / V^T staging reads whole 64-key tiles from seg_vt0[s] on: they have to lie inside a V^T row
+    LX_CHECK_ARG(d->seg_vt0[s] % 64 == 0 && d->seg_vt0[s] >= 0, "%s: seg_vt0 must be 64-aligned", who);
+    const int q_tiles = (d->seg_len[s] + 255) / 256, k_tiles = (d->seg_len[s] + KVBLK - 1) / KVBLK;
+    const long long vt_end = (long long)d->seg_vt0[s] + (long long)k_tiles * KVBLK;
+    LX_CHECK_ARG(!launch || vt_end <= d->vt_ld, "%s: segment %d's V^T tiles end at %lld > vt_ld=%d", who, s, vt_end, d->vt_ld);
+    qt += q_tiles;
+    kt += k_tiles;
+    if ((p.qmask >> s) & 1) qq += q_tiles;
+  }
+  p.qt_start[3] = qt;
+  p.qq_start[3] = qq;
+  p.kt_start[3] = kt;
+  p.items = qq * d->B * d->H;
+  if (!launch) return LX_OK;
+  // "the rows of O of a segment without queries are not written" can only hold if no query segment's rows [seg_row0, + B * seg_len) share them
+  for (int s = 0; s < d->n_seg; ++s)
+    for (int q = 0; q < d->n_seg; ++q) {
+      if (((p.qmask >> s) & 1) || !((p.qmask >> q) & 1)) continue;
+      const long long s0 = d->seg_row0[s], s1 = s0 + (long long)d->B * d->seg_len[s], q0 = d->seg_row0[q], q1 = q0 + (long long)d->B * d->seg_len[q];
+      LX_CHECK_ARG(s1 <= q0 || q1 <= s0, "%s: n_qseg / qseg_mask leave segment %d without queries, but its rows [%lld, %lld) of O overlap "
+                   "query segment %d's rows [%lld, %lld)", who, s, s0, s1, q, q0, q1);
+    }
+  if (rules & LX_ATTN_RULE_QUERY_HAS_KEYS)
+    for (int s = 0; s < d->n_seg; ++s) {
+      bool any = !((p.qmask >> s) & 1);          // a segment without queries (n_qseg / qseg_mask): keys / values only
+      for (int k = 0; k < d->n_seg; ++k) any |= d->bias[s][k] > -1e37f;
+      LX_CHECK_ARG(any, "%s: query segment %d is masked from every key segment", who, s);
+    }
+  return LX_OK;
 }
 
 static thread_local int lx_attn_last = LX_ATTN_KERNEL_NONE;
 extern "C" int lx_attn_last_kernel(void) { return lx_attn_last; }
 
 extern "C" int lx_attn_fwd(const lx_attn_desc* d, void* stream) {
-  LX_CHECK_ARG(d && d->Q && d->K && d->VT && d->O, "lx_attn_fwd: NULL operand");
-  LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "lx_attn_fwd: n_seg=%d must be 1..3", d->n_seg);
-  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "lx_attn_fwd: bad B/H");
-  LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required");
-  LX_CHECK_ARG(d->q_col % 8 == 0 && d->k_col % 8 == 0 && d->o_col % 4 == 0, "lx_attn_fwd: column offsets must be 16-byte aligned");
-  const int qblk = 256;                        // query rows per workgroup (8 waves x 32 / 4 waves x 64)
-  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd: n_qseg=%d must be 0..n_seg", d->n_qseg);
-  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
-  const int qmask = lx_attn_qmask(d);
+  AttnPlan p;
+  const int rc = lx_attn_plan("lx_attn_fwd", d, LX_ATTN_OPERANDS_16BIT, LX_ATTN_RULE_QUERY_HAS_KEYS, p);
+  if (rc != LX_OK) return rc;
+  const int qmask = p.qmask, grid = p.items;
   AttnArgs a;
   a.d = *d;
-  a.wide_store = lx_attn_wide_store(d);
-  int t = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.qt_start[s] = t;
-    if (s < d->n_seg) {
-      LX_CHECK_ARG(d->seg_len[s] >= 1, "lx_attn_fwd: empty segment %d", s);
-      LX_CHECK_ARG(d->seg_vt0[s] % 64 == 0, "lx_attn_fwd: seg_vt0 must be 64-aligned");
-      bool any = false;
-      for (int k = 0; k < d->n_seg; ++k) any |= d->bias[s][k] > -1e37f;
-      if (!((qmask >> s) & 1)) continue;     // a segment without queries (n_qseg / qseg_mask): keys / values only
-      LX_CHECK_ARG(any, "lx_attn_fwd: query segment %d is masked from every key segment", s);
-      t += (d->seg_len[s] + qblk - 1) / qblk;
-    }
-  }
-  a.qt_start[3] = t;
-  const int grid = t * d->B * d->H;
+  for (int s = 0; s < 4; ++s) a.qt_start[s] = p.qq_start[s];
+  a.wide_store = p.wide_store;
   hipStream_t st = (hipStream_t)stream;
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_Q_LOG2 | LX_ATTN_BOUNDED | LX_ATTN_INVARIANT | LX_ATTN_O_F16 | LX_ATTN_PREFER_4WAVE)) == 0 &&
                    (!(d->flags & LX_ATTN_BOUNDED) || (d->flags & LX_ATTN_Q_LOG2)) && !((d->flags & LX_ATTN_INVARIANT) && (d->flags & LX_ATTN_PREFER_4WAVE)),
@@ -1008,34 +1038,16 @@ extern "C" int lx_attn_fwd(const lx_attn_desc* d, void* stream) {
 }
 
 extern "C" int lx_attn_fwd_fp8(const lx_attn_desc* d, float qk_descale, float v_descale, void* stream) {
-  LX_CHECK_ARG(d && d->Q && d->K && d->VT && d->O, "lx_attn_fwd_fp8: NULL operand");
-  LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "lx_attn_fwd_fp8: n_seg=%d must be 1..3", d->n_seg);
-  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "lx_attn_fwd_fp8: bad B/H");
-  LX_CHECK_ARG(d->ldq % 16 == 0 && d->ldk % 16 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd_fp8: ldq/ldk %% 16 (bytes), ldo %% 4, vt_ld %% 64 required");
-  LX_CHECK_ARG(d->q_col % 16 == 0 && d->k_col % 16 == 0 && d->o_col % 4 == 0, "lx_attn_fwd_fp8: column offsets must be 16-byte aligned");
+  AttnPlan p;
+  const int rc = lx_attn_plan("lx_attn_fwd_fp8", d, LX_ATTN_OPERANDS_E4M3, LX_ATTN_RULE_QUERY_HAS_KEYS, p);
+  if (rc != LX_OK) return rc;
   LX_CHECK_ARG(qk_descale > 0.f && v_descale > 0.f, "lx_attn_fwd_fp8: descale factors must be positive");
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_O_F16 | LX_ATTN_P_EXP2)) == 0, "lx_attn_fwd_fp8: the flags are LX_ATTN_O_F16 and LX_ATTN_P_EXP2 (the e4m3 kernels fold their own scales)");
-  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd_fp8: n_qseg=%d must be 0..n_seg", d->n_qseg);
-  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd_fp8: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
-  const int qmask = lx_attn_qmask(d);
   AttnArgs a;
   a.d = *d;
-  a.wide_store = lx_attn_wide_store(d);
-  int t = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.qt_start[s] = t;
-    if (s < d->n_seg) {
-      LX_CHECK_ARG(d->seg_len[s] >= 1, "lx_attn_fwd_fp8: empty segment %d", s);
-      LX_CHECK_ARG(d->seg_vt0[s] % 64 == 0, "lx_attn_fwd_fp8: seg_vt0 must be 64-aligned");
-      bool any = false;
-      for (int k = 0; k < d->n_seg; ++k) any |= d->bias[s][k] > -1e37f;
-      if (!((qmask >> s) & 1)) continue;
-      LX_CHECK_ARG(any, "lx_attn_fwd_fp8: query segment %d is masked from every key segment", s);
-      t += (d->seg_len[s] + 255) / 256;
-    }
-  }
-  a.qt_start[3] = t;
-  const int grid = t * d->B * d->H;
+  for (int s = 0; s < 4; ++s) a.qt_start[s] = p.qq_start[s];
+  a.wide_store = p.wide_store;
+  const int grid = p.items;
   // softmax scale x log2(e) x operand descale an exact power of two 2^-k (ops.py chooses the q scale so)? Then the score MFMAs
   // apply it as an MX block scale and the scores come out as exp2 arguments (lx_attn_fp8_pipe_kernel, POW2); any other combination of
   // scales runs the generic form (one fma per score)

@@ -1,5 +1,6 @@
 // attn_common.h -- what the attention translation units (attn.hip: the 8-wave kernels; attn4.hip: the one-wave-per-SIMD kernel) share:
-// the launch argument block, the K / V^T tile geometry and the row-per-lane epilogue store.
+// the launch argument block, the K / V^T tile geometry and the row-per-lane epilogue store; with attn_mask.hip and precise.hip, the
+// lx_attn_desc validator (lx_attn_plan) and the parts of the plain 8-wave tile loop.
 #pragma once
 #include "common.h"
 
@@ -86,7 +87,8 @@ __device__ __forceinline__ uint32_t lx_pack_o(float lo, float hi, bool f16, floa
 // (the swap inside exchanges data between the two half-waves of a row: both halves of a row must be valid or invalid together; `valid`
 //  guards the stores of rows past the segment.) `mode` = lx_o_mode(args): bit 0 wide stores, bit 1 fp16 output; `ovf` = the overflow
 //  word. Both are VALUES the kernel computes once, up front: no kernel-argument load inside lx_attn4_kernel's item loop.
-__device__ __forceinline__ int lx_o_mode(const AttnArgs& args) { return (args.wide_store != 0 ? 1 : 0) | ((args.d.flags & LX_ATTN_O_F16) ? 2 : 0); }
+template <class Args>   // AttnArgs, or attn_mask.hip's block: both carry wide_store and the descriptor
+__device__ __forceinline__ int lx_o_mode(const Args& args) { return (args.wide_store != 0 ? 1 : 0) | ((args.d.flags & LX_ATTN_O_F16) ? 2 : 0); }
 __device__ __forceinline__ void lx_store_o(int mode, int* ovf, bool valid, uint16_t* row, const f32x16 (&oacc)[4], float inv, int lhi) {
   float mx = 0.f;
   const bool f16 = (mode & 2) != 0;
@@ -120,7 +122,73 @@ __device__ __forceinline__ void lx_store_o(int mode, int* ovf, bool valid, uint1
   if (f16) report_f16_overflow(mx, ovf);
 }
 
+// ---- the parts of the plain 8-wave tile loop that lx_attn_mask_kernel and attn_split_kernel share ---------------------
+// One workgroup = 8 waves x 32 query rows; a K tile is [64 keys][128] and a V^T tile [128][64 keys] of 16-bit elements per operand image,
+// 16-byte slots XOR-swizzled by the row. Both kernels sit at the register limit and hipcc's allocation of them moves with the smallest
+// change of the text it is given, so a part lives here only where BOTH kernels' instruction streams stayed identical with it
+// (tools/README.md, "kernel streams"; profiles/attn_plain_shared.txt). Parts that changed a stream as a function, in every form tried,
+// and so stay as text in the kernels: the K / V^T staging lambda (lx_attn_mask_kernel 240 -> 242 VGPRs, <true> 8 bytes of scratch), the
+// ragged-tile key mask (244 VGPRs / 20 bytes of scratch there, another allocation in attn_split_kernel), the alpha rescale of O and l
+// (commuted multiplies), and in attn_split_kernel alone the query-segment lookup and the zeroing of O. Compare streams before moving one.
+
+// the last segment whose range of a tile prefix starts at or before t (an empty range is never chosen)
+__device__ __forceinline__ int lx_seg_of(int t, const int (&start)[4], int n_seg) {
+  int s = 0;
+  if (n_seg > 1 && t >= start[1]) s = 1;
+  if (n_seg > 2 && t >= start[2]) s = 2;
+  return s;
+}
+
+// byte offset of a lane's MFMA fragment within a staged image (the read side of the staging swizzle). K: row kb*32 + l31 at k-step ks, with
+// k_row_off = l31 * 256 and ksw = l31 & 15; V^T: row db*32 + l31 at key step s, with v_row_off = the image's offset + l31 * 128 and
+// vsw = (l31 >> 1) & 7. (The lane's row terms are arguments: computed inside, attn_split_kernel's stream changed.)
+__device__ __forceinline__ int lx_k_frag_off(int kb, int ks, int lhi, int k_row_off, int ksw) { return kb * 32 * 256 + k_row_off + (((ks * 2 + lhi) ^ ksw) * 16); }
+__device__ __forceinline__ int lx_v_frag_off(int db, int s, int lhi, int v_row_off, int vsw) { return v_row_off + db * 32 * 128 + (((s * 2 + lhi) ^ vsw) * 16); }
+
+// the maximum of a query row's 64 scores: the lane's 32, then the other half-wave's
+__device__ __forceinline__ float lx_tile_max(const f32x16 (&sacc)[2]) {
+  float tmax = fmaxf(sacc[0][0], sacc[0][1]);
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = (kb == 0 ? 2 : 0); r < 16; r += 2) tmax = fmaxf(fmaxf(tmax, sacc[kb][r]), sacc[kb][r + 1]);
+  return fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+}
+
+template <int N>
+__device__ __forceinline__ void lx_zero_acc(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
 }  // namespace
+
+// ---- lx_attn_desc -> a launch: the one validator of the entry points that take the descriptor (attn.hip defines it) ------------------
+// What the kernels assume and only the host can say: every segment's 64-key tiles lie inside a V^T row (seg_vt0 >= 0, a multiple of 64,
+// tiles ending at or before vt_ld) -- the staging reads whole tiles; a segment without queries shares no row of O with a segment that
+// has them. Every message starts with `who`, the entry point's name. The flag bits stay with the entry points: each has its own set, its
+// own combination rules and its own wording for them.
+enum LxAttnOperands {
+  LX_ATTN_SEGMENTS_ONLY,     // lx_attn_mask_workspace / _prep: n_seg, B / H, segment lengths and seg_vt0 only (no operands, no vt_ld, no query subset)
+  LX_ATTN_OPERANDS_16BIT,    // ldq / ldk / q_col / k_col in 16-bit elements: multiples of 8
+  LX_ATTN_OPERANDS_E4M3      // ... in bytes: multiples of 16
+};
+enum LxAttnRules {
+  // "query segment s is masked from every key segment" (its softmax would be over nothing). lx_attn_fwd_masked does not ask for it: a mask
+  // can empty any row anyway, and such rows are written as zeros.
+  LX_ATTN_RULE_QUERY_HAS_KEYS = 1
+};
+struct AttnPlan {
+  int qmask;          // the segments that have queries: qseg_mask when given, else the first n_qseg (0: all)
+  int qt_start[4];    // prefix of 256-row query tiles over ALL segments
+  int qq_start[4];    // ... over the segments that have queries only: the launch's items per (batch, head)
+  int kt_start[4];    // prefix of 64-key tiles (the padded V^T layout, compacted over the segments)
+  int wide_store;     // O rows and head columns are 16-byte aligned (lx_store_o's 16-byte stores)
+  int items;          // qq_start[3] * B * H workgroups
+};
+int lx_attn_plan(const char* who, const lx_attn_desc* d, int operands, int rules, AttnPlan& p);
 
 // attn4.hip: launches lx_attn4_kernel (one wave per SIMD; bounded-score contract only) on a validated AttnArgs block (256-row query tiles)
 int lx_attn4_launch(const void* attn_args, int n_items, int mode, void* stream);

@@ -27,7 +27,7 @@ constexpr float MASKED = -3.0e30f;         // score (log2 units) of a masked pai
 constexpr float ATT_MIN = -1.0e30f;
 enum { CLS_EMPTY = 0, CLS_FULL = 1, CLS_PARTIAL = 2 };
 
-struct MaskGeom {
+struct MaskGeom {              // what the two passes key the workspace by; qt_start / kt_start are the AttnPlan's (lx_mask_geom)
   int n_seg;
   int seg_len[3];
   int qt_start[4];            // prefix of 256-row query tiles per segment
@@ -48,20 +48,13 @@ struct PrepArgs {
   void* data;
 };
 
-__device__ __forceinline__ int seg_of(int t, const int (&start)[4], int n_seg) {
-  int s = 0;
-  if (n_seg > 1 && t >= start[1]) s = 1;
-  if (n_seg > 2 && t >= start[2]) s = 2;
-  return s;
-}
-
 // one workgroup per tile: 4 waves x 64 rows each, lane = position p of the row (key lx_vt8_key(p))
 template <bool FLOAT>
 __global__ __launch_bounds__(256) void lx_attn_mask_prep_kernel(const PrepArgs a) {
   const MaskGeom& g = a.g;
   const int kt = blockIdx.x, qt = blockIdx.y, plane = blockIdx.z;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sq = seg_of(qt, g.qt_start, g.n_seg), sk = seg_of(kt, g.kt_start, g.n_seg);
+  const int sq = lx_seg_of(qt, g.qt_start, g.n_seg), sk = lx_seg_of(kt, g.kt_start, g.n_seg);
   const int q0 = (qt - g.qt_start[sq]) * MQBLK, k_in = (kt - g.kt_start[sk]) * KVBLK + lx_vt8_key(lane);
   const int lq = g.seg_len[sq], lk = g.seg_len[sk];
   const bool pair_on = a.bias[sq][sk] > -1e37f;
@@ -121,8 +114,6 @@ struct MaskAttnArgs {
   const void* data;
 };
 
-typedef const __attribute__((address_space(1))) void* mk_gptr_t;
-
 template <bool FLOAT>
 __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs args) {
   constexpr int NW = 8;
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
   int qc, bh;
   lx_item_decode((int)blockIdx.x, (int)gridDim.x, BH, args.qq_start[3], qc, bh);
   const int b = bh / D.H, h = bh % D.H;
-  const int sq = seg_of(qc, args.qq_start, G.n_seg);
+  const int sq = lx_seg_of(qc, args.qq_start, G.n_seg);
   const int qt = G.qt_start[sq] + (qc - args.qq_start[sq]);
   const int q_len = D.seg_len[sq];
   const int q_in_seg = (qt - G.qt_start[sq]) * MQBLK + wave * 32 + l31;
@@ -158,10 +149,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
   }
   const float c2 = (D.flags & LX_ATTN_Q_LOG2) ? 1.0f : D.scale * LX_LOG2E;
   f32x16 oacc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
+  lx_zero_acc(oacc);
   float m_run = MASKED, l_run = 0.f;
   bool any = false;                      // this lane's half of the row attended to some key
 
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
     const int e = lst[1 + i];
     kt = min(max(e & 0xffff, 0), G.n_kt - 1);
     cls = e >> 16;
-    sk = seg_of(kt, G.kt_start, G.n_seg);
+    sk = lx_seg_of(kt, G.kt_start, G.n_seg);
     ktl = kt - G.kt_start[sk];
   };
   // K: one instruction = 4 key rows of 256 B (lane -> row lane>>4, 16-B slot lane&15, slot ^= key&15); V^T: 8 d rows of 128 B (lane -> row
@@ -186,7 +174,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
       const int lslot = (lane & 15) ^ (key & 15);
       const int kin = min(ktl * KVBLK + key, klen - 1);
       const __bf16* src = Kbase + (krow0 + kin) * D.ldk + lslot * 8;
-      __builtin_amdgcn_global_load_lds((mk_gptr_t)src, (lptr_t)(base + (j * NW + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + (j * NW + wave) * 1024), 16, 0, 0);
     }
     const int vpos = D.seg_vt0[sk] + ktl * KVBLK;
 #pragma unroll
@@ -194,7 +182,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
       const int drow = (j * NW + wave) * 8 + (lane >> 3);
       const int lslot = (lane & 7) ^ ((drow >> 1) & 7);
       const __bf16* src = Vbase + (size_t)drow * D.vt_ld + vpos + lslot * 8;
-      __builtin_amdgcn_global_load_lds((mk_gptr_t)src, (lptr_t)(base + K_BYTES + (j * NW + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + K_BYTES + (j * NW + wave) * 1024), 16, 0, 0);
     }
   };
   const int ksw = l31 & 15, vsw = (l31 >> 1) & 7;
@@ -220,15 +208,12 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
     if (!FLOAT && cls == CLS_PARTIAL) mbits = ((const uint32_t*)args.data)[trow * 2 + lhi];
     const char* sb = smem + buf * STAGE_BYTES;
     f32x16 sacc[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
+    lx_zero_acc(sacc);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        const bf16x8 kf = *(const bf16x8*)(sb + kb * 32 * 256 + k_row_off + (((ks * 2 + lhi) ^ ksw) * 16));
+        const bf16x8 kf = *(const bf16x8*)(sb + lx_k_frag_off(kb, ks, lhi, k_row_off, ksw));
         sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kb], 0, 0, 0);
       }
     // scores -> exp2 arguments (log2 units); score (kb, r) of this lane is key kb*32 + 8*(r>>2) + 4*lhi + (r&3) of the tile
@@ -272,13 +257,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
       }
     }
     // online softmax, fp32, exact running maximum
-    float tmax = fmaxf(sacc[0][0], sacc[0][1]);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = (kb == 0 ? 2 : 0); r < 16; r += 2) tmax = fmaxf(fmaxf(tmax, sacc[kb][r]), sacc[kb][r + 1]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
+    const float m_new = fmaxf(m_run, lx_tile_max(sacc));
     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
     l_run *= alpha;
     m_run = m_new;
@@ -305,7 +284,7 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
       const bf16x8 pf = __builtin_bit_cast(bf16x8, w);
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        const bf16x8 vf = *(const bf16x8*)(sb + v_row_off + db * 32 * 128 + (((s * 2 + lhi) ^ vsw) * 16));
+        const bf16x8 vf = *(const bf16x8*)(sb + lx_v_frag_off(db, s, lhi, v_row_off, vsw));
         oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[db], 0, 0, 0);
       }
     }
@@ -313,47 +292,36 @@ __global__ __launch_bounds__(512, 1) void lx_attn_mask_kernel(const MaskAttnArgs
   }
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const bool any_row = (__shfl_xor((int)any, 32, 64) | (int)any) != 0;
-  if (!any_row) {                        // no key attended: SDPA's exact zeros (not the uniform average of V)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[j][r] = 0.f;
-  }
+  if (!any_row) lx_zero_acc(oacc);       // no key attended: SDPA's exact zeros (not the uniform average of V)
   const float inv = any_row && l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  const int mode = (args.wide_store ? 1 : 0) | ((D.flags & LX_ATTN_O_F16) ? 2 : 0);   // (lx_o_mode's encoding)
-  lx_store_o(mode, (int*)D.f16_ovf, q_valid, (uint16_t*)D.O + q_row * D.ldo + D.o_col + h * DH, oacc, inv, lhi);
+  lx_store_o(lx_o_mode(args), (int*)D.f16_ovf, q_valid, (uint16_t*)D.O + q_row * D.ldo + D.o_col + h * DH, oacc, inv, lhi);
 }
 
 }  // namespace
 
 static size_t lx_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// validation shared by the three entry points + the tile geometry and the workspace layout
-static int lx_mask_geom(const lx_attn_desc* d, const lx_attn_mask_desc* m, const char* who, MaskGeom& g) {
+// the three entry points' common start: the descriptor through lx_attn_plan (the attention launch with its operands, the other two
+// with the segment part only), then what is the mask's own -- dims, dtype, planes and the workspace layout. The tile prefixes are the plan's.
+static int lx_mask_geom(const lx_attn_desc* d, const lx_attn_mask_desc* m, const char* who, int operands, AttnPlan& p, MaskGeom& g) {
   LX_CHECK_ARG(d && m, "%s: NULL descriptor", who);
-  LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "%s: n_seg=%d must be 1..3", who, d->n_seg);
-  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "%s: bad B/H", who);
+  const int rc = lx_attn_plan(who, d, operands, 0, p);
+  if (rc != LX_OK) return rc;
   LX_CHECK_ARG(m->dtype >= LX_ATTN_MASK_BOOL && m->dtype <= LX_ATTN_MASK_F16, "%s: mask dtype=%d must be LX_ATTN_MASK_BOOL / F32 / BF16 / F16", who, m->dtype);
   g.n_seg = d->n_seg;
-  int S = 0, qt = 0, kt = 0;
+  int S = 0;
   for (int s = 0; s < 3; ++s) {
-    g.qt_start[s] = qt;
-    g.kt_start[s] = kt;
     g.lstart[s] = S;
     g.seg_len[s] = s < d->n_seg ? d->seg_len[s] : 0;
-    if (s < d->n_seg) {
-      LX_CHECK_ARG(d->seg_len[s] >= 1, "%s: empty segment %d", who, s);
-      LX_CHECK_ARG(d->seg_vt0[s] % 64 == 0 && d->seg_vt0[s] >= 0, "%s: seg_vt0 must be 64-aligned", who);
-      S += d->seg_len[s];
-      qt += (d->seg_len[s] + MQBLK - 1) / MQBLK;
-      kt += (d->seg_len[s] + KVBLK - 1) / KVBLK;
-    }
+    S += g.seg_len[s];
   }
-  g.qt_start[3] = qt;
-  g.kt_start[3] = kt;
-  g.n_qt = qt;
-  g.n_kt = kt;
-  LX_CHECK_ARG(kt < 65536, "%s: %d key tiles (at most 65535)", who, kt);
+  for (int s = 0; s < 4; ++s) {
+    g.qt_start[s] = p.qt_start[s];
+    g.kt_start[s] = p.kt_start[s];
+  }
+  g.n_qt = p.qt_start[3];
+  g.n_kt = p.kt_start[3];
+  LX_CHECK_ARG(g.n_kt < 65536, "%s: %d key tiles (at most 65535)", who, g.n_kt);
   const int* dm = m->dims;
   LX_CHECK_ARG((dm[0] == 1 || dm[0] == d->B) && (dm[1] == 1 || dm[1] == d->H) && (dm[2] == 1 || dm[2] == S) && dm[3] == S,
                "%s: mask dims [%d, %d, %d, %d] must be [1|B, 1|H, 1|S, S] with B=%d H=%d S=%d", who, dm[0], dm[1], dm[2], dm[3], d->B, d->H, S);
@@ -376,8 +344,9 @@ static int lx_mask_ws_check(const lx_attn_mask_desc* m, const MaskGeom& g, const
 }
 
 extern "C" int lx_attn_mask_workspace(const lx_attn_desc* d, const lx_attn_mask_desc* m, size_t* bytes) {
+  AttnPlan p;
   MaskGeom g;
-  const int st = lx_mask_geom(d, m, "lx_attn_mask_workspace", g);
+  const int st = lx_mask_geom(d, m, "lx_attn_mask_workspace", LX_ATTN_SEGMENTS_ONLY, p, g);
   if (st != LX_OK) return st;
   LX_CHECK_ARG(bytes, "lx_attn_mask_workspace: NULL result pointer");
   *bytes = g.bytes;
@@ -385,8 +354,9 @@ extern "C" int lx_attn_mask_workspace(const lx_attn_desc* d, const lx_attn_mask_
 }
 
 extern "C" int lx_attn_mask_prep(const lx_attn_desc* d, const lx_attn_mask_desc* m, void* stream) {
+  AttnPlan p;
   MaskGeom g;
-  int st = lx_mask_geom(d, m, "lx_attn_mask_prep", g);
+  int st = lx_mask_geom(d, m, "lx_attn_mask_prep", LX_ATTN_SEGMENTS_ONLY, p, g);
   if (st != LX_OK) return st;
   LX_CHECK_ARG(m->mask, "lx_attn_mask_prep: NULL mask");
   if ((st = lx_mask_ws_check(m, g, "lx_attn_mask_prep")) != LX_OK) return st;
@@ -413,44 +383,21 @@ extern "C" int lx_attn_mask_prep(const lx_attn_desc* d, const lx_attn_mask_desc*
 }
 
 extern "C" int lx_attn_fwd_masked(const lx_attn_desc* d, const lx_attn_mask_desc* m, void* stream) {
+  AttnPlan p;
   MaskGeom g;
-  int st = lx_mask_geom(d, m, "lx_attn_fwd_masked", g);
+  int st = lx_mask_geom(d, m, "lx_attn_fwd_masked", LX_ATTN_OPERANDS_16BIT, p, g);
   if (st != LX_OK) return st;
-  LX_CHECK_ARG(d->Q && d->K && d->VT && d->O, "lx_attn_fwd_masked: NULL operand");
-  LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd_masked: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required");
-  LX_CHECK_ARG(d->q_col % 8 == 0 && d->k_col % 8 == 0 && d->o_col % 4 == 0, "lx_attn_fwd_masked: column offsets must be 16-byte aligned");
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_Q_LOG2 | LX_ATTN_O_F16)) == 0, "lx_attn_fwd_masked: flags=%d: only LX_ATTN_Q_LOG2 and LX_ATTN_O_F16 are accepted", d->flags);
-  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd_masked: n_qseg=%d must be 0..n_seg", d->n_qseg);
-  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd_masked: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
-  // which segments have queries, as in lx_attn_fwd: qseg_mask when given, else the first n_qseg (0: all)
-  const int qmask = d->qseg_mask != 0 ? d->qseg_mask : (1 << (d->n_qseg > 0 ? d->n_qseg : d->n_seg)) - 1;
-  // "the rows of O of a segment without queries are not written" can only hold if no query segment's rows [seg_row0, + B * seg_len) share them
-  for (int s = 0; s < d->n_seg; ++s)
-    for (int t = 0; t < d->n_seg; ++t) {
-      if (((qmask >> s) & 1) || !((qmask >> t) & 1)) continue;
-      const long long s0 = d->seg_row0[s], s1 = s0 + (long long)d->B * d->seg_len[s], t0 = d->seg_row0[t], t1 = t0 + (long long)d->B * d->seg_len[t];
-      LX_CHECK_ARG(s1 <= t0 || t1 <= s0, "lx_attn_fwd_masked: n_qseg / qseg_mask leave segment %d without queries, but its rows [%lld, %lld) of O overlap "
-                   "query segment %d's rows [%lld, %lld)", s, s0, s1, t, t0, t1);
-    }
-  for (int s = 0; s < d->n_seg; ++s) {
-    const long long vt_end = (long long)d->seg_vt0[s] + (d->seg_len[s] + KVBLK - 1) / KVBLK * KVBLK;
-    LX_CHECK_ARG(vt_end <= d->vt_ld, "lx_attn_fwd_masked: segment %d's V^T tiles end at %lld > vt_ld=%d", s, vt_end, d->vt_ld);
-  }
   if ((st = lx_mask_ws_check(m, g, "lx_attn_fwd_masked")) != LX_OK) return st;
   MaskAttnArgs a;
   a.d = *d;
   a.g = g;
-  a.wide_store = d->ldo % 8 == 0 && d->o_col % 8 == 0 && ((uintptr_t)d->O & 15) == 0;
+  a.wide_store = p.wide_store;
   a.list = (const int*)((const char*)m->workspace + g.list_off);
   a.data = (const char*)m->workspace + g.data_off;
   // The prep pass classified every query tile; this launch covers the tiles of the query segments only.
-  int nq = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.qq_start[s] = nq;
-    if (s < d->n_seg && ((qmask >> s) & 1)) nq += g.qt_start[s + 1] - g.qt_start[s];
-  }
-  a.qq_start[3] = nq;
-  const int grid = nq * d->B * d->H;
+  for (int i = 0; i < 4; ++i) a.qq_start[i] = p.qq_start[i];
+  const int grid = p.items;
   hipStream_t s = (hipStream_t)stream;
   if (m->dtype == LX_ATTN_MASK_BOOL) hipLaunchKernelGGL(lx_attn_mask_kernel<false>, dim3(grid), dim3(512), 0, s, a);
   else hipLaunchKernelGGL(lx_attn_mask_kernel<true>, dim3(grid), dim3(512), 0, s, a);

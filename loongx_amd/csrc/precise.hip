@@ -408,15 +408,12 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
     const char* sb = smem + buf * SP_STAGE;
     // ---- S^T = K . Q^T : the two small cross terms first, then hi.hi -------------------------------
     f32x16 sacc[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
+    lx_zero_acc(sacc);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        const int off = kb * 32 * 256 + k_row_off + (((ks * 2 + lhi) ^ ksw) * 16);
+        const int off = lx_k_frag_off(kb, ks, lhi, k_row_off, ksw);
         const bf16x8 kfh = *(const bf16x8*)(sb + off);
         const bf16x8 kfl = *(const bf16x8*)(sb + SP_TILE + off);
         sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfl, qh[ks], sacc[kb], 0, 0, 0);
@@ -440,13 +437,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
     }
     float off = bl;
     if constexpr (!BOUNDED) {
-      float tmax = fmaxf(sacc[0][0], sacc[0][1]);
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = (kb == 0 ? 2 : 0); r < 16; r += 2) tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, sacc[kb][r]), sacc[kb][r + 1]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float m_new = fmaxf(m_run, tmax * c2 + bl);
+      const float m_new = fmaxf(m_run, lx_tile_max(sacc) * c2 + bl);
       const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
       l_run *= alpha;
       m_run = m_new;
@@ -480,7 +471,7 @@ __global__ __launch_bounds__(512, 1) void attn_split_kernel(const AttnSplitArgs 
       const bf16x8 ph = __builtin_bit_cast(bf16x8, wh), pl = __builtin_bit_cast(bf16x8, wl);
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        const int off2 = v_row_off + db * 32 * 128 + (((s * 2 + lhi) ^ vsw) * 16);
+        const int off2 = lx_v_frag_off(db, s, lhi, v_row_off, vsw);
         const bf16x8 vfh = *(const bf16x8*)(sb + off2);
         const bf16x8 vfl = *(const bf16x8*)(sb + SP_TILE + off2);
         oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfl, ph, oacc[db], 0, 0, 0);
@@ -638,49 +629,19 @@ extern "C" int lx_qkv_prep_split_kv_segs(const float* QKV, int ld, int q_col, in
 }
 
 extern "C" int lx_attn_fwd_split(const lx_attn_desc* d, int qk_lo_off, long long vt_lo_off, int o_lo_off, void* stream) {
-  LX_CHECK_ARG(d && d->Q && d->K && d->VT && d->O, "lx_attn_fwd_split: NULL operand");
-  LX_CHECK_ARG(d->n_seg >= 1 && d->n_seg <= 3, "lx_attn_fwd_split: n_seg=%d must be 1..3", d->n_seg);
-  LX_CHECK_ARG(d->B >= 1 && d->H >= 1, "lx_attn_fwd_split: bad B/H");
-  LX_CHECK_ARG(d->n_qseg >= 0 && d->n_qseg <= d->n_seg, "lx_attn_fwd_split: n_qseg=%d must be 0..n_seg", d->n_qseg);
-  LX_CHECK_ARG(d->qseg_mask >= 0 && d->qseg_mask < (1 << d->n_seg), "lx_attn_fwd_split: qseg_mask=%d names a segment >= n_seg", d->qseg_mask);
-  LX_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldo % 4 == 0 && d->vt_ld % 64 == 0, "lx_attn_fwd_split: ldq/ldk %% 8, ldo %% 4, vt_ld %% 64 required");
-  LX_CHECK_ARG(d->q_col % 8 == 0 && d->k_col % 8 == 0 && d->o_col % 4 == 0, "lx_attn_fwd_split: column offsets must be 16-byte aligned");
+  AttnPlan p;
+  const int rc = lx_attn_plan("lx_attn_fwd_split", d, LX_ATTN_OPERANDS_16BIT, LX_ATTN_RULE_QUERY_HAS_KEYS, p);
+  if (rc != LX_OK) return rc;
   LX_CHECK_ARG(qk_lo_off % 8 == 0 && qk_lo_off >= d->H * 128 && vt_lo_off % 8 == 0 && vt_lo_off > 0 && o_lo_off % 4 == 0 && o_lo_off >= 0,
                "lx_attn_fwd_split: qk_lo_off %% 8 (>= H*128), vt_lo_off %% 8 (> 0), o_lo_off %% 4 (>= 0) required");
-  AttnSplitArgs a;
-  a.d = *d;
-  a.qk_lo_off = qk_lo_off; a.vt_lo_off = vt_lo_off; a.o_lo_off = o_lo_off;
-  // which segments have queries, as in lx_attn_fwd: qseg_mask when given, else the first n_qseg (0: all)
-  const int qmask = d->qseg_mask != 0 ? d->qseg_mask : (1 << (d->n_qseg > 0 ? d->n_qseg : d->n_seg)) - 1;
-  for (int s = 0; s < d->n_seg; ++s) {
-    LX_CHECK_ARG(d->seg_len[s] >= 1, "lx_attn_fwd_split: empty segment %d", s);
-    LX_CHECK_ARG(d->seg_vt0[s] >= 0 && d->seg_vt0[s] % 64 == 0, "lx_attn_fwd_split: seg_vt0 must be 64-aligned");
-    const long long vt_end = (long long)d->seg_vt0[s] + (d->seg_len[s] + SP_KV - 1) / SP_KV * SP_KV;
-    LX_CHECK_ARG(vt_end <= d->vt_ld, "lx_attn_fwd_split: segment %d's V^T tiles end at %lld > vt_ld=%d", s, vt_end, d->vt_ld);
-  }
-  // "the rows of O of a segment without queries are not written" can only hold if no query segment's rows [seg_row0, + B * seg_len) share them
-  for (int s = 0; s < d->n_seg; ++s)
-    for (int q = 0; q < d->n_seg; ++q) {
-      if (((qmask >> s) & 1) || !((qmask >> q) & 1)) continue;
-      const long long s0 = d->seg_row0[s], s1 = s0 + (long long)d->B * d->seg_len[s], q0 = d->seg_row0[q], q1 = q0 + (long long)d->B * d->seg_len[q];
-      LX_CHECK_ARG(s1 <= q0 || q1 <= s0, "lx_attn_fwd_split: n_qseg / qseg_mask leave segment %d without queries, but its rows [%lld, %lld) of O overlap "
-                   "query segment %d's rows [%lld, %lld)", s, s0, s1, q, q0, q1);
-    }
-  int t = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.qq_start[s] = t;
-    if (s < d->n_seg && ((qmask >> s) & 1)) {
-      bool any = false;
-      for (int k = 0; k < d->n_seg; ++k) any |= d->bias[s][k] > -1e37f;
-      LX_CHECK_ARG(any, "lx_attn_fwd_split: query segment %d is masked from every key segment", s);
-      t += (d->seg_len[s] + 255) / 256;
-    }
-  }
-  a.qq_start[3] = t;
   LX_CHECK_ARG((d->flags & ~(LX_ATTN_Q_LOG2 | LX_ATTN_BOUNDED)) == 0 && (!(d->flags & LX_ATTN_BOUNDED) || (d->flags & LX_ATTN_Q_LOG2)),
                "lx_attn_fwd_split: flags=%d: unknown bit, or LX_ATTN_BOUNDED without LX_ATTN_Q_LOG2", d->flags);
-  if (d->flags & LX_ATTN_BOUNDED) hipLaunchKernelGGL(attn_split_kernel<true>, dim3(t * d->B * d->H), dim3(512), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(attn_split_kernel<false>, dim3(t * d->B * d->H), dim3(512), 0, (hipStream_t)stream, a);
+  AttnSplitArgs a;
+  a.d = *d;
+  for (int s = 0; s < 4; ++s) a.qq_start[s] = p.qq_start[s];
+  a.qk_lo_off = qk_lo_off; a.vt_lo_off = vt_lo_off; a.o_lo_off = o_lo_off;
+  if (d->flags & LX_ATTN_BOUNDED) hipLaunchKernelGGL(attn_split_kernel<true>, dim3(p.items), dim3(512), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(attn_split_kernel<false>, dim3(p.items), dim3(512), 0, (hipStream_t)stream, a);
   LX_LAUNCH_CHECK("lx_attn_fwd_split");
   return LX_OK;
 }

@@ -1,7 +1,8 @@
-"""CPU-only: what the ln-modulate, qkv-prep and precise attention entry points reject on the host, which status they return and the complete
+"""CPU-only: what the ln-modulate, qkv-prep and attention entry points reject on the host, which status they return and the complete
 lx_last_error() text, check order included. Every call here is refused before anything is launched (fake, aligned addresses:
 nothing dereferences them), so a call that would pass validation never appears -- where an entry point ACCEPTS a value that
-another one rejects, the accepting call carries a later defect (an empty segment 1) and the test pins that later message."""
+another one rejects, the accepting call carries a later defect (an empty segment 1) and the test pins that later message.
+(lx_attn_mask_workspace launches nothing: its accepting call is here.)"""
 import ctypes as C
 
 import pytest
@@ -377,3 +378,131 @@ def test_precise_attention_refuses_a_query_segment_masked_from_every_key():
     _rejected(_attn_f32([[0.0, NINF, 0.0], [NINF, 0.0, 0.0], DEAD2[2]], n_seg=2, seg_len=(40, 0, 70)), "lx_attn_fwd_f32: empty segment 1")
     # the earlier checks still come first
     _rejected(_attn_f32(DEAD2, o_lo_off=258), "lx_attn_fwd_f32: ldo / o_col / o_lo_off must be multiples of 4")
+
+
+# ---- lx_attn_desc: one validator behind every entry point that takes the descriptor ---------------------------------------------------
+ATTN_ENTRIES = ("lx_attn_fwd", "lx_attn_fwd_fp8", "lx_attn_fwd_split", "lx_attn_fwd_masked")
+ATTN_DEFAULTS = dict(Q=A, K=A, VT=A, O=A, ldq=1024, ldk=1024, ldo=512, vt_ld=320, q_col=512, k_col=0, o_col=0, B=2, H=2, n_seg=3,
+                     row0=(0, 80, 280), seg_len=(40, 100, 70), vt0=(0, 64, 192), bias=None, n_qseg=0, qseg_mask=0, flags=0, ws_short=0)
+WS = 0x100000        # 256-byte aligned
+BAD_FLAG = 1 << 12
+ATTN_FLAG_TEXT = {
+    "lx_attn_fwd": "lx_attn_fwd: flags=4096: unknown bit, LX_ATTN_BOUNDED without LX_ATTN_Q_LOG2, or LX_ATTN_INVARIANT with LX_ATTN_PREFER_4WAVE",
+    "lx_attn_fwd_fp8": "lx_attn_fwd_fp8: the flags are LX_ATTN_O_F16 and LX_ATTN_P_EXP2 (the e4m3 kernels fold their own scales)",
+    "lx_attn_fwd_split": "lx_attn_fwd_split: flags=4096: unknown bit, or LX_ATTN_BOUNDED without LX_ATTN_Q_LOG2",
+    "lx_attn_fwd_masked": "lx_attn_fwd_masked: flags=4096: only LX_ATTN_Q_LOG2 and LX_ATTN_O_F16 are accepted",
+}
+
+
+def _attn_desc(a):
+    d = _lib.AttnDesc()
+    d.Q, d.K, d.VT, d.O = a["Q"], a["K"], a["VT"], a["O"]
+    d.ldq, d.ldk, d.ldo, d.vt_ld = a["ldq"], a["ldk"], a["ldo"], a["vt_ld"]
+    d.q_col, d.k_col, d.o_col, d.B, d.H, d.n_seg = a["q_col"], a["k_col"], a["o_col"], a["B"], a["H"], a["n_seg"]
+    for i in range(3):
+        d.seg_row0[i], d.seg_len[i], d.seg_vt0[i] = a["row0"][i], a["seg_len"][i], a["vt0"][i]
+        for j in range(3):
+            d.bias[i][j] = 0.0 if a["bias"] is None else a["bias"][i][j]
+    d.scale, d.n_qseg, d.qseg_mask, d.flags = 0.088, a["n_qseg"], a["qseg_mask"], a["flags"]
+    return d
+
+
+def _attn_mask_desc(a, workspace=None, workspace_bytes=0):
+    S = sum(a["seg_len"][:3])
+    m = _lib.AttnMaskDesc()
+    m.mask, m.dtype = 0x20000, _lib.LX_ATTN_MASK_BOOL
+    for i, (n, st) in enumerate(zip((a["B"], a["H"], S, S), (a["H"] * S * S, S * S, S, 1))):
+        m.dims[i], m.strides[i] = n, st
+    m.workspace, m.workspace_bytes = workspace, workspace_bytes
+    return m
+
+
+def _attn_ws_need():
+    """the workspace of the valid base descriptor (every launching case below keeps its segment lengths, B and H, or fails before the mask)"""
+    n = C.c_size_t(0)
+    assert _lib.lib.lx_attn_mask_workspace(C.byref(_attn_desc(ATTN_DEFAULTS)), C.byref(_attn_mask_desc(ATTN_DEFAULTS)), C.byref(n)) == 0
+    return n.value
+
+
+def _attn_call(entry, **over):
+    a = dict(ATTN_DEFAULTS, **over)
+    d = _attn_desc(a)
+    lib = _lib.lib
+    if entry == "lx_attn_fwd":
+        return lib.lx_attn_fwd(C.byref(d), None)
+    if entry == "lx_attn_fwd_fp8":
+        return lib.lx_attn_fwd_fp8(C.byref(d), 0.01, 0.5, None)
+    if entry == "lx_attn_fwd_split":
+        return lib.lx_attn_fwd_split(C.byref(d), 256, 2 * 2 * 128 * 320, 256, None)
+    if entry == "lx_attn_fwd_masked":
+        m = _attn_mask_desc(ATTN_DEFAULTS, WS, _attn_ws_need() - a["ws_short"])
+        return lib.lx_attn_fwd_masked(C.byref(d), C.byref(m), None)
+    raise KeyError(entry)
+
+
+@pytest.mark.parametrize("entry", ATTN_ENTRIES)
+def test_attn_descriptor_rules(entry):
+    """Each shared rule violated alone on one valid 3-segment descriptor: the same text behind every entry point, with its name in front."""
+    for op in ("Q", "K", "VT", "O"):
+        _rejected(_attn_call(entry, **{op: None}), f"{entry}: NULL operand")
+    _rejected(_attn_call(entry, n_seg=0), f"{entry}: n_seg=0 must be 1..3")
+    _rejected(_attn_call(entry, n_seg=4), f"{entry}: n_seg=4 must be 1..3")
+    _rejected(_attn_call(entry, B=0), f"{entry}: bad B/H")
+    if entry == "lx_attn_fwd_fp8":
+        _rejected(_attn_call(entry, ldk=1032), f"{entry}: ldq/ldk % 16 (bytes), ldo % 4, vt_ld % 64 required")     # a multiple of 8 is not enough in bytes
+    else:
+        _rejected(_attn_call(entry, ldk=1028), f"{entry}: ldq/ldk % 8, ldo % 4, vt_ld % 64 required")
+    _rejected(_attn_call(entry, n_qseg=-1), f"{entry}: n_qseg=-1 must be 0..n_seg")
+    _rejected(_attn_call(entry, n_qseg=4), f"{entry}: n_qseg=4 must be 0..n_seg")
+    _rejected(_attn_call(entry, qseg_mask=8), f"{entry}: qseg_mask=8 names a segment >= n_seg")
+    _rejected(_attn_call(entry, qseg_mask=-1), f"{entry}: qseg_mask=-1 names a segment >= n_seg")
+    _rejected(_attn_call(entry, seg_len=(40, 0, 70)), f"{entry}: empty segment 1")
+    # what keeps the K / V^T staging inside the caller's V^T rows
+    _rejected(_attn_call(entry, vt0=(0, 32, 192)), f"{entry}: seg_vt0 must be 64-aligned")
+    _rejected(_attn_call(entry, vt0=(-64, 64, 192)), f"{entry}: seg_vt0 must be 64-aligned")
+    _rejected(_attn_call(entry, vt_ld=256), f"{entry}: segment 2's V^T tiles end at 320 > vt_ld=256")
+    _rejected(_attn_call(entry, vt_ld=256, n_qseg=2), f"{entry}: segment 2's V^T tiles end at 320 > vt_ld=256")       # a key-only segment is read too
+    # a key-only segment's rows of O are promised untouched: no query segment may share them
+    _rejected(_attn_call(entry, n_qseg=2, row0=(0, 80, 200)),
+              f"{entry}: n_qseg / qseg_mask leave segment 2 without queries, but its rows [200, 340) of O overlap query segment 1's rows [80, 280)")
+    _rejected(_attn_call(entry, qseg_mask=0b100, row0=(0, 80, 40)),
+              f"{entry}: n_qseg / qseg_mask leave segment 0 without queries, but its rows [0, 80) of O overlap query segment 2's rows [40, 180)")
+    _rejected(_attn_call(entry, flags=BAD_FLAG), ATTN_FLAG_TEXT[entry])
+    # the descriptor is looked at before the entry point's own flags
+    _rejected(_attn_call(entry, flags=BAD_FLAG, seg_len=(40, 0, 70)), f"{entry}: empty segment 1")
+
+
+@pytest.mark.parametrize("entry", ATTN_ENTRIES[:3])
+def test_attn_fully_masked_query_segment(entry):
+    text = f"{entry}: query segment 2 is masked from every key segment"
+    _rejected(_attn_call(entry, bias=DEAD2), text)
+    _rejected(_attn_call(entry, bias=DEAD2, qseg_mask=0b110), text)
+    _rejected(_attn_call(entry, bias=DEAD2, flags=BAD_FLAG), text)
+    # key-only, segment 2 needs no key of its own: the call gets as far as the flag bit broken on purpose
+    _rejected(_attn_call(entry, bias=DEAD2, n_qseg=2, flags=BAD_FLAG), ATTN_FLAG_TEXT[entry])
+    _rejected(_attn_call(entry, bias=DEAD2, qseg_mask=0b011, flags=BAD_FLAG), ATTN_FLAG_TEXT[entry])
+
+
+def test_attn_masked_accepts_a_fully_masked_query_segment():
+    """lx_attn_fwd_masked does not apply that rule (a mask can empty any row; such rows are written as zeros): the descriptor gets past it
+    and fails on the workspace, one byte short on purpose."""
+    need = _attn_ws_need()
+    _rejected(_attn_call("lx_attn_fwd_masked", bias=DEAD2, ws_short=1),
+              f"lx_attn_fwd_masked: workspace of {need - 1} bytes, {need} needed (lx_attn_mask_workspace)")
+    _rejected(_attn_call("lx_attn_fwd_masked", ws_short=1), f"lx_attn_fwd_masked: workspace of {need - 1} bytes, {need} needed (lx_attn_mask_workspace)")
+
+
+def test_attn_mask_workspace_checks_the_segment_part_only():
+    e = "lx_attn_mask_workspace"
+    n = C.c_size_t(0)
+
+    def call(**over):
+        a = dict(ATTN_DEFAULTS, Q=None, K=None, VT=None, O=None, vt_ld=0, ldk=1028, n_qseg=7, row0=(0, 0, 0), flags=BAD_FLAG, **over)
+        return _lib.lib.lx_attn_mask_workspace(C.byref(_attn_desc(a)), C.byref(_attn_mask_desc(ATTN_DEFAULTS)), C.byref(n))
+    assert call() == 0 and n.value == _attn_ws_need() > 0        # no operands, no vt_ld, no query subset: a size all the same
+    _rejected(call(n_seg=0), f"{e}: n_seg=0 must be 1..3")
+    _rejected(call(n_seg=4), f"{e}: n_seg=4 must be 1..3")
+    _rejected(call(B=0), f"{e}: bad B/H")
+    _rejected(call(seg_len=(40, 0, 70)), f"{e}: empty segment 1")
+    _rejected(call(vt0=(0, 32, 192)), f"{e}: seg_vt0 must be 64-aligned")
+    _rejected(call(vt0=(-64, 64, 192)), f"{e}: seg_vt0 must be 64-aligned")
