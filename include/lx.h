@@ -34,6 +34,8 @@ extern "C" {
  *         a fourth additive extension of 0.4.4 (no layout change): + lx_softmax_rows_valid (the VAE's row softmax over a padded key axis)
  *         a fifth additive extension of 0.4.4 (no layout change): + lx_groupnorm_silu_split, lx_im2col3x3_split, lx_softmax_rows_split (the
  *         VAE's row kernels on split-bf16 pair images: the precise-mode VAE)
+ *         a sixth additive extension of 0.4.4 (no layout change): + lx_groupnorm_silu_f16, lx_softmax_rows_f16, lx_convert_f16 (the VAE's row
+ *         kernels writing fp16 operand images: LxAutoencoderKL(operands="fp16"))
  *  0.4.3  + LX_ATTN_P_EXP2; lx_attn_fwd_fp8's default probability bytes are the log-linear code of the score (POW2 scales)
  *  0.4.2  + lx_qkv_prep_f16in_segs, lx_qkv_prep_fp8_f16in_segs (the separate RMSNorm + RoPE + V^T pass on a projection an LX_OPERANDS_F16
  *         launch stored as fp16: stream lengths LX_EPI_QKV does not take)
@@ -623,6 +625,21 @@ int lx_im2col3x3_split(const void* x, int ldx, int x_lo_off, int B, int H, int W
  * +0 in columns [n_valid, n_store) of both halves, nothing else written; columns >= n_valid of S are never read. n_valid == n_store is
  * the unpadded key axis. p_lo_off >= n_store, ldp >= p_lo_off + n_store; alignment rules as for lx_softmax_rows_valid. */
 int lx_softmax_rows_split(const float* S, int lds, float scale, void* P, int ldp, int p_lo_off, int M, int n_valid, int n_store, void* stream);
+
+/* The VAE's glue on fp16 operands (LxAutoencoderKL(operands="fp16"), dtype=torch.float16): the producers of the operand images of
+ * LX_OPERANDS_F16 launches of lx_gemm_bf16. lx_im2col3x3 gathers 16-bit words and serves fp16 images as it stands. */
+/* lx_groupnorm_silu of fp32 x [B, P, C] with y stored as IEEE fp16 [B, P, C]: round to nearest even, saturated to +-65504. Same two
+ * passes and the same fixed-order fold. *f16_ovf (device, may be NULL) += the number of waves that clipped a value. x, gamma, beta 16-byte
+ * and y 8-byte aligned. */
+int lx_groupnorm_silu_f16(const float* x, int B, int P, int C, int G, const float* gamma, const float* beta, float eps, int silu, void* y,
+                          void* ws, size_t ws_bytes, int32_t* f16_ovf, void* stream);
+/* lx_softmax_rows_valid with P stored as IEEE fp16 (probabilities are <= 1: nothing saturates, nothing is counted). Same contract:
+ * columns >= n_valid of S are never read, P[m, n_valid:n_store] = +0, nothing at or beyond column n_store of P is written; n_valid ==
+ * n_store is the unpadded key axis. Alignment rules as there. */
+int lx_softmax_rows_f16(const float* S, int lds, float scale, void* P, int ldp, int M, int n_valid, int n_store, void* stream);
+/* dst(fp16)[i] = src(fp32 | bf16)[i], saturated to +-65504 (+-inf included; NaN stays NaN) and, unlike lx_convert with dst 2, counted:
+ * *f16_ovf (device, may be NULL) += the number of waves that clipped a value. */
+int lx_convert_f16(void* dst, const void* src, int src_bf16, size_t n, int32_t* f16_ovf, void* stream);
 
 #ifdef __cplusplus
 }

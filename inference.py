@@ -57,6 +57,9 @@ def load_model(checkpoint_path, config=None, device=None):
     model.to("cuda")
     model.flux_pipe.to("cuda")
     model.eval()
+    vae = getattr(model.flux_pipe, "vae", None)
+    if config.get("model", {}).get("operands") == "fp16" and hasattr(vae, "set_operands") and not vae.precise:
+        vae.set_operands("fp16")                         # --operands fp16: the VAE either side of the fp16 DiT runs on fp16 operands too
     return model
 
 

@@ -134,6 +134,9 @@ _SIGS = {
     "lx_groupnorm_silu_split": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _I, _I, _P, _Z, _P]),
     "lx_im2col3x3_split": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "lx_softmax_rows_split": (C.c_int, [_P, _I, _F, _P, _I, _I, _I, _I, _I, _P]),
+    "lx_groupnorm_silu_f16": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _Z, _P, _P]),
+    "lx_softmax_rows_f16": (C.c_int, [_P, _I, _F, _P, _I, _I, _I, _I, _P]),
+    "lx_convert_f16": (C.c_int, [_P, _P, _I, _Z, _P, _P]),
     "lx_ln_modulate_fp8_segs": (C.c_int, [_P, _I, C.POINTER(LnSeg), _I, _I, _P, _I, _P, _I, _F, _I, _F, _P]),
     "lx_convert_fp8": (C.c_int, [_P, _I, _I, _P, _I, _F, _I, _I, _P]),
     "lx_lora_down_fp8": (C.c_int, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -7,6 +7,8 @@
 //     decoder's nearest-neighbour 2x upsample folded into the gather (the upsampled image is never materialised);
 //   * row softmax (fp32 scores -> bf16 probabilities) for the single-head mid-block attention, and its form for a key axis padded
 //     to the GEMM's granule (token counts that are no multiple of 64): the pad keys get probability +0.
+// GroupNorm and the padded softmax also store IEEE fp16 (the operand images of LX_OPERANDS_F16 launches: LxAutoencoderKL(operands="fp16")),
+// from the same kernel bodies; with lx_convert_f16 they saturate at +-65504 and count the waves that clipped. im2col moves 16-bit words.
 // All accesses are 8-16 B per lane along the channel axis (the padded softmax falls back to scalar ones on unaligned rows).
 #include "common.h"
 
@@ -57,11 +59,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
   }
 }
 
-template <typename T>
+// F16: y is the fp16 operand image of an LX_OPERANDS_F16 GEMM (round to nearest even, saturated to +-65504); a wave that clipped a value
+// adds 1 to *f16_ovf (NULL: not reported). The bf16 instantiation never touches f16_ovf.
+template <typename T, bool F16>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, int P, int C, int G, const float* __restrict__ part, int nchunk,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int silu,
-                                                       uint16_t* __restrict__ y) {
+                                                       uint16_t* __restrict__ y, int* __restrict__ f16_ovf) {
   const int b = blockIdx.y;
+  float mx = 0.f;
   const size_t n4 = (size_t)P * C / 4;
   const float inv_n = 1.0f / ((float)P * (float)(C / G));
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -84,8 +89,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
       if (silu) t = t / (1.0f + __expf(-t));
       o[c] = t;
     }
-    *(u32x2*)(y + (size_t)b * P * C + i * 4) = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+    *(u32x2*)(y + (size_t)b * P * C + i * 4) = u32x2{pack_op16x2<F16>(o[0], o[1], mx), pack_op16x2<F16>(o[2], o[3], mx)};
   }
+  if constexpr (F16) report_f16_overflow(mx, f16_ovf);
 }
 
 // ---- im2col for 3x3 convolutions, NHWC bf16 -> [B*Ho*Wo, Kpad] bf16, column = (dy*3 + dx)*C + c ------------------------------------
@@ -150,11 +156,25 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   }
 }
 
+// The 16-bit format of a probability image: how two / one fp32 values are stored. Probabilities are <= 1, so the fp16 form needs no
+// saturation (and has no overflow to report).
+struct StoreBf16 {
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
+  static __device__ __forceinline__ uint16_t one(float v) { return f32_to_bf16(v); }
+};
+struct StoreF16 {
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+    const f16x2 v = {(_Float16)lo, (_Float16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+  }
+  static __device__ __forceinline__ uint16_t one(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
+};
+
 // ---- row softmax over the first n_valid columns of a row whose key axis is padded: P[row, 0:n_valid] = softmax(scale * S[row, 0:n_valid]),
 // P[row, n_valid:n_store] = +0. One wave per row. Columns >= n_valid of S (scores against padding: anything, NaN included) are never
 // loaded; nothing at or beyond column n_store of P is written. VEC: every row of S starts 16-byte and every row of P 8-byte aligned, so
 // columns [0, n_valid & ~3) go four per lane and only the < 4 columns behind them one per lane; otherwise every access is a scalar one.
-template <bool VEC>
+template <bool VEC, typename ST>
 __global__ __launch_bounds__(256) void softmax_rows_valid_kernel(const float* __restrict__ S, int lds, float scale, uint16_t* __restrict__ Pm, int ldp,
                                                                  int M, int n_valid, int n_store) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -182,9 +202,9 @@ __global__ __launch_bounds__(256) void softmax_rows_valid_kernel(const float* __
     float o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = __expf(v[k] * scale - m) * inv;
-    *(u32x2*)(p + c) = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+    *(u32x2*)(p + c) = u32x2{ST::pack2(o[0], o[1]), ST::pack2(o[2], o[3])};
   }
-  for (int c = nv + lane; c < n_valid; c += 64) p[c] = f32_to_bf16(__expf(s[c] * scale - m) * inv);
+  for (int c = nv + lane; c < n_valid; c += 64) p[c] = ST::one(__expf(s[c] * scale - m) * inv);
   // the pad keys' probabilities: scalar up to the next multiple of 4 (z0), vectors up to the last one (z1), scalar to n_store
   const int z0 = VEC ? min((n_valid + 3) & ~3, n_store) : n_store, z1 = VEC ? max(z0, n_store & ~3) : n_store;
   for (int c = n_valid + lane; c < z0; c += 64) p[c] = 0;
@@ -199,25 +219,38 @@ extern "C" size_t lx_groupnorm_workspace_bytes(int B, int P, int G) {
   return (size_t)B * nchunk * G * 2 * sizeof(float);
 }
 
+// The two passes of lx_groupnorm_silu / lx_groupnorm_silu_f16 (arguments checked by the caller).
+template <typename T, bool F16>
+static void gn_launch(const T* x, int B, int P, int C, int G, const float* gamma, const float* beta, float eps, int silu, void* y, void* ws,
+                      int32_t* f16_ovf, hipStream_t s) {
+  const int nchunk = P >= 4096 ? 64 : (P >= 256 ? 16 : 1);
+  const int rpc = (P + nchunk - 1) / nchunk;
+  float* part = (float*)ws;
+  const size_t n4 = (size_t)P * C / 4;
+  const int gx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+  hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunk, B), dim3(256), 0, s, x, P, C, G, rpc, part);
+  hipLaunchKernelGGL((gn_apply_kernel<T, F16>), dim3(gx, B), dim3(256), 0, s, x, P, C, G, part, nchunk, gamma, beta, eps, silu, (uint16_t*)y, (int*)f16_ovf);
+}
+
 extern "C" int lx_groupnorm_silu(const void* x, int x_is_bf16, int B, int P, int C, int G, const float* gamma, const float* beta, float eps,
                                  int silu, void* y, void* ws, size_t ws_bytes, void* stream) {
   LX_CHECK_ARG(x && y && gamma && beta && ws, "lx_groupnorm_silu: NULL operand");
   LX_CHECK_ARG(B > 0 && P > 0 && C > 0 && G > 0 && G <= 64 && C % G == 0 && (C / G) % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "lx_groupnorm_silu: need G <= 64, C %% G == 0, (C/G) %% 4 == 0, C/4 a divisor of 256 (C=%d G=%d)", C, G);
   LX_CHECK_ARG(ws_bytes >= lx_groupnorm_workspace_bytes(B, P, G), "lx_groupnorm_silu: workspace too small");
-  const int nchunk = P >= 4096 ? 64 : (P >= 256 ? 16 : 1);
-  const int rpc = (P + nchunk - 1) / nchunk;
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  const size_t n4 = (size_t)P * C / 4;
-  const int gx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  if (x_is_bf16) {
-    hipLaunchKernelGGL(gn_stats_kernel<uint16_t>, dim3(nchunk, B), dim3(256), 0, s, (const uint16_t*)x, P, C, G, rpc, part);
-    hipLaunchKernelGGL(gn_apply_kernel<uint16_t>, dim3(gx, B), dim3(256), 0, s, (const uint16_t*)x, P, C, G, part, nchunk, gamma, beta, eps, silu, (uint16_t*)y);
-  } else {
-    hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(nchunk, B), dim3(256), 0, s, (const float*)x, P, C, G, rpc, part);
-    hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(gx, B), dim3(256), 0, s, (const float*)x, P, C, G, part, nchunk, gamma, beta, eps, silu, (uint16_t*)y);
-  }
+  if (x_is_bf16) gn_launch<uint16_t, false>((const uint16_t*)x, B, P, C, G, gamma, beta, eps, silu, y, ws, nullptr, (hipStream_t)stream);
+  else gn_launch<float, false>((const float*)x, B, P, C, G, gamma, beta, eps, silu, y, ws, nullptr, (hipStream_t)stream);
   LX_LAUNCH_CHECK("lx_groupnorm_silu");
+  return LX_OK;
+}
+
+extern "C" int lx_groupnorm_silu_f16(const float* x, int B, int P, int C, int G, const float* gamma, const float* beta, float eps, int silu, void* y,
+                                     void* ws, size_t ws_bytes, int32_t* f16_ovf, void* stream) {
+  LX_CHECK_ARG(x && y && gamma && beta && ws, "lx_groupnorm_silu_f16: NULL operand");
+  LX_CHECK_ARG(B > 0 && P > 0 && C > 0 && G > 0 && G <= 64 && C % G == 0 && (C / G) % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "lx_groupnorm_silu_f16: need G <= 64, C %% G == 0, (C/G) %% 4 == 0, C/4 a divisor of 256 (C=%d G=%d)", C, G);
+  LX_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0 && ((uintptr_t)f16_ovf & 3) == 0, "lx_groupnorm_silu_f16: misaligned operand");
+  LX_CHECK_ARG(ws_bytes >= lx_groupnorm_workspace_bytes(B, P, G), "lx_groupnorm_silu_f16: workspace too small");
+  gn_launch<float, true>(x, B, P, C, G, gamma, beta, eps, silu, y, ws, f16_ovf, (hipStream_t)stream);
+  LX_LAUNCH_CHECK("lx_groupnorm_silu_f16");
   return LX_OK;
 }
 
@@ -245,9 +278,46 @@ extern "C" int lx_softmax_rows_valid(const float* S, int lds, float scale, void*
   LX_CHECK_ARG(M > 0 && n_valid >= 1 && n_store >= n_valid, "lx_softmax_rows_valid: need M > 0 and 1 <= n_valid <= n_store (M=%d n_valid=%d n_store=%d)", M, n_valid, n_store);
   LX_CHECK_ARG(lds >= n_valid && ldp >= n_store, "lx_softmax_rows_valid: need lds >= n_valid and ldp >= n_store (lds=%d ldp=%d n_valid=%d n_store=%d)", lds, ldp, n_valid, n_store);
   const bool vec = ((uintptr_t)S & 15) == 0 && lds % 4 == 0 && ((uintptr_t)P & 7) == 0 && ldp % 4 == 0;
-  if (vec) hipLaunchKernelGGL(softmax_rows_valid_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
-  else hipLaunchKernelGGL(softmax_rows_valid_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  if (vec) hipLaunchKernelGGL((softmax_rows_valid_kernel<true, StoreBf16>), dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  else hipLaunchKernelGGL((softmax_rows_valid_kernel<false, StoreBf16>), dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
   LX_LAUNCH_CHECK("lx_softmax_rows_valid");
+  return LX_OK;
+}
+
+extern "C" int lx_softmax_rows_f16(const float* S, int lds, float scale, void* P, int ldp, int M, int n_valid, int n_store, void* stream) {
+  LX_CHECK_ARG(S && P, "lx_softmax_rows_f16: NULL operand");
+  LX_CHECK_ARG(M > 0 && n_valid >= 1 && n_store >= n_valid, "lx_softmax_rows_f16: need M > 0 and 1 <= n_valid <= n_store (M=%d n_valid=%d n_store=%d)", M, n_valid, n_store);
+  LX_CHECK_ARG(lds >= n_valid && ldp >= n_store, "lx_softmax_rows_f16: need lds >= n_valid and ldp >= n_store (lds=%d ldp=%d n_valid=%d n_store=%d)", lds, ldp, n_valid, n_store);
+  LX_CHECK_ARG(((uintptr_t)S & 3) == 0 && ((uintptr_t)P & 1) == 0, "lx_softmax_rows_f16: misaligned operand");
+  const bool vec = ((uintptr_t)S & 15) == 0 && lds % 4 == 0 && ((uintptr_t)P & 7) == 0 && ldp % 4 == 0;
+  if (vec) hipLaunchKernelGGL((softmax_rows_valid_kernel<true, StoreF16>), dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  else hipLaunchKernelGGL((softmax_rows_valid_kernel<false, StoreF16>), dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, scale, (uint16_t*)P, ldp, M, n_valid, n_store);
+  LX_LAUNCH_CHECK("lx_softmax_rows_f16");
+  return LX_OK;
+}
+
+// ---- fp32 | bf16 -> the fp16 operand image, saturated to +-65504 AND counted (lx_convert's dst 2 clips silently). NaN stays NaN.
+namespace {
+__global__ __launch_bounds__(256) void convert_f16_kernel(uint16_t* __restrict__ dst, const void* __restrict__ src, int src_bf16, size_t n,
+                                                          int* __restrict__ f16_ovf) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  float mx = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float v = src_bf16 ? bf16_to_f32(((const uint16_t*)src)[i]) : ((const float*)src)[i];
+    const uint16_t h = (uint16_t)(pack_f16x2_sat(v, 0.f, mx) & 0xffffu);
+    dst[i] = v != v ? (uint16_t)0x7e00u : h;               // (the clamp would turn a NaN into -65504)
+  }
+  report_f16_overflow(mx, f16_ovf);
+}
+}  // namespace
+
+extern "C" int lx_convert_f16(void* dst, const void* src, int src_bf16, size_t n, int32_t* f16_ovf, void* stream) {
+  LX_CHECK_ARG(dst && src, "lx_convert_f16: NULL operand");
+  LX_CHECK_ARG(((uintptr_t)dst & 1) == 0 && ((uintptr_t)src & (src_bf16 ? 1 : 3)) == 0 && ((uintptr_t)f16_ovf & 3) == 0, "lx_convert_f16: misaligned operand");
+  if (n == 0) return LX_OK;
+  const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(convert_f16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (uint16_t*)dst, src, src_bf16, n, (int*)f16_ovf);
+  LX_LAUNCH_CHECK("lx_convert_f16");
   return LX_OK;
 }
 

@@ -15,6 +15,7 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import warnings
 from typing import Any, Callable, Dict, List, Optional, Union
@@ -33,6 +34,22 @@ F16_OVERFLOW_POLICIES = ("raise", "warn", "fallback")
 
 class F16OverflowError(RuntimeError):
     """An operand of the fp16 operand mode left fp16's range (+-65504) and was saturated: the image is not what the mode promises."""
+
+
+@contextlib.contextmanager
+def vae_f16_overflow(vae, policy: Optional[str]):
+    """model_config["f16_overflow"] handed to the VAE for one call: a VAE that has the attribute (LxAutoencoderKL; it matters on fp16
+    operands only) runs under `policy` inside the block and gets its own setting back after it. Any other VAE, or no policy: a no-op."""
+    if policy is None or not hasattr(vae, "f16_overflow"):
+        yield
+        return
+    if policy not in F16_OVERFLOW_POLICIES:
+        raise ValueError(f'model_config["f16_overflow"] = {policy!r}: one of {F16_OVERFLOW_POLICIES}')
+    own, vae.f16_overflow = vae.f16_overflow, policy
+    try:
+        yield
+    finally:
+        vae.f16_overflow = own
 
 
 def get_config(config_path: str = None):
@@ -174,7 +191,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         if not default_lora:
             _select_adapter(pipeline, conditions[0].condition_type)
         for condition in conditions:
-            tokens, ids, type_id = condition.encode(self)
+            with vae_f16_overflow(self.vae, (model_config or {}).get("f16_overflow")):      # (condition images go through encode_images)
+                tokens, ids, type_id = condition.encode(self)
             condition_latents.append(tokens)
             condition_ids.append(ids)
             condition_type_ids.append(type_id)
@@ -273,7 +291,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             pipeline.transformer.engine.check_status(sync=True)
         z = self._unpack_latents(latents, height, width, self.vae_scale_factor)
         z = (z / self.vae.config.scaling_factor) + self.vae.config.shift_factor
-        image = self.vae.decode(z, return_dict=False)[0]
+        with vae_f16_overflow(self.vae, (model_config or {}).get("f16_overflow")):      # (an fp16-operand VAE applies it to its own counter)
+            image = self.vae.decode(z, return_dict=False)[0]
         image = self.image_processor.postprocess(image, output_type=output_type)
     self.maybe_free_model_hooks()
     if condition_scale != 1:

@@ -118,7 +118,8 @@ class LxFluxPipeline:
         MI355X engine; `vae/` becomes an `LxAutoencoderKL`; `text_encoder*/` + `tokenizer*/` a `FluxTextEncoders` (transformers on
         ROCm). Missing optional parts leave the corresponding slot empty. dtype float32 selects the engine's precise mode, float16 its
         fp16 operand mode (bfloat16: bf16 operands). The VAE follows the transformer into precise mode (`LxAutoencoderKL(precise=True)`:
-        split-bf16 operand pairs) and runs on bf16 operands otherwise."""
+        split-bf16 operand pairs) and into the fp16 operand mode (`LxAutoencoderKL(operands="fp16")`: fp16 operand images, saturation counted
+        and reported per encode / decode under model_config["f16_overflow"]); bfloat16 runs it on bf16 operands."""
         import json
         import os
         from safetensors.torch import load_file
@@ -160,7 +161,8 @@ class LxFluxPipeline:
             vc = json.load(open(os.path.join(vdir, "config.json"))) if os.path.isfile(os.path.join(vdir, "config.json")) else {}
             keep = ("in_channels", "out_channels", "latent_channels", "block_out_channels", "layers_per_block", "norm_num_groups",
                     "scaling_factor", "shift_factor")
-            vae = LxAutoencoderKL(load_dir(vdir), {k: vc[k] for k in keep if k in vc}, device, precise=dtype == torch.float32)
+            vae = LxAutoencoderKL(load_dir(vdir), {k: vc[k] for k in keep if k in vc}, device, precise=dtype == torch.float32,
+                                  operands="fp16" if dtype == torch.float16 else "bf16")
         if load_text_encoders and all(os.path.isdir(os.path.join(path, d)) for d in ("text_encoder", "tokenizer", "text_encoder_2", "tokenizer_2")):
             from .text import FluxTextEncoders
             text = FluxTextEncoders.from_pretrained(path, device, dtype)

@@ -4,15 +4,18 @@ from __future__ import annotations
 import torch
 
 
-def encode_images(pipeline, images):
+def encode_images(pipeline, images, f16_overflow=None):
     """VAE-encode + (x - shift) * scale + 2x2 pack + ids.  Needs `pipeline.vae`; VAE-free callers hand packed
-    latents to `Condition(latents=...)` instead (the VAE is outside the denoise hot path)."""
+    latents to `Condition(latents=...)` instead (the VAE is outside the denoise hot path).
+    f16_overflow: model_config["f16_overflow"] for this call, for a VAE on fp16 operands (None: the VAE's own setting)."""
+    from .generate import vae_f16_overflow
     if pipeline.vae is None or pipeline.image_processor is None:
         raise NotImplementedError("encode_images needs a VAE: construct LxFluxPipeline(vae=..., image_processor=...) or "
                                   "pass pre-encoded packed latents via Condition(latents=...)")
     images = pipeline.image_processor.preprocess(images)
     images = images.to(pipeline.device).to(pipeline.dtype)
-    z = pipeline.vae.encode(images).latent_dist.sample()
+    with vae_f16_overflow(pipeline.vae, f16_overflow):
+        z = pipeline.vae.encode(images).latent_dist.sample()
     z = (z - pipeline.vae.config.shift_factor) * pipeline.vae.config.scaling_factor
     tokens = pipeline._pack_latents(z, *z.shape)
     ids = pipeline._prepare_latent_image_ids(z.shape[0], z.shape[2], z.shape[3], pipeline.device, torch.float32)

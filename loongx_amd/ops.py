@@ -672,6 +672,46 @@ def softmax_rows_split(S: torch.Tensor, P: torch.Tensor, scale: float, n_valid: 
           "lx_softmax_rows_split")
 
 
+# The fp16-operand VAE's producers (operands="fp16"): fp16 images for LX_OPERANDS_F16 launches. f16_ovf: int32 device counter of the waves
+# that clipped a value to +-65504, or None (not reported). im2col3x3 takes the fp16 images viewed as 16-bit words.
+def _req_ovf(f16_ovf) -> None:
+    if f16_ovf is not None:
+        _req(f16_ovf, torch.int32, "f16_ovf")
+
+
+def groupnorm_silu_f16(x: torch.Tensor, gamma, beta, y: torch.Tensor, groups: int = 32, eps: float = 1e-6, silu: bool = True, f16_ovf=None) -> None:
+    """x fp32 [B, P, C] (contiguous) -> y fp16 [B, P, C] (contiguous), saturated to +-65504."""
+    B, P, Cc = x.shape
+    _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta"); _req(y, torch.float16, "y")
+    _req_ovf(f16_ovf)
+    if not (x.is_contiguous() and y.is_contiguous() and y.numel() == B * P * Cc):
+        raise ValueError("groupnorm_silu_f16: x and y contiguous, y as many elements as x")
+    nb = lib.lx_groupnorm_workspace_bytes(B, P, groups)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    check(lib.lx_groupnorm_silu_f16(x.data_ptr(), B, P, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps, int(silu), y.data_ptr(), ws.data_ptr(), nb,
+                                    _p(f16_ovf), _stream()), "lx_groupnorm_silu_f16")
+
+
+def softmax_rows_f16(S: torch.Tensor, P: torch.Tensor, scale: float, n_valid: Optional[int] = None) -> None:
+    """softmax_rows with fp16 probabilities; one entry point for both forms (n_valid None: every column of S is a key and P has as many)."""
+    _req(S, torch.float32, "S"); _req(P, torch.float16, "P")
+    nv = S.shape[1] if n_valid is None else int(n_valid)
+    if P.shape[0] != S.shape[0] or S.shape[1] < nv or P.shape[1] < nv or S.stride(1) != 1 or P.stride(1) != 1:
+        raise ValueError("softmax_rows_f16: S and P need the same rows, unit column strides and at least n_valid columns each")
+    check(lib.lx_softmax_rows_f16(S.data_ptr(), S.stride(0), scale, P.data_ptr(), P.stride(0), S.shape[0], nv, P.shape[1], _stream()), "lx_softmax_rows_f16")
+
+
+def convert_f16(dst: torch.Tensor, src: torch.Tensor, f16_ovf=None) -> None:
+    """dst fp16 = src (fp32 | bf16), saturated to +-65504 and counted in f16_ovf."""
+    _req(dst, torch.float16, "dst")
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"src: expected torch.float32 or torch.bfloat16, got {src.dtype}")
+    _req(src, src.dtype, "src"); _req_ovf(f16_ovf)
+    if dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+        raise ValueError("convert_f16: dst and src contiguous with the same number of elements")
+    check(lib.lx_convert_f16(dst.data_ptr(), src.data_ptr(), int(src.dtype == torch.bfloat16), dst.numel(), _p(f16_ovf), _stream()), "lx_convert_f16")
+
+
 # ---- CS3 / DGF -------------------------------------------------------------------------------------------
 def s4_scan(u, lam, w, D, y) -> None:
     B, H, Lq = u.shape

@@ -19,10 +19,19 @@ split-bf16 pair (hi = bf16(v), lo = bf16(v - hi), lo_off columns further in the 
 that are bf16-representable, FLUX.1's) or 3 (weights packed as [W_hi | W_lo], decided per tensor at load time) and the attention's q, k,
 v^T, probabilities (`lx_softmax_rows_split`) and output are pairs too. Biases and the GroupNorm affine are fp32 in both modes. Scratch per
 image in precise mode: P * Ppad * 8 bytes (fp32 scores + the bf16 probability pair).
+
+`operands="fp16"` (what `dtype=torch.float16` selects, as for the transformer; not with `precise`) keeps the bf16 path's launches one for one
+and stores every GEMM operand as IEEE fp16 instead (11 significand bits for bf16's 8): `lx_groupnorm_silu_f16`, `lx_convert_f16` and
+`lx_softmax_rows_f16` write the images, `lx_im2col3x3` gathers them as 16-bit words, the GEMMs are LX_OPERANDS_F16 launches on fp16 weight
+images (`.w16`, rounded from the fp32 weights). fp16 has 5 exponent bits: every producer saturates at +-65504 and counts the waves that did in
+`f16_ovf`; each encode / decode reads the counter once and applies `f16_overflow` ("raise" -> F16OverflowError, "warn", or "fallback": the call
+is computed again on the bf16 images, which stay resident for that). Probabilities below 2^-14 are fp16 subnormals: through 128x128 latents
+(P = 16384 tokens, 1024x1024 images) they cost nothing measurable, beyond that the attention's precision degrades towards bf16's.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from types import SimpleNamespace
 from typing import Dict, NamedTuple, Optional, Tuple
 
@@ -37,6 +46,51 @@ FLUX_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=16, block_
 
 def _pad_to(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+OPERANDS = ("bf16", "fp16")
+F16_OVERFLOW_POLICIES = ("raise", "warn", "fallback")              # flux.generate's, restated here: that module imports this one
+
+
+class _Operands16:
+    """The 16-bit operand format of the non-precise VAE in one place: the dtype of the operand buffers, the three row kernels that write them,
+    the weight images and the flags of the GEMM launches. bf16: today's calls, argument for argument. fp16: the saturating, counting
+    producers and LX_OPERANDS_F16 launches; `ovf` is the int32 device counter they share."""
+
+    def __init__(self, name: str, weights: Dict[str, torch.Tensor], ovf: Optional[torch.Tensor] = None):
+        self.name, self.f16, self.ovf = name, name == "fp16", ovf
+        self.dtype = torch.float16 if self.f16 else torch.bfloat16
+        self._w = weights
+
+    def weight(self, name: str) -> torch.Tensor:
+        return self._w[name] if self.f16 else self._w[name + ".w"]
+
+    def groupnorm_silu(self, x, gamma, beta, y, groups, eps, silu) -> None:
+        if self.f16:
+            ops.groupnorm_silu_f16(x, gamma, beta, y, groups, eps, silu, f16_ovf=self.ovf)
+        else:
+            ops.groupnorm_silu(x, gamma, beta, y, groups, eps, silu)
+
+    def convert(self, dst, src) -> None:
+        if self.f16:
+            ops.convert_f16(dst, src, f16_ovf=self.ovf)
+        else:
+            ops.convert(dst, src)
+
+    def softmax_rows(self, S, P, scale, n_valid=None) -> None:
+        if self.f16:
+            ops.softmax_rows_f16(S, P, scale, n_valid)
+        else:
+            ops.softmax_rows(S, P, scale, n_valid=n_valid)
+
+    def im2col3x3(self, x, out, mode) -> None:
+        """A 16-bit gather: the fp16 images go in viewed as 16-bit words."""
+        ops.im2col3x3(x.view(torch.bfloat16), out.view(torch.bfloat16), mode)
+
+    def gemm(self, A, W, C_, **kw) -> None:
+        if self.f16:
+            kw.update(f16=True, f16_ovf=self.ovf)
+        ops.gemm([ops.gemm_desc(A, W, C_, **kw)])
 
 
 class _Pair(NamedTuple):
@@ -64,7 +118,14 @@ class DiagonalGaussianDistribution:
 
 
 class LxAutoencoderKL:
-    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[dict] = None, device="cuda", precise: bool = False):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[dict] = None, device="cuda", precise: bool = False,
+                 operands: str = "bf16", f16_overflow: str = "raise"):
+        if operands not in OPERANDS:
+            raise ValueError(f"operands = {operands!r}: one of {OPERANDS}")
+        if f16_overflow not in F16_OVERFLOW_POLICIES:
+            raise ValueError(f"f16_overflow = {f16_overflow!r}: one of {F16_OVERFLOW_POLICIES}")
+        if precise and operands == "fp16":
+            raise ValueError('operands="fp16" with precise=True: the precise mode runs on split-bf16 pairs')
         cfg = dict(FLUX_VAE_CONFIG)
         cfg.update(config or {})
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
@@ -74,7 +135,14 @@ class LxAutoencoderKL:
         self.precise = bool(precise)
         self.G = cfg["norm_num_groups"]
         self.w: Dict[str, torch.Tensor] = {}
-        sd = state_dict
+        # fp16 operands: the fp16 weight images by layer name, the counter the producers share, and what building the images found
+        # (the engine's counters of the same names): weights beyond +-65504 (clipped), and the share of elements of the bf16 images that
+        # fp16 cannot hold exactly (magnitudes below 2^-14).
+        self.w16: Dict[str, torch.Tensor] = {}
+        self.f16_ovf: Optional[torch.Tensor] = None
+        self.w16_clipped, self.w16_inexact_share = 0, 0.0
+        self.f16_overflow = f16_overflow
+        self._sd = sd = state_dict                                               # (a reference: set_operands("fp16") rounds .w16 from the fp32 weights)
         for k, v in sd.items():
             if k.endswith(".weight") and v.dim() == 4:
                 self._pack_conv(k[: -len(".weight")], v, sd.get(k[: -len("weight")] + "bias"))
@@ -83,6 +151,24 @@ class LxAutoencoderKL:
             elif k.endswith(".weight") and v.dim() == 1:                        # GroupNorm affine
                 self.w[k[: -len(".weight")] + ".g"] = v.detach().to(self.device, torch.float32).contiguous()
                 self.w[k[: -len(".weight")] + ".b"] = sd[k[: -len("weight")] + "bias"].detach().to(self.device, torch.float32).contiguous()
+        self._op = _Operands16("bf16", self.w)
+        self.set_operands(operands)
+
+    @property
+    def operands(self) -> str:
+        return self._op.name
+
+    def set_operands(self, operands: str) -> None:
+        """Switch a non-precise instance between bf16 and fp16 operands. The fp16 weight images are built at the first switch to fp16 and
+        kept; the bf16 images always stay (the overflow fallback runs on them)."""
+        if operands not in OPERANDS:
+            raise ValueError(f"operands = {operands!r}: one of {OPERANDS}")
+        if operands == "fp16":
+            if self.precise:
+                raise ValueError('operands="fp16" with precise=True: the precise mode runs on split-bf16 pairs')
+            if not self.w16:
+                self._pack_w16()
+        self._op = _Operands16(operands, self.w16 if operands == "fp16" else self.w, self.f16_ovf if operands == "fp16" else None)
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def _pack_conv(self, name: str, w: torch.Tensor, b: Optional[torch.Tensor]) -> None:
@@ -109,6 +195,31 @@ class LxAutoencoderKL:
         self.w[name + ".w"], self.w[name + ".bias"] = Wp, bp
         self.w[name + ".shape"] = (co, ci, kh)
 
+    def _pack_w16(self) -> None:
+        """The fp16 image of every GEMM weight, in the layout of its bf16 image: the fp32 weight rounded to nearest even, SATURATED to
+        +-65504 (never inf) with the clipped elements counted in `w16_clipped`; `w16_inexact_share` as the engine defines it. One host
+        synchronisation."""
+        self.f16_ovf = torch.zeros(1, dtype=torch.int32, device=self.device)
+        stat = torch.zeros(2, dtype=torch.int64, device=self.device)            # [elements of the bf16 images fp16 cannot hold, clipped]
+        total = 0
+        for k, v in self._sd.items():
+            if not k.endswith(".weight") or v.dim() not in (2, 4):
+                continue
+            name = k[: -len(".weight")]
+            w = v if v.dim() == 4 else v[:, :, None, None]
+            co, ci, kh, kw = w.shape
+            W = w.detach().to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
+            Wb = self.w[name + ".w"]
+            img = torch.zeros(Wb.shape, dtype=torch.float16, device=self.device)
+            img[:co, : kh * kw * ci] = W.clamp(-65504.0, 65504.0).to(torch.float16)
+            real = Wb[:co, : kh * kw * ci]
+            stat[0] += (real.float().clamp(-65504.0, 65504.0).to(torch.float16).to(torch.bfloat16) != real).sum()
+            stat[1] += (W.abs() > 65504.0).sum()
+            total += W.numel()
+            self.w16[name] = img
+        lost, clipped = (int(n) for n in stat.tolist())
+        self.w16_inexact_share, self.w16_clipped = lost / max(total, 1), clipped
+
     # ---- building blocks (x: fp32 [B*H*W, C]) ----------------------------------------------------------------------------
     def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         C = x.shape[1]
@@ -116,16 +227,17 @@ class LxAutoencoderKL:
             y = torch.empty(x.shape[0], 2 * C, dtype=torch.bfloat16, device=self.device) if out is None else out
             ops.groupnorm_silu_split(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y, C, self.G, 1e-6, silu)
             return _Pair(y, C, C)
-        y = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device) if out is None else out
-        ops.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y.view(B, -1, C), self.G, 1e-6, silu)
+        y = torch.empty(x.shape, dtype=self._op.dtype, device=self.device) if out is None else out
+        self._op.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y.view(B, -1, C), self.G, 1e-6, silu)
         return y
 
     def _conv3(self, h: torch.Tensor, B: int, H: int, W: int, name: str, mode: int = 0, out: Optional[torch.Tensor] = None,
                epilogue: int = LX_EPI_STORE_F32) -> Tuple[torch.Tensor, int, int]:
-        """3x3 convolution of bf16 NHWC h [B*H*W, Cin] as im2col + GEMM; image by image so the im2col scratch stays one image
-        large. out: fp32 [B*Ho*Wo, Npad] (epilogue STORE_F32 / RESID_F32 accumulates into it) or bf16 (STORE_BF16).
+        """3x3 convolution of 16-bit NHWC h [B*H*W, Cin] as im2col + GEMM; image by image so the im2col scratch stays one image
+        large. out: fp32 [B*Ho*Wo, Npad] (epilogue STORE_F32 / RESID_F32 accumulates into it) or the operand format (STORE_BF16).
         Precise mode: h is a _Pair, the rows are [hi taps | lo taps] and the GEMM takes them with k_segs = 2 | 3."""
-        Wt, bias = self.w[name + ".w"], self.w[name + ".bias"]
+        bias = self.w[name + ".bias"]
+        Wt = self.w[name + ".w"] if self.precise else self._op.weight(name)
         Ho, Wo = (H // 2, W // 2) if mode == 1 else ((2 * H, 2 * W) if mode == 2 else (H, W))
         if self.precise:
             segs = self.w[name + ".segs"]
@@ -138,21 +250,23 @@ class LxAutoencoderKL:
                 ops.im2col3x3_split(hv[b:b + 1], h.C, h.lo, cols, mode)
                 ops.gemm([ops.gemm_desc(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp)])
             return out, Ho, Wo
+        op = self._op
         Cin = h.shape[1]
         Np, Kp = Wt.shape
         if out is None:
-            out = torch.empty(B * Ho * Wo, Np, dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
-        cols = torch.empty(Ho * Wo, Kp, dtype=torch.bfloat16, device=self.device)
+            out = torch.empty(B * Ho * Wo, Np, dtype=op.dtype if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
+        cols = torch.empty(Ho * Wo, Kp, dtype=op.dtype, device=self.device)
         hv = h.view(B, H, W, Cin)
         for b in range(B):
-            ops.im2col3x3(hv[b:b + 1], cols, mode)
-            ops.gemm([ops.gemm_desc(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue)])
+            op.im2col3x3(hv[b:b + 1], cols, mode)
+            op.gemm(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue)
         return out, Ho, Wo
 
     def _lin(self, a: torch.Tensor, name: str, out: Optional[torch.Tensor] = None, epilogue: int = LX_EPI_STORE_BF16) -> torch.Tensor:
         """Precise mode: a is a _Pair with lo = K (channel counts here are multiples of 64), and a bf16 store writes the output pair
         [M, 2 Npad] (lo half Npad columns after the hi half)."""
-        Wt, bias = self.w[name + ".w"], self.w[name + ".bias"]
+        bias = self.w[name + ".bias"]
+        Wt = self.w[name + ".w"] if self.precise else self._op.weight(name)
         if self.precise:
             segs = self.w[name + ".segs"]
             Np, Kp = Wt.shape[0], Wt.shape[1] // (segs - 1)
@@ -163,17 +277,17 @@ class LxAutoencoderKL:
             ops.gemm([ops.gemm_desc(a.t, Wt, out, bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp, c_lo_off=Np if pair_out else 0)])
             return out
         if out is None:
-            out = torch.empty(a.shape[0], Wt.shape[0], dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
-        ops.gemm([ops.gemm_desc(a, Wt, out, bias=bias, epilogue=epilogue)])
+            out = torch.empty(a.shape[0], Wt.shape[0], dtype=self._op.dtype if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
+        self._op.gemm(a, Wt, out, bias=bias, epilogue=epilogue)
         return out
 
     def _operand(self, x: torch.Tensor):
-        """The fp32 stream x [M, C] as a GEMM operand: bf16 [M, C], or in precise mode the pair [M, 2 * roundup(C, 8)] (`lx_split_bf16`; a
+        """The fp32 stream x [M, C] as a GEMM operand: bf16 | fp16 [M, C], or in precise mode the pair [M, 2 * roundup(C, 8)] (`lx_split_bf16`; a
         channel count that is no multiple of 4 -- the encoder's RGB input -- is zero-padded to one first, which is torch plumbing)."""
         M, C = x.shape
         if not self.precise:
-            xb = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
-            ops.convert(xb, x)
+            xb = torch.empty(x.shape, dtype=self._op.dtype, device=self.device)
+            self._op.convert(xb, x)
             return xb
         if C % 4:
             x = torch.nn.functional.pad(x, (0, _pad_to(C, 4) - C))
@@ -197,20 +311,20 @@ class LxAutoencoderKL:
             return self._attn_precise(x, B, P, p)
         if P % 64:
             return self._attn_ragged(x, B, P, p)
-        C = x.shape[1]
+        C, op = x.shape[1], self._op
         n = self._gn(x, B, p + ".group_norm", silu=False)
         q, k = self._lin(n, p + ".to_q"), self._lin(n, p + ".to_k")
-        Wv, bv = self.w[p + ".to_v.w"], self.w[p + ".to_v.bias"]
+        Wv, bv = op.weight(p + ".to_v"), self.w[p + ".to_v.bias"]
         S = torch.empty(P, P, dtype=torch.float32, device=self.device)
-        Pm = torch.empty(P, P, dtype=torch.bfloat16, device=self.device)
-        vT = torch.empty(C, P, dtype=torch.bfloat16, device=self.device)
-        o = torch.empty(B * P, C, dtype=torch.bfloat16, device=self.device)
+        Pm = torch.empty(P, P, dtype=op.dtype, device=self.device)
+        vT = torch.empty(C, P, dtype=op.dtype, device=self.device)
+        o = torch.empty(B * P, C, dtype=op.dtype, device=self.device)
         for b in range(B):
             r = slice(b * P, (b + 1) * P)
-            ops.gemm([ops.gemm_desc(q[r], k[r], S, epilogue=LX_EPI_STORE_F32)])                       # S = q k^T
-            ops.softmax_rows(S, Pm, 1.0 / math.sqrt(C))
-            ops.gemm([ops.gemm_desc(Wv, n[r], vT, epilogue=LX_EPI_STORE_BF16)])                       # v^T = Wv n^T (bias added below)
-            ops.gemm([ops.gemm_desc(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)])              # rows of P sum to 1: P (v + 1 bv^T) = P v + bv
+            op.gemm(q[r], k[r], S, epilogue=LX_EPI_STORE_F32)                                         # S = q k^T
+            op.softmax_rows(S, Pm, 1.0 / math.sqrt(C))
+            op.gemm(Wv, n[r], vT, epilogue=LX_EPI_STORE_BF16)                                         # v^T = Wv n^T (bias added below)
+            op.gemm(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)                                # rows of P sum to 1: P (v + 1 bv^T) = P v + bv
         self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
         return x
 
@@ -220,25 +334,25 @@ class LxAutoencoderKL:
         rows and, for the last image, into a zero tail that both buffers carry: every row a GEMM reads lies inside its allocation and
         is finite (real rows of a neighbour, or zeros). Columns [P, Ppad) of S and of v^T are therefore finite garbage; the softmax
         reads none of the former and writes exact zeros for those keys, so the latter contribute nothing to P v."""
-        C = x.shape[1]
+        C, op = x.shape[1], self._op
         Pp = _pad_to(P, 64)
         rows = (B - 1) * P + Pp                                                                       # the last image's Ppad rows end here
-        n = torch.zeros(rows, C, dtype=torch.bfloat16, device=self.device)
-        k = torch.zeros(rows, C, dtype=torch.bfloat16, device=self.device)
+        n = torch.zeros(rows, C, dtype=op.dtype, device=self.device)
+        k = torch.zeros(rows, C, dtype=op.dtype, device=self.device)
         self._gn(x, B, p + ".group_norm", silu=False, out=n[: B * P])
         q = self._lin(n[: B * P], p + ".to_q")
         self._lin(n[: B * P], p + ".to_k", out=k[: B * P])
-        Wv, bv = self.w[p + ".to_v.w"], self.w[p + ".to_v.bias"]
+        Wv, bv = op.weight(p + ".to_v"), self.w[p + ".to_v.bias"]
         S = torch.empty(P, Pp, dtype=torch.float32, device=self.device)
-        Pm = torch.empty(P, Pp, dtype=torch.bfloat16, device=self.device)
-        vT = torch.empty(C, Pp, dtype=torch.bfloat16, device=self.device)
-        o = torch.empty(B * P, C, dtype=torch.bfloat16, device=self.device)
+        Pm = torch.empty(P, Pp, dtype=op.dtype, device=self.device)
+        vT = torch.empty(C, Pp, dtype=op.dtype, device=self.device)
+        o = torch.empty(B * P, C, dtype=op.dtype, device=self.device)
         for b in range(B):
             r, rp = slice(b * P, (b + 1) * P), slice(b * P, b * P + Pp)
-            ops.gemm([ops.gemm_desc(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32)])                      # S[:, :P] = q k^T
-            ops.softmax_rows(S, Pm, 1.0 / math.sqrt(C), n_valid=P)                                    # Pm[:, P:] = +0
-            ops.gemm([ops.gemm_desc(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16)])                      # v^T[:, :P] = Wv n^T
-            ops.gemm([ops.gemm_desc(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)])
+            op.gemm(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32)                                        # S[:, :P] = q k^T
+            op.softmax_rows(S, Pm, 1.0 / math.sqrt(C), n_valid=P)                                     # Pm[:, P:] = +0
+            op.gemm(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16)                                        # v^T[:, :P] = Wv n^T
+            op.gemm(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)
         self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
         return x
 
@@ -279,15 +393,48 @@ class LxAutoencoderKL:
         return t.to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
 
     def _input(self, t: torch.Tensor):
-        """NCHW input -> the operand of conv_in: NHWC rows [B*H*W, C], bf16 or (precise mode) the pair of the fp32 values."""
-        if self.precise:
+        """NCHW input -> the operand of conv_in: NHWC rows [B*H*W, C], bf16, fp16 (saturated and counted) or (precise mode) the pair of
+        the fp32 values."""
+        if self.precise or self._op.f16:
             return self._operand(t.to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous())
         return self._nhwc_bf16(t).view(-1, t.shape[1])
+
+    def _checked(self, run, what: str):
+        """run() under the fp16 overflow contract (a plain call in the other modes): the counter is zeroed, and read once when the call
+        has been enqueued -- 4 bytes; the caller reads the result anyway."""
+        if not self._op.f16:
+            return run()
+        policy = self.f16_overflow
+        if policy not in F16_OVERFLOW_POLICIES:
+            raise ValueError(f"f16_overflow = {policy!r}: one of {F16_OVERFLOW_POLICIES}")
+        self.f16_ovf.zero_()
+        out = run()
+        n_sat = int(self.f16_ovf.item())
+        if not n_sat and not self.w16_clipped:
+            return out
+        from .flux.generate import F16OverflowError
+        msg = (f"VAE {what} on fp16 operands: {n_sat} producer wave(s) clipped an operand to +-65504, {self.w16_clipped} weight(s) were "
+               f"clipped building the fp16 images")
+        if policy == "raise":
+            raise F16OverflowError(msg + '; f16_overflow="fallback" recomputes such calls with bf16 operands, "warn" keeps them')
+        if policy == "warn":
+            warnings.warn(msg + "; the result was kept", RuntimeWarning, stacklevel=3)
+            return out
+        warnings.warn(msg + f"; recomputing this {what} with bf16 operands", RuntimeWarning, stacklevel=3)
+        f16, self._op = self._op, _Operands16("bf16", self.w)
+        try:
+            return run()
+        finally:
+            self._op = f16
 
     # ---- public surface -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
         """z [B, latent, h, w] (any h, w >= 1) -> image [B, 3, 8h, 8w] fp32."""
+        img = self._checked(lambda: self._decode(z), "decode")
+        return SimpleNamespace(sample=img) if return_dict else (img,)
+
+    def _decode(self, z: torch.Tensor) -> torch.Tensor:
         cfg = self.config
         B, _, H, W = z.shape
         x, _, _ = self._conv3(self._input(z), B, H, W, "decoder.conv_in")
@@ -300,8 +447,7 @@ class LxAutoencoderKL:
                 x, H, W = self._conv3(self._operand(x), B, H, W, f"decoder.up_blocks.{i}.upsamplers.0.conv", mode=2)
         h = self._gn(x, B, "decoder.conv_norm_out")
         y, _, _ = self._conv3(h, B, H, W, "decoder.conv_out")
-        img = y[:, : cfg.out_channels].reshape(B, H, W, cfg.out_channels).permute(0, 3, 1, 2).contiguous()
-        return SimpleNamespace(sample=img) if return_dict else (img,)
+        return y[:, : cfg.out_channels].reshape(B, H, W, cfg.out_channels).permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
     def encode(self, images: torch.Tensor, return_dict: bool = True):
@@ -311,6 +457,13 @@ class LxAutoencoderKL:
         nd = len(cfg.block_out_channels) - 1
         if H % (1 << nd) or W % (1 << nd):
             raise ValueError(f"image {H}x{W}: sides must be multiples of {1 << nd} (the encoder halves them {nd} times)")
+        d = DiagonalGaussianDistribution(self._checked(lambda: self._encode(images), "encode"))
+        return SimpleNamespace(latent_dist=d) if return_dict else (d,)
+
+    def _encode(self, images: torch.Tensor) -> torch.Tensor:
+        cfg = self.config
+        B, _, H, W = images.shape
+        nd = len(cfg.block_out_channels) - 1
         x, _, _ = self._conv3(self._input(images), B, H, W, "encoder.conv_in")
         for i in range(len(cfg.block_out_channels)):
             for j in range(cfg.layers_per_block):
@@ -320,9 +473,7 @@ class LxAutoencoderKL:
         x = self._mid(x, B, H, W, "encoder.mid_block")
         h = self._gn(x, B, "encoder.conv_norm_out")
         y, _, _ = self._conv3(h, B, H, W, "encoder.conv_out")
-        params = y[:, : 2 * cfg.latent_channels].reshape(B, H, W, 2 * cfg.latent_channels).permute(0, 3, 1, 2).contiguous()
-        d = DiagonalGaussianDistribution(params)
-        return SimpleNamespace(latent_dist=d) if return_dict else (d,)
+        return y[:, : 2 * cfg.latent_channels].reshape(B, H, W, 2 * cfg.latent_channels).permute(0, 3, 1, 2).contiguous()
 
     def to(self, *a, **k):
         return self
