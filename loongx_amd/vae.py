@@ -13,20 +13,28 @@ gives the pad keys probability +0 (multiples of 64 take the unpadded launches). 
 + bf16 probabilities). Parameter names are diffusers' (`decoder.up_blocks.0.resnets.1.conv1.weight` ...),
 so `vae/diffusion_pytorch_model.safetensors` of a FLUX.1 checkpoint loads as is.
 
-`precise=True` (what `dtype=torch.float32` selects, as for the transformer) keeps the fp32 residual stream and makes every GEMM operand a
-split-bf16 pair (hi = bf16(v), lo = bf16(v - hi), lo_off columns further in the same row): `lx_groupnorm_silu_split` writes pairs,
-`lx_split_bf16` replaces the bf16 casts, `lx_im2col3x3_split` gathers [hi taps | lo taps] rows, the GEMMs run with k_segs = 2 (weights
-that are bf16-representable, FLUX.1's) or 3 (weights packed as [W_hi | W_lo], decided per tensor at load time) and the attention's q, k,
-v^T, probabilities (`lx_softmax_rows_split`) and output are pairs too. Biases and the GroupNorm affine are fp32 in both modes. Scratch per
-image in precise mode: P * Ppad * 8 bytes (fp32 scores + the bf16 probability pair).
+The layers (`_gn`, `_conv3`, `_lin`, `_operand`, `_input`, `_attn`) exist once, written against operand handles (`_Operand`: tensor,
+channel count, lo offset) and the instance's operand policy `_op`, which owns what differs by format: buffers, the row kernels that
+fill them, the weight images and their packing, and the GEMM descriptor. Three formats, two policy classes:
 
-`operands="fp16"` (what `dtype=torch.float16` selects, as for the transformer; not with `precise`) keeps the bf16 path's launches one for one
-and stores every GEMM operand as IEEE fp16 instead (11 significand bits for bf16's 8): `lx_groupnorm_silu_f16`, `lx_convert_f16` and
-`lx_softmax_rows_f16` write the images, `lx_im2col3x3` gathers them as 16-bit words, the GEMMs are LX_OPERANDS_F16 launches on fp16 weight
-images (`.w16`, rounded from the fp32 weights). fp16 has 5 exponent bits: every producer saturates at +-65504 and counts the waves that did in
-`f16_ovf`; each encode / decode reads the counter once and applies `f16_overflow` ("raise" -> F16OverflowError, "warn", or "fallback": the call
-is computed again on the bf16 images, which stay resident for that). Probabilities below 2^-14 are fp16 subnormals: through 128x128 latents
-(P = 16384 tokens, 1024x1024 images) they cost nothing measurable, beyond that the attention's precision degrades towards bf16's.
+bf16 (`_Operands16`, the default): the launches named above.
+
+`operands="fp16"` (`_Operands16` too; what `dtype=torch.float16` selects, as for the transformer; not with `precise`) keeps the bf16 path's
+launches one for one and stores every GEMM operand as IEEE fp16 instead (11 significand bits for bf16's 8): `lx_groupnorm_silu_f16`,
+`lx_convert_f16` and `lx_softmax_rows_f16` write the images, `lx_im2col3x3` gathers them as 16-bit words, the GEMMs are LX_OPERANDS_F16
+launches on fp16 weight images (`.w16`, rounded from the fp32 weights). fp16 has 5 exponent bits: every producer saturates at +-65504 and
+counts the waves that did in `f16_ovf`; each encode / decode reads the counter once and applies `f16_overflow` ("raise" -> F16OverflowError,
+"warn", or "fallback": the call is computed again on the bf16 images, which stay resident for that). Probabilities below 2^-14 are fp16
+subnormals: through 128x128 latents (P = 16384 tokens, 1024x1024 images) they cost nothing measurable, beyond that the attention's
+precision degrades towards bf16's.
+
+`precise=True` (`_OperandsSplit`; what `dtype=torch.float32` selects, as for the transformer) makes every GEMM operand a split-bf16 pair
+(hi = bf16(v), lo = bf16(v - hi), lo columns further in the same row): `lx_groupnorm_silu_split` writes pairs, `lx_split_bf16` replaces
+the casts, `lx_im2col3x3_split` gathers [hi taps | lo taps] rows, the GEMMs run with k_segs = 2 (weights that are bf16-representable,
+FLUX.1's) or 3 (weights packed as [W_hi | W_lo], decided per tensor at load time) and the attention's q, k, v^T, probabilities
+(`lx_softmax_rows_split`) and output are pairs too. Scratch per image: P * Ppad * 8 bytes (fp32 scores + the bf16 probability pair).
+
+The residual stream, the biases and the GroupNorm affine are fp32 in every format.
 """
 from __future__ import annotations
 
@@ -52,52 +60,146 @@ OPERANDS = ("bf16", "fp16")
 F16_OVERFLOW_POLICIES = ("raise", "warn", "fallback")              # flux.generate's, restated here: that module imports this one
 
 
-class _Operands16:
-    """The 16-bit operand format of the non-precise VAE in one place: the dtype of the operand buffers, the three row kernels that write them,
-    the weight images and the flags of the GEMM launches. bf16: today's calls, argument for argument. fp16: the saturating, counting
-    producers and LX_OPERANDS_F16 launches; `ovf` is the int32 device counter they share."""
-
-    def __init__(self, name: str, weights: Dict[str, torch.Tensor], ovf: Optional[torch.Tensor] = None):
-        self.name, self.f16, self.ovf = name, name == "fp16", ovf
-        self.dtype = torch.float16 if self.f16 else torch.bfloat16
-        self._w = weights
-
-    def weight(self, name: str) -> torch.Tensor:
-        return self._w[name] if self.f16 else self._w[name + ".w"]
-
-    def groupnorm_silu(self, x, gamma, beta, y, groups, eps, silu) -> None:
-        if self.f16:
-            ops.groupnorm_silu_f16(x, gamma, beta, y, groups, eps, silu, f16_ovf=self.ovf)
-        else:
-            ops.groupnorm_silu(x, gamma, beta, y, groups, eps, silu)
-
-    def convert(self, dst, src) -> None:
-        if self.f16:
-            ops.convert_f16(dst, src, f16_ovf=self.ovf)
-        else:
-            ops.convert(dst, src)
-
-    def softmax_rows(self, S, P, scale, n_valid=None) -> None:
-        if self.f16:
-            ops.softmax_rows_f16(S, P, scale, n_valid)
-        else:
-            ops.softmax_rows(S, P, scale, n_valid=n_valid)
-
-    def im2col3x3(self, x, out, mode) -> None:
-        """A 16-bit gather: the fp16 images go in viewed as 16-bit words."""
-        ops.im2col3x3(x.view(torch.bfloat16), out.view(torch.bfloat16), mode)
-
-    def gemm(self, A, W, C_, **kw) -> None:
-        if self.f16:
-            kw.update(f16=True, f16_ovf=self.ovf)
-        ops.gemm([ops.gemm_desc(A, W, C_, **kw)])
-
-
-class _Pair(NamedTuple):
-    """A GEMM operand of the precise mode: t bf16 [M, ld] with the hi halves of the C channels at columns [0, C), the lo halves at [lo, lo + C)."""
+class _Operand(NamedTuple):
+    """A GEMM operand: t [M, ld] holds the C channels at columns [0, C) -- bf16 or fp16 values with lo = 0, or the hi halves of a split-bf16
+    pair whose lo halves lie at [lo, lo + C) of the same row."""
     t: torch.Tensor
     C: int
     lo: int
+
+    def rows(self, r: slice) -> "_Operand":
+        return _Operand(self.t[r], self.C, self.lo)
+
+
+def _im2col_weight(w: torch.Tensor, device) -> torch.Tensor:
+    """[Cout, Cin, kh, kw] (a Linear's [Cout, Cin] is a 1x1) -> fp32 [Npad, Kpad] with column = (dy*kw + dx)*Cin + c (the im2col order), zero
+    padded to the GEMM's granules (N % 8, K % 64). Every weight image is an elementwise rounding of this one, so its pads are +0 too."""
+    if w.dim() == 2:
+        w = w[:, :, None, None]
+    co, ci, kh, kw = w.shape
+    W = torch.zeros(_pad_to(co, 8), _pad_to(kh * kw * ci, 64), dtype=torch.float32, device=device)
+    W[:co, : kh * kw * ci] = w.detach().to(device, torch.float32).permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
+    return W
+
+
+class _Operands:
+    """What the layers ask of an operand format. `weights` is the instance's `.w` (or `.w16`), shared, not copied."""
+    name, f16, dtype = "bf16", False, torch.bfloat16
+
+    def __init__(self, weights: Dict[str, torch.Tensor], device):
+        self._w, self.device = weights, device
+
+    def out(self, M: int, Np: int, epilogue: int):
+        """The output of a GEMM: the fp32 stream [M, Np] (STORE_F32 / RESID_F32) or an operand (STORE_BF16)."""
+        return self.operand(M, Np) if epilogue == LX_EPI_STORE_BF16 else torch.empty(M, Np, dtype=torch.float32, device=self.device)
+
+    def input(self, t: torch.Tensor) -> _Operand:
+        """NCHW input -> the operand of conv_in: NHWC rows [B*H*W, C]."""
+        return self.from_stream(t.to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous())
+
+    def gemm(self, A: _Operand, W: _Operand, out, *, N: int, K: int, bias=None, epilogue: int) -> None:
+        """out (+)= A W^T (+ bias). W: a weight image (`weight(name)`) or another operand as the [N, K] matrix; out as `out()` gives it."""
+        C_, c_lo = (out.t, out.lo) if isinstance(out, _Operand) else (out, 0)
+        ops.gemm([ops.gemm_desc(A.t, W.t, C_, bias=bias, epilogue=epilogue, N=N, K=K, a_lo_off=A.lo, c_lo_off=c_lo, **self._gemm_kw(W))])
+
+
+class _Operands16(_Operands):
+    """bf16 and fp16: operands are [rows, C] in `dtype`. bf16: `lx_groupnorm_silu`, `lx_convert`, `lx_softmax_rows` / `_valid` on the `.w`
+    images. fp16: the saturating, counting producers and LX_OPERANDS_F16 launches on the `.w16` images; `ovf` is the int32 device counter
+    they share."""
+
+    def __init__(self, name: str, weights: Dict[str, torch.Tensor], device, ovf: Optional[torch.Tensor] = None):
+        super().__init__(weights, device)
+        self.name, self.f16, self.ovf = name, name == "fp16", ovf
+        self.dtype = torch.float16 if self.f16 else torch.bfloat16
+
+    def operand(self, rows: int, C: int, zero: bool = False) -> _Operand:
+        return _Operand((torch.zeros if zero else torch.empty)(rows, C, dtype=self.dtype, device=self.device), C, 0)
+
+    def pack(self, name: str, W: torch.Tensor) -> torch.Tensor:
+        return W.to(torch.bfloat16)
+
+    def weight(self, name: str) -> _Operand:
+        t = self._w[name] if self.f16 else self._w[name + ".w"]
+        return _Operand(t, t.shape[1], 0)
+
+    def _gemm_kw(self, W: _Operand) -> dict:
+        return dict(f16=True, f16_ovf=self.ovf) if self.f16 else {}
+
+    def groupnorm_silu(self, x, gamma, beta, y: _Operand, groups, eps, silu) -> None:
+        if self.f16:
+            ops.groupnorm_silu_f16(x, gamma, beta, y.t.view(x.shape), groups, eps, silu, f16_ovf=self.ovf)
+        else:
+            ops.groupnorm_silu(x, gamma, beta, y.t.view(x.shape), groups, eps, silu)
+
+    def from_stream(self, x: torch.Tensor) -> _Operand:
+        y = self.operand(*x.shape)
+        if self.f16:
+            ops.convert_f16(y.t, x, f16_ovf=self.ovf)
+        else:
+            ops.convert(y.t, x)
+        return y
+
+    def input(self, t: torch.Tensor) -> _Operand:
+        if self.f16:                                                            # (saturated and counted)
+            return super().input(t)
+        C = t.shape[1]                                                          # bf16: a torch cast
+        return _Operand(t.to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).view(-1, C), C, 0)
+
+    def im2col3x3(self, x: torch.Tensor, h: _Operand, cols: _Operand, mode: int) -> None:
+        """A 16-bit gather: the fp16 images go in viewed as 16-bit words."""
+        ops.im2col3x3(x.view(torch.bfloat16), cols.t.view(torch.bfloat16), mode)
+
+    def softmax_rows(self, S, Pm: _Operand, scale, P: int, Ppad: int) -> None:
+        n_valid = None if Ppad == P else P                                      # (bf16: lx_softmax_rows | lx_softmax_rows_valid)
+        if self.f16:
+            ops.softmax_rows_f16(S, Pm.t, scale, n_valid)
+        else:
+            ops.softmax_rows(S, Pm.t, scale, n_valid=n_valid)
+
+
+class _OperandsSplit(_Operands):
+    """precise: operands are bf16 pairs [rows, 2 lo] = [hi | lo] with lo = roundup(C, 8); a bf16 store writes a pair as well. A GEMM is a
+    k_segs = 3 launch (hi hi + lo hi + hi lo) where W carries a lo half -- the weights packed as [W_hi | W_lo], and the attention's three
+    products -- and a k_segs = 2 launch on a weight that is bf16-representable."""
+
+    def operand(self, rows: int, C: int, zero: bool = False) -> _Operand:
+        lo = _pad_to(C, 8)
+        return _Operand((torch.zeros if zero else torch.empty)(rows, 2 * lo, dtype=torch.bfloat16, device=self.device), C, lo)
+
+    def pack(self, name: str, W: torch.Tensor) -> torch.Tensor:
+        """Records `<name>.segs`, the k_segs of the launches on this tensor: 3 with the image [W_hi | W_lo] when any element has a bf16
+        residual, else 2 on the plain image. to_v is the A operand of v^T = Wv n^T against the pair n, so it always carries a lo half."""
+        Wh = W.to(torch.bfloat16)
+        Wl = (W - Wh.float()).to(torch.bfloat16)
+        segs = self._w[name + ".segs"] = 3 if name.endswith(".to_v") or bool((Wl != 0).any()) else 2
+        return torch.cat([Wh, Wl], 1) if segs == 3 else Wh
+
+    def weight(self, name: str) -> _Operand:
+        t = self._w[name + ".w"]
+        Kp = t.shape[1] // (self._w[name + ".segs"] - 1)
+        return _Operand(t, Kp, t.shape[1] - Kp)
+
+    def _gemm_kw(self, W: _Operand) -> dict:
+        return dict(k_segs=3 if W.lo else 2)
+
+    def groupnorm_silu(self, x, gamma, beta, y: _Operand, groups, eps, silu) -> None:
+        ops.groupnorm_silu_split(x, gamma, beta, y.t, y.lo, groups, eps, silu)
+
+    def from_stream(self, x: torch.Tensor) -> _Operand:
+        """`lx_split_bf16`; a channel count that is no multiple of 4 -- the encoder's RGB input -- is zero-padded to one first (torch plumbing)."""
+        M, C = x.shape
+        if C % 4:
+            x = torch.nn.functional.pad(x, (0, _pad_to(C, 4) - C))
+        y = self.operand(M, C)
+        ops.split_bf16(x, y.t, y.lo)
+        return y
+
+    def im2col3x3(self, x: torch.Tensor, h: _Operand, cols: _Operand, mode: int) -> None:
+        ops.im2col3x3_split(x, h.C, h.lo, cols.t, mode)
+
+    def softmax_rows(self, S, Pm: _Operand, scale, P: int, Ppad: int) -> None:
+        ops.softmax_rows_split(S, Pm.t, scale, P, Ppad, Pm.lo)                  # Pm[:, P:Ppad] = +0, both halves
 
 
 class DiagonalGaussianDistribution:
@@ -143,15 +245,13 @@ class LxAutoencoderKL:
         self.w16_clipped, self.w16_inexact_share = 0, 0.0
         self.f16_overflow = f16_overflow
         self._sd = sd = state_dict                                               # (a reference: set_operands("fp16") rounds .w16 from the fp32 weights)
+        self._op = _OperandsSplit(self.w, self.device) if self.precise else _Operands16("bf16", self.w, self.device)
         for k, v in sd.items():
-            if k.endswith(".weight") and v.dim() == 4:
+            if k.endswith(".weight") and v.dim() in (2, 4):                     # Linear | Conv2d
                 self._pack_conv(k[: -len(".weight")], v, sd.get(k[: -len("weight")] + "bias"))
-            elif k.endswith(".weight") and v.dim() == 2:
-                self._pack_conv(k[: -len(".weight")], v[:, :, None, None], sd.get(k[: -len("weight")] + "bias"))
             elif k.endswith(".weight") and v.dim() == 1:                        # GroupNorm affine
                 self.w[k[: -len(".weight")] + ".g"] = v.detach().to(self.device, torch.float32).contiguous()
                 self.w[k[: -len(".weight")] + ".b"] = sd[k[: -len("weight")] + "bias"].detach().to(self.device, torch.float32).contiguous()
-        self._op = _Operands16("bf16", self.w)
         self.set_operands(operands)
 
     @property
@@ -163,37 +263,23 @@ class LxAutoencoderKL:
         kept; the bf16 images always stay (the overflow fallback runs on them)."""
         if operands not in OPERANDS:
             raise ValueError(f"operands = {operands!r}: one of {OPERANDS}")
-        if operands == "fp16":
-            if self.precise:
-                raise ValueError('operands="fp16" with precise=True: the precise mode runs on split-bf16 pairs')
-            if not self.w16:
-                self._pack_w16()
-        self._op = _Operands16(operands, self.w16 if operands == "fp16" else self.w, self.f16_ovf if operands == "fp16" else None)
+        if operands == "fp16" and self.precise:
+            raise ValueError('operands="fp16" with precise=True: the precise mode runs on split-bf16 pairs')
+        if operands == "fp16" and not self.w16:
+            self._pack_w16()
+        if not self.precise:
+            self._op = _Operands16(operands, self.w16 if operands == "fp16" else self.w, self.device, self.f16_ovf if operands == "fp16" else None)
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def _pack_conv(self, name: str, w: torch.Tensor, b: Optional[torch.Tensor]) -> None:
-        """[Cout, Cin, kh, kw] -> bf16 [Npad, Kpad] with column = (dy*kw + dx)*Cin + c (the im2col order), zero padded to the
-        GEMM's granules (K % 64, N % 8). Precise mode also records `<name>.segs` and widens the image to [Npad, 2 Kpad] =
-        [W_hi | W_lo] where that is 3."""
-        co, ci, kh, kw = w.shape
-        W = w.detach().to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
-        Np, Kp = _pad_to(co, 8), _pad_to(kh * kw * ci, 64)
-        Wh = W.to(torch.bfloat16)
-        if self.precise:
-            # k_segs of the launches on this tensor: 3 with the image [W_hi | W_lo] when any element has a bf16 residual, else 2 on the
-            # plain image. to_v is the A operand of v^T = Wv n^T against the pair n (k_segs = 3), so it always carries a lo half.
-            Wl = (W - Wh.float()).to(torch.bfloat16)
-            segs = 3 if name.endswith(".to_v") or bool((Wl != 0).any()) else 2
-            self.w[name + ".segs"] = segs
-        Wp = torch.zeros(Np, Kp * (2 if self.precise and segs == 3 else 1), dtype=torch.bfloat16, device=self.device)
-        Wp[:co, : kh * kw * ci] = Wh
-        if self.precise and segs == 3:
-            Wp[:co, Kp: Kp + kh * kw * ci] = Wl
-        bp = torch.zeros(Np, dtype=torch.float32, device=self.device)
+        """`<name>.w`: the policy's image of the weight in `_im2col_weight`'s layout (bf16 [Npad, Kpad]; precise mode: `<name>.segs`
+        and, where that is 3, [Npad, 2 Kpad] = [W_hi | W_lo]); `<name>.bias`: fp32 [Npad]; `<name>.shape`: (Cout, Cin, kh)."""
+        Wp = self._op.pack(name, _im2col_weight(w, self.device))
+        bp = torch.zeros(Wp.shape[0], dtype=torch.float32, device=self.device)
         if b is not None:
-            bp[:co] = b.detach().to(self.device, torch.float32)
+            bp[: w.shape[0]] = b.detach().to(self.device, torch.float32)
         self.w[name + ".w"], self.w[name + ".bias"] = Wp, bp
-        self.w[name + ".shape"] = (co, ci, kh)
+        self.w[name + ".shape"] = (w.shape[0], w.shape[1], w.shape[2] if w.dim() == 4 else 1)
 
     def _pack_w16(self) -> None:
         """The fp16 image of every GEMM weight, in the layout of its bf16 image: the fp32 weight rounded to nearest even, SATURATED to
@@ -206,95 +292,50 @@ class LxAutoencoderKL:
             if not k.endswith(".weight") or v.dim() not in (2, 4):
                 continue
             name = k[: -len(".weight")]
-            w = v if v.dim() == 4 else v[:, :, None, None]
-            co, ci, kh, kw = w.shape
-            W = w.detach().to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
-            Wb = self.w[name + ".w"]
-            img = torch.zeros(Wb.shape, dtype=torch.float16, device=self.device)
-            img[:co, : kh * kw * ci] = W.clamp(-65504.0, 65504.0).to(torch.float16)
-            real = Wb[:co, : kh * kw * ci]
-            stat[0] += (real.float().clamp(-65504.0, 65504.0).to(torch.float16).to(torch.bfloat16) != real).sum()
+            W, Wb = _im2col_weight(v, self.device), self.w[name + ".w"]         # (the pads are zeros in both and count as exact)
+            stat[0] += (Wb.float().clamp(-65504.0, 65504.0).to(torch.float16).to(torch.bfloat16) != Wb).sum()
             stat[1] += (W.abs() > 65504.0).sum()
-            total += W.numel()
-            self.w16[name] = img
+            total += v.numel()
+            self.w16[name] = W.clamp(-65504.0, 65504.0).to(torch.float16)
         lost, clipped = (int(n) for n in stat.tolist())
         self.w16_inexact_share, self.w16_clipped = lost / max(total, 1), clipped
 
     # ---- building blocks (x: fp32 [B*H*W, C]) ----------------------------------------------------------------------------
-    def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _gn(self, x: torch.Tensor, B: int, name: str, silu: bool = True, out: Optional[_Operand] = None) -> _Operand:
         C = x.shape[1]
-        if self.precise:
-            y = torch.empty(x.shape[0], 2 * C, dtype=torch.bfloat16, device=self.device) if out is None else out
-            ops.groupnorm_silu_split(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y, C, self.G, 1e-6, silu)
-            return _Pair(y, C, C)
-        y = torch.empty(x.shape, dtype=self._op.dtype, device=self.device) if out is None else out
-        self._op.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y.view(B, -1, C), self.G, 1e-6, silu)
+        y = self._op.operand(x.shape[0], C) if out is None else out
+        self._op.groupnorm_silu(x.view(B, -1, C), self.w[name + ".g"], self.w[name + ".b"], y, self.G, 1e-6, silu)
         return y
 
-    def _conv3(self, h: torch.Tensor, B: int, H: int, W: int, name: str, mode: int = 0, out: Optional[torch.Tensor] = None,
+    def _conv3(self, h: _Operand, B: int, H: int, W: int, name: str, mode: int = 0, out: Optional[torch.Tensor] = None,
                epilogue: int = LX_EPI_STORE_F32) -> Tuple[torch.Tensor, int, int]:
-        """3x3 convolution of 16-bit NHWC h [B*H*W, Cin] as im2col + GEMM; image by image so the im2col scratch stays one image
-        large. out: fp32 [B*Ho*Wo, Npad] (epilogue STORE_F32 / RESID_F32 accumulates into it) or the operand format (STORE_BF16).
-        Precise mode: h is a _Pair, the rows are [hi taps | lo taps] and the GEMM takes them with k_segs = 2 | 3."""
-        bias = self.w[name + ".bias"]
-        Wt = self.w[name + ".w"] if self.precise else self._op.weight(name)
+        """3x3 convolution of the NHWC operand h [B*H*W, Cin] as im2col + GEMM; image by image so the im2col scratch stays one image
+        large. out: the fp32 stream [B*Ho*Wo, Npad] (epilogue STORE_F32, or RESID_F32, which accumulates into it)."""
+        op, Wt, bias = self._op, self._op.weight(name), self.w[name + ".bias"]
+        Np, Kp = Wt.t.shape[0], Wt.C
         Ho, Wo = (H // 2, W // 2) if mode == 1 else ((2 * H, 2 * W) if mode == 2 else (H, W))
-        if self.precise:
-            segs = self.w[name + ".segs"]
-            Np, Kp = Wt.shape[0], Wt.shape[1] // (segs - 1)
-            if out is None:
-                out = torch.empty(B * Ho * Wo, Np, dtype=torch.bfloat16 if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
-            cols = torch.empty(Ho * Wo, 2 * Kp, dtype=torch.bfloat16, device=self.device)
-            hv = h.t.view(B, H, W, h.t.shape[1])
-            for b in range(B):
-                ops.im2col3x3_split(hv[b:b + 1], h.C, h.lo, cols, mode)
-                ops.gemm([ops.gemm_desc(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp)])
-            return out, Ho, Wo
-        op = self._op
-        Cin = h.shape[1]
-        Np, Kp = Wt.shape
         if out is None:
-            out = torch.empty(B * Ho * Wo, Np, dtype=op.dtype if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
-        cols = torch.empty(Ho * Wo, Kp, dtype=op.dtype, device=self.device)
-        hv = h.view(B, H, W, Cin)
+            out = torch.empty(B * Ho * Wo, Np, dtype=torch.float32, device=self.device)
+        cols = op.operand(Ho * Wo, Kp)                                                                # gather rows: [taps], or [hi taps | lo taps]
+        hv = h.t.view(B, H, W, h.t.shape[1])
         for b in range(B):
-            op.im2col3x3(hv[b:b + 1], cols, mode)
-            op.gemm(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], bias=bias, epilogue=epilogue)
+            op.im2col3x3(hv[b:b + 1], h, cols, mode)
+            op.gemm(cols, Wt, out[b * Ho * Wo:(b + 1) * Ho * Wo], N=Np, K=Kp, bias=bias, epilogue=epilogue)
         return out, Ho, Wo
 
-    def _lin(self, a: torch.Tensor, name: str, out: Optional[torch.Tensor] = None, epilogue: int = LX_EPI_STORE_BF16) -> torch.Tensor:
-        """Precise mode: a is a _Pair with lo = K (channel counts here are multiples of 64), and a bf16 store writes the output pair
-        [M, 2 Npad] (lo half Npad columns after the hi half)."""
-        bias = self.w[name + ".bias"]
-        Wt = self.w[name + ".w"] if self.precise else self._op.weight(name)
-        if self.precise:
-            segs = self.w[name + ".segs"]
-            Np, Kp = Wt.shape[0], Wt.shape[1] // (segs - 1)
-            assert a.C == Kp and a.lo == Kp, (name, a.C, a.lo, Kp)
-            pair_out = epilogue == LX_EPI_STORE_BF16
-            if out is None:
-                out = torch.empty(a.t.shape[0], 2 * Np if pair_out else Np, dtype=torch.bfloat16 if pair_out else torch.float32, device=self.device)
-            ops.gemm([ops.gemm_desc(a.t, Wt, out, bias=bias, epilogue=epilogue, N=Np, K=Kp, k_segs=segs, a_lo_off=Kp, c_lo_off=Np if pair_out else 0)])
-            return out
+    def _lin(self, a: _Operand, name: str, out=None, epilogue: int = LX_EPI_STORE_BF16):
+        """a W^T + bias into `out`: an operand (STORE_BF16) or the fp32 stream (STORE_F32; RESID_F32 accumulates)."""
+        Wt = self._op.weight(name)
+        Np, Kp = Wt.t.shape[0], Wt.C
+        assert a.C == Kp, (name, a.C, Kp)
         if out is None:
-            out = torch.empty(a.shape[0], Wt.shape[0], dtype=self._op.dtype if epilogue == LX_EPI_STORE_BF16 else torch.float32, device=self.device)
-        self._op.gemm(a, Wt, out, bias=bias, epilogue=epilogue)
+            out = self._op.out(a.t.shape[0], Np, epilogue)
+        self._op.gemm(a, Wt, out, N=Np, K=Kp, bias=self.w[name + ".bias"], epilogue=epilogue)
         return out
 
-    def _operand(self, x: torch.Tensor):
-        """The fp32 stream x [M, C] as a GEMM operand: bf16 | fp16 [M, C], or in precise mode the pair [M, 2 * roundup(C, 8)] (`lx_split_bf16`; a
-        channel count that is no multiple of 4 -- the encoder's RGB input -- is zero-padded to one first, which is torch plumbing)."""
-        M, C = x.shape
-        if not self.precise:
-            xb = torch.empty(x.shape, dtype=self._op.dtype, device=self.device)
-            self._op.convert(xb, x)
-            return xb
-        if C % 4:
-            x = torch.nn.functional.pad(x, (0, _pad_to(C, 4) - C))
-        lo = _pad_to(C, 8)
-        y = torch.empty(M, 2 * lo, dtype=torch.bfloat16, device=self.device)
-        ops.split_bf16(x, y, lo)
-        return _Pair(y, C, lo)
+    def _operand(self, x: torch.Tensor) -> _Operand:
+        """The fp32 stream x [M, C] as a GEMM operand."""
+        return self._op.from_stream(x)
 
     def _resnet(self, x: torch.Tensor, B: int, H: int, W: int, p: str) -> torch.Tensor:
         h = self._gn(x, B, p + ".norm1")
@@ -306,82 +347,29 @@ class LxAutoencoderKL:
         return x
 
     def _attn(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
-        """Single-head attention over the P = H*W tokens of each image (diffusers Attention, residual_connection=True)."""
-        if self.precise:
-            return self._attn_precise(x, B, P, p)
-        if P % 64:
-            return self._attn_ragged(x, B, P, p)
-        C, op = x.shape[1], self._op
-        n = self._gn(x, B, p + ".group_norm", silu=False)
-        q, k = self._lin(n, p + ".to_q"), self._lin(n, p + ".to_k")
-        Wv, bv = op.weight(p + ".to_v"), self.w[p + ".to_v.bias"]
-        S = torch.empty(P, P, dtype=torch.float32, device=self.device)
-        Pm = torch.empty(P, P, dtype=op.dtype, device=self.device)
-        vT = torch.empty(C, P, dtype=op.dtype, device=self.device)
-        o = torch.empty(B * P, C, dtype=op.dtype, device=self.device)
-        for b in range(B):
-            r = slice(b * P, (b + 1) * P)
-            op.gemm(q[r], k[r], S, epilogue=LX_EPI_STORE_F32)                                         # S = q k^T
-            op.softmax_rows(S, Pm, 1.0 / math.sqrt(C))
-            op.gemm(Wv, n[r], vT, epilogue=LX_EPI_STORE_BF16)                                         # v^T = Wv n^T (bias added below)
-            op.gemm(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)                                # rows of P sum to 1: P (v + 1 bv^T) = P v + bv
-        self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
-        return x
-
-    def _attn_ragged(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
-        """_attn for a token count that is no multiple of 64 (the GEMM's K granule; its N granule is 8): the key axis is padded to
-        Ppad = roundup(P, 64). The images lie back to back in n and k ([B*P, C]), so the Ppad key rows of image b run into image b+1's
-        rows and, for the last image, into a zero tail that both buffers carry: every row a GEMM reads lies inside its allocation and
-        is finite (real rows of a neighbour, or zeros). Columns [P, Ppad) of S and of v^T are therefore finite garbage; the softmax
-        reads none of the former and writes exact zeros for those keys, so the latter contribute nothing to P v."""
+        """Single-head attention over the P = H*W tokens of each image (diffusers Attention, residual_connection=True), one path for every
+        format and token count. The key axis is padded to Ppad = roundup(P, 64) (the GEMM's K granule; its N granule is 8). The images lie
+        back to back in n and k ([B*P, C]), so the Ppad key rows of image b run into image b+1's rows and, for the last image, into a zero
+        tail that both buffers carry when Ppad > P: every row a GEMM reads lies inside its allocation and is finite (real rows of a
+        neighbour, or zeros). Columns [P, Ppad) of S and of v^T are therefore finite garbage; the softmax reads none of the former and
+        writes exact zeros for those keys, so the latter contribute nothing to P v. At Ppad == P there is no tail and nothing to fill."""
         C, op = x.shape[1], self._op
         Pp = _pad_to(P, 64)
-        rows = (B - 1) * P + Pp                                                                       # the last image's Ppad rows end here
-        n = torch.zeros(rows, C, dtype=op.dtype, device=self.device)
-        k = torch.zeros(rows, C, dtype=op.dtype, device=self.device)
-        self._gn(x, B, p + ".group_norm", silu=False, out=n[: B * P])
-        q = self._lin(n[: B * P], p + ".to_q")
-        self._lin(n[: B * P], p + ".to_k", out=k[: B * P])
+        rows, real = (B - 1) * P + Pp, slice(0, B * P)                                                # the last image's Ppad rows end at `rows`
+        n, k = op.operand(rows, C, zero=Pp > P), op.operand(rows, C, zero=Pp > P)
+        self._gn(x, B, p + ".group_norm", silu=False, out=n.rows(real))
+        q = self._lin(n.rows(real), p + ".to_q")
+        self._lin(n.rows(real), p + ".to_k", out=k.rows(real))
         Wv, bv = op.weight(p + ".to_v"), self.w[p + ".to_v.bias"]
         S = torch.empty(P, Pp, dtype=torch.float32, device=self.device)
-        Pm = torch.empty(P, Pp, dtype=op.dtype, device=self.device)
-        vT = torch.empty(C, Pp, dtype=op.dtype, device=self.device)
-        o = torch.empty(B * P, C, dtype=op.dtype, device=self.device)
+        Pm, vT, o = op.operand(P, Pp), op.operand(C, Pp), op.operand(B * P, C)
         for b in range(B):
             r, rp = slice(b * P, (b + 1) * P), slice(b * P, b * P + Pp)
-            op.gemm(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32)                                        # S[:, :P] = q k^T
-            op.softmax_rows(S, Pm, 1.0 / math.sqrt(C), n_valid=P)                                     # Pm[:, P:] = +0
-            op.gemm(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16)                                        # v^T[:, :P] = Wv n^T
-            op.gemm(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16)
+            op.gemm(q.rows(r), k.rows(rp), S, N=Pp, K=C, epilogue=LX_EPI_STORE_F32)                   # S[:, :P] = q k^T
+            op.softmax_rows(S, Pm, 1.0 / math.sqrt(C), P, Pp)                                         # Pm[:, P:] = +0
+            op.gemm(Wv, n.rows(rp), vT, N=Pp, K=C, epilogue=LX_EPI_STORE_BF16)                        # v^T[:, :P] = Wv n^T (bias added below)
+            op.gemm(Pm, vT, o.rows(r), N=C, K=Pp, bias=bv, epilogue=LX_EPI_STORE_BF16)                # rows of P sum to 1: P (v + 1 bv^T) = P v + bv
         self._lin(o, p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
-        return x
-
-    def _attn_precise(self, x: torch.Tensor, B: int, P: int, p: str) -> torch.Tensor:
-        """_attn on pairs, one path for every token count: the key axis is padded to Ppad = roundup(P, 64) as in _attn_ragged (zero-tailed n
-        and k, both halves; Ppad == P when P is a multiple of 64). q, k, v^T, the probabilities and the attention output are pair images and
-        all three products are k_segs = 3 launches (hi hi + lo hi + hi lo); to_out accumulates into the fp32 stream."""
-        C = x.shape[1]
-        Pp = _pad_to(P, 64)
-        rows = (B - 1) * P + Pp
-        n = torch.zeros(rows, 2 * C, dtype=torch.bfloat16, device=self.device)
-        k = torch.zeros(rows, 2 * C, dtype=torch.bfloat16, device=self.device)
-        self._gn(x, B, p + ".group_norm", silu=False, out=n[: B * P])
-        np_ = _Pair(n[: B * P], C, C)
-        q = self._lin(np_, p + ".to_q")
-        self._lin(np_, p + ".to_k", out=k[: B * P])
-        Wv, bv = self.w[p + ".to_v.w"], self.w[p + ".to_v.bias"]                                      # [C, 2C] = [Wv_hi | Wv_lo]
-        assert Wv.shape == (C, 2 * C), (Wv.shape, C)
-        S = torch.empty(P, Pp, dtype=torch.float32, device=self.device)
-        Pm = torch.empty(P, 2 * Pp, dtype=torch.bfloat16, device=self.device)
-        vT = torch.empty(C, 2 * Pp, dtype=torch.bfloat16, device=self.device)
-        o = torch.empty(B * P, 2 * C, dtype=torch.bfloat16, device=self.device)
-        for b in range(B):
-            r, rp = slice(b * P, (b + 1) * P), slice(b * P, b * P + Pp)
-            ops.gemm([ops.gemm_desc(q[r], k[rp], S, epilogue=LX_EPI_STORE_F32, N=Pp, K=C, k_segs=3, a_lo_off=C)])             # S[:, :P] = q k^T
-            ops.softmax_rows_split(S, Pm, 1.0 / math.sqrt(C), P, Pp, Pp)                                                     # Pm[:, P:Pp] = +0, both halves
-            ops.gemm([ops.gemm_desc(Wv, n[rp], vT, epilogue=LX_EPI_STORE_BF16, N=Pp, K=C, k_segs=3, a_lo_off=C, c_lo_off=Pp)])  # v^T[:, :P] = Wv n^T
-            ops.gemm([ops.gemm_desc(Pm, vT, o[r], bias=bv, epilogue=LX_EPI_STORE_BF16, N=C, K=Pp, k_segs=3, a_lo_off=Pp, c_lo_off=C)])
-        self._lin(_Pair(o, C, C), p + ".to_out.0", out=x, epilogue=LX_EPI_RESID_F32)
         return x
 
     def _mid(self, x, B, H, W, p):
@@ -389,15 +377,9 @@ class LxAutoencoderKL:
         x = self._attn(x, B, H * W, p + ".attentions.0")
         return self._resnet(x, B, H, W, p + ".resnets.1")
 
-    def _nhwc_bf16(self, t: torch.Tensor) -> torch.Tensor:
-        return t.to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
-
-    def _input(self, t: torch.Tensor):
-        """NCHW input -> the operand of conv_in: NHWC rows [B*H*W, C], bf16, fp16 (saturated and counted) or (precise mode) the pair of
-        the fp32 values."""
-        if self.precise or self._op.f16:
-            return self._operand(t.to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous())
-        return self._nhwc_bf16(t).view(-1, t.shape[1])
+    def _input(self, t: torch.Tensor) -> _Operand:
+        """NCHW input -> the operand of conv_in."""
+        return self._op.input(t)
 
     def _checked(self, run, what: str):
         """run() under the fp16 overflow contract (a plain call in the other modes): the counter is zeroed, and read once when the call
@@ -421,7 +403,7 @@ class LxAutoencoderKL:
             warnings.warn(msg + "; the result was kept", RuntimeWarning, stacklevel=3)
             return out
         warnings.warn(msg + f"; recomputing this {what} with bf16 operands", RuntimeWarning, stacklevel=3)
-        f16, self._op = self._op, _Operands16("bf16", self.w)
+        f16, self._op = self._op, _Operands16("bf16", self.w, self.device)
         try:
             return run()
         finally:
