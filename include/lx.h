@@ -525,6 +525,22 @@ int lx_lora_down_fp8(const void* X8, int ldx, float x_descale, const void* Adown
 
 /* x(fp32) += dsigma * v   (FlowMatchEulerDiscreteScheduler.step, generate.py:349); v is bf16 or fp32 */
 int lx_euler_step(float* x, const void* v, int v_is_bf16, float dsigma, size_t n, void* stream);
+/* Start of an img2img trajectory: out = sigma*z + (1 - sigma)*x0 over n fp32 elements (diffusers
+ * FlowMatchEulerDiscreteScheduler.scale_noise, called by FluxImg2ImgPipeline / FluxInpaintPipeline.prepare_latents; the reference's
+ * generate.py:262 always starts from pure noise). Computed as fmaf(sigma, z, (1 - sigma)*x0) with the product rounded on its own, so
+ * sigma == 1 returns z and sigma == 0 returns x0 exactly (finite inputs; up to the sign of a zero). x0 and z may not alias out. */
+int lx_scale_noise(float* out, const float* x0, const float* z, float sigma, size_t n, void* stream);
+/* One Euler step, then the kept region pinned to the source noised to the NEXT level, in one pass with x updated in place: replaces
+ * scheduler.step (generate.py:349) plus the blend of diffusers' FluxInpaintPipeline loop (init_latents_proper =
+ * scale_noise(image_latents, next timestep, noise); latents = (1 - mask)*init_latents_proper + mask*latents).
+ *   e = fmaf(dsigma, v, x)                       -- bit-identical to lx_euler_step
+ *   r = fmaf(sigma_next, z, (1 - sigma_next)*x0) -- bit-identical to lx_scale_noise(x0, z, sigma_next)
+ *   x = fmaf(m, e, (1 - m)*r)                    -- m = 1 repaint, m = 0 keep
+ * Three fused multiply-adds and two separately rounded products, in this order: m == 1 gives exactly e, m == 0 exactly r, and
+ * sigma_next == 0 with m == 0 exactly x0 (finite inputs; up to the sign of a zero). v bf16 or fp32 as in lx_euler_step; x0, z, m
+ * fp32 with n elements each; none of them may alias x. */
+int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float dsigma, const float* x0, const float* z, const float* m,
+                        float sigma_next, size_t n, void* stream);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

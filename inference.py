@@ -89,6 +89,23 @@ def inference_single_image(model, condition_img, prompt, condition_type="SEED", 
     return result.images[0]
 
 
+def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
+    """--strength / --mask_dir / --mask_path -> generate()'s img2img / inpaint keywords (an addition; diffusers' FluxImg2ImgPipeline /
+    FluxInpaintPipeline): the input image, resized to the target size, is the source that `strength` starts from and that the black part
+    of the mask keeps. Nothing given: no keywords, and generate() is called as before."""
+    if strength is None and mask_path is None:
+        return {}
+    from PIL import Image
+    kw = {"image": source_img.convert("RGB").resize((target_size, target_size), resample=Image.LANCZOS)}
+    if strength is not None:
+        kw["strength"] = strength
+    if mask_path is not None:
+        if not os.path.isfile(mask_path):
+            raise FileNotFoundError(f"no mask at {mask_path} (--mask_dir holds one mask per input file name; --mask_path is the one of --single_image)")
+        kw["mask_image"] = Image.open(mask_path).convert("L")
+    return kw
+
+
 def _signals(brain_data, img_file, device=None):
     out = {"eeg_data": None, "fnirs_data": None, "ppg_data": None, "motion_data": None}
     rec = brain_data.get(img_file) if brain_data else None
@@ -112,8 +129,8 @@ def load_captions(caption_path):
 
 
 def process_image_batch(rank, world_size, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta,
-                        target_size, seed):
-    """inference.py:124-176: this rank's contiguous slice of the image list."""
+                        target_size, seed, strength=None, mask_dir=None):
+    """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image."""
     from PIL import Image
     from loongx_amd.dist import shard_range
     start_idx, end_idx = shard_range(len(image_files), rank, world_size)
@@ -122,20 +139,22 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
         condition_img = Image.open(os.path.join(input_dir, img_file)).convert("RGB")
         prompt = captions.get(img_file, "Edit this image")
         result_img = inference_single_image(model, condition_img, prompt, condition_type=condition_type, position_delta=position_delta,
-                                            target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device))
+                                            target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device),
+                                            **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None))
         result_img.save(os.path.join(output_dir, img_file))
         if rank == 0 and (idx - start_idx) % 10 == 0:
             print(f"Process {rank}: Completed {idx - start_idx}/{end_idx - start_idx} images")
 
 
 def batch_inference(model, input_dir, output_dir, caption_path=None, condition_type="SEED", target_size=512, position_delta=[0, -32],
-                    seed=42, brain_data_path=None):
+                    seed=42, brain_data_path=None, strength=None, mask_dir=None):
     """inference.py:255-339: all captioned images of a directory on one GPU."""
     os.makedirs(output_dir, exist_ok=True)
     brain_data = load_brain_data(brain_data_path) if brain_data_path and os.path.exists(brain_data_path) else {}
     captions = load_captions(caption_path)
     image_files = [f for f in captions if f.endswith((".png", ".jpg", ".jpeg"))]
-    process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed)
+    process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed,
+                        strength=strength, mask_dir=mask_dir)
     print(f"Processed {len(image_files)} images. Results saved to {output_dir}")
 
 
@@ -241,7 +260,8 @@ def distributed_inference_worker(rank, world_size, args, config, model_loaded_ev
             print(f"Processing {len(image_files)} images across {world_size} GPUs")
         t0 = time.time()
         process_image_batch(rank, world_size, model, image_files, args.input_dir, args.output_dir, captions, brain_data, args.condition_type,
-                            [args.position_delta_x, args.position_delta_y], args.target_size, args.seed)
+                            [args.position_delta_x, args.position_delta_y], args.target_size, args.seed, strength=args.strength,
+                            mask_dir=args.mask_dir)
         n_total, n, dt = len(image_files), len(image_files) // world_size, time.time() - t0
     if world_size > 1:
         dist.barrier()
@@ -274,7 +294,14 @@ def main(argv=None):
     p.add_argument("--f16-overflow", dest="f16_overflow", type=str, default="raise", choices=("raise", "warn", "fallback"),
                    help="what an fp16 operand beyond +-65504 does (the kernels saturate and count; the reference clips silently, "
                         "block.py:275-276): raise | warn | fallback (recompute that image with bf16 operands)")
+    p.add_argument("--strength", type=float, default=None,
+                   help="img2img: start from the input image noised to this level, in (0, 1] (generate(image=, strength=)); default: pure noise")
+    p.add_argument("--mask_dir", type=str, default=None,
+                   help="inpaint: a directory with one mask per input file name; white is repainted, black keeps the input image (generate(mask_image=))")
+    p.add_argument("--mask_path", type=str, default=None, help="(--single_image) the mask of that image")
     args = p.parse_args(argv)
+    if args.synthetic and (args.strength is not None or args.mask_dir or args.mask_path):
+        p.error("--strength / --mask_dir / --mask_path edit an input image: not with --synthetic")
     config = get_config()
     config.setdefault("model", {})
     if args.operands:
@@ -289,7 +316,8 @@ def main(argv=None):
         name = os.path.basename(args.single_image)
         result_img = inference_single_image(model, condition_img, args.prompt, condition_type=args.condition_type,
                                             position_delta=[args.position_delta_x, args.position_delta_y], target_size=args.target_size,
-                                            seed=args.seed, **_signals(brain_data, name))
+                                            seed=args.seed, **_signals(brain_data, name),
+                                            **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path))
         os.makedirs(args.output_dir, exist_ok=True)
         output_path = os.path.join(args.output_dir, name)
         result_img.save(output_path)
@@ -307,7 +335,7 @@ def main(argv=None):
             model = load_model(args.checkpoint, config)
             batch_inference(model, args.input_dir, args.output_dir, args.caption_path, condition_type=args.condition_type,
                             target_size=args.target_size, position_delta=[args.position_delta_x, args.position_delta_y], seed=args.seed,
-                            brain_data_path=args.brain_data_path)
+                            brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir)
     else:
         print(f"Running distributed inference on {world} GPUs")
         mp.set_start_method("spawn", force=True)

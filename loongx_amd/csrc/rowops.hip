@@ -634,6 +634,67 @@ __global__ void euler_kernel(float* __restrict__ x, const void* __restrict__ v, 
   }
 }
 
+// ---- img2img start and the inpaint step (lx_scale_noise, lx_euler_step_blend) ----------------------------------------------------------
+// The operation order is the contract of include/lx.h: three fused multiply-adds, two separately rounded products, written out so that
+// no contraction setting can move a rounding. A work item is VEC consecutive elements (VEC = 4: 16-byte accesses, 8-byte for bf16 v;
+// taken when every pointer is 16-byte aligned; the last n % 4 elements go one by one), grid-stride loop under euler_kernel's grid cap.
+__device__ __forceinline__ float scale_noise1(float x0, float z, float sigma, float one_minus_sigma) {
+  return fmaf(sigma, z, __fmul_rn(one_minus_sigma, x0));
+}
+__device__ __forceinline__ float euler_blend1(float x, float v, float ds, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
+  const float e = fmaf(ds, v, x);
+  const float r = scale_noise1(x0, z, sigma_next, one_minus_sigma);
+  return fmaf(m, e, __fmul_rn(__fsub_rn(1.f, m), r));
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void scale_noise_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ z,
+                                                          float sigma, float one_minus_sigma, size_t n) {
+  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4 && i + 4 <= n) {
+      const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i);
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = scale_noise1(a[j], b[j], sigma, one_minus_sigma);
+      *(f32x4*)(out + i) = o;
+    } else {
+      for (size_t k = i; k < n && k < i + VEC; ++k) out[k] = scale_noise1(x0[k], z[k], sigma, one_minus_sigma);
+    }
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void euler_blend_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds,
+                                                          const float* __restrict__ x0, const float* __restrict__ z,
+                                                          const float* __restrict__ m, float sigma_next, float one_minus_sigma, size_t n) {
+  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4 && i + 4 <= n) {
+      f32x4 vv;
+      if (v_bf16) {
+        const u32x2 p = *(const u32x2*)((const uint16_t*)v + i);
+        vv = f32x4{bf16_to_f32((uint16_t)(p[0] & 0xffffu)), bf16_to_f32((uint16_t)(p[0] >> 16)),
+                   bf16_to_f32((uint16_t)(p[1] & 0xffffu)), bf16_to_f32((uint16_t)(p[1] >> 16))};
+      } else {
+        vv = *(const f32x4*)((const float*)v + i);
+      }
+      const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
+      f32x4 o = *(const f32x4*)(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = euler_blend1(o[j], vv[j], ds, a[j], b[j], mm[j], sigma_next, one_minus_sigma);
+      *(f32x4*)(x + i) = o;
+    } else {
+      for (size_t k = i; k < n && k < i + VEC; ++k) {
+        const float vk = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[k]) : ((const float*)v)[k];
+        x[k] = euler_blend1(x[k], vk, ds, x0[k], z[k], m[k], sigma_next, one_minus_sigma);
+      }
+    }
+  }
+}
+
 __global__ void convert_kernel(void* __restrict__ dst, int dst_bf16, const void* __restrict__ src, int src_bf16, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -982,6 +1043,42 @@ extern "C" int lx_euler_step(float* x, const void* v, int v_is_bf16, float dsigm
   const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(euler_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, n);
   LX_LAUNCH_CHECK("lx_euler_step");
+  return LX_OK;
+}
+
+// [a, a + n) and [b, b + n) fp32 elements share an address
+static bool f32_ranges_overlap(const void* a, const void* b, size_t n) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = n * sizeof(float);
+  return pa < pb + bytes && pb < pa + bytes;
+}
+
+extern "C" int lx_scale_noise(float* out, const float* x0, const float* z, float sigma, size_t n, void* stream) {
+  LX_CHECK_ARG(out && x0 && z, "lx_scale_noise: NULL operand");
+  LX_CHECK_ARG(!f32_ranges_overlap(out, x0, n) && !f32_ranges_overlap(out, z, n), "lx_scale_noise: x0 and z may not alias out");
+  if (n == 0) return LX_OK;
+  const bool vec = (((uintptr_t)out | (uintptr_t)x0 | (uintptr_t)z) & 15) == 0;
+  const size_t items = vec ? (n + 3) / 4 : n;
+  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  const float oms = 1.0f - sigma;
+  if (vec) hipLaunchKernelGGL(scale_noise_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, x0, z, sigma, oms, n);
+  else hipLaunchKernelGGL(scale_noise_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, x0, z, sigma, oms, n);
+  LX_LAUNCH_CHECK("lx_scale_noise");
+  return LX_OK;
+}
+
+extern "C" int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float dsigma, const float* x0, const float* z, const float* m,
+                                   float sigma_next, size_t n, void* stream) {
+  LX_CHECK_ARG(x && v && x0 && z && m, "lx_euler_step_blend: NULL operand");
+  LX_CHECK_ARG(!f32_ranges_overlap(x, x0, n) && !f32_ranges_overlap(x, z, n) && !f32_ranges_overlap(x, m, n),
+               "lx_euler_step_blend: x0, z and m may not alias x (it is updated in place)");
+  if (n == 0) return LX_OK;
+  const bool vec = (((uintptr_t)x | (uintptr_t)v | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0;
+  const size_t items = vec ? (n + 3) / 4 : n;
+  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  const float oms = 1.0f - sigma_next;
+  if (vec) hipLaunchKernelGGL(euler_blend_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
+  else hipLaunchKernelGGL(euler_blend_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
+  LX_LAUNCH_CHECK("lx_euler_step_blend");
   return LX_OK;
 }
 

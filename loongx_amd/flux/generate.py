@@ -26,6 +26,7 @@ import yaml
 
 from .condition import Condition
 from .pipeline import FluxPipelineOutput, calculate_shift, retrieve_timesteps
+from .pipeline_tools import encode_images
 from .transformer import tranformer_forward
 
 
@@ -67,10 +68,73 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    output_type: Optional[str] = "pil", return_dict: bool = True,
                    joint_attention_kwargs: Optional[Dict[str, Any]] = None,
                    callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
-                   callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512, **kwargs):
+                   callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
+                   image=None, image_latents: Optional[torch.Tensor] = None, mask_image=None,
+                   latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0, **kwargs):
+    """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline are named here
+    (so they are not among the swallowed **kwargs) and returned by prepare_inpaint_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
+
+
+def prepare_inpaint_params(image=None, image_latents: Optional[torch.Tensor] = None, mask_image=None,
+                           latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0, **kwargs):
+    return image, image_latents, mask_image, latent_mask, strength
+
+
+def _inpaint_source(pipeline, image, image_latents, mask_image, latent_mask, strength, num_inference_steps, batch, tokens, height, width,
+                    f16_overflow):
+    """generate()'s img2img / inpaint arguments -> (image_latents, mask): fp32 contiguous [batch, tokens, 64] on the pipeline's device (None
+    where not asked for). Every refusal is a ValueError and comes before the first launch -- the host-side ones first, then the one
+    synchronous min / max of a latent_mask -- so that a refused call leaves the pipeline as it was. `batch` is None where the caller's
+    arguments do not determine it (check_inputs then refuses the call)."""
+    if not (isinstance(strength, (int, float)) and 0.0 <= float(strength) <= 1.0):          # (a NaN fails both comparisons)
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+    if image is not None and image_latents is not None:
+        raise ValueError("Cannot forward both `image` and `image_latents`.")
+    if mask_image is not None and latent_mask is not None:
+        raise ValueError("Cannot forward both `mask_image` and `latent_mask`.")
+    source, mask = (image if image is not None else image_latents), (mask_image if mask_image is not None else latent_mask)
+    if source is None:
+        if mask is not None:
+            raise ValueError("`mask_image` / `latent_mask` need a source to keep: pass `image` or `image_latents`.")
+        if float(strength) != 1.0:
+            raise ValueError(f"strength={strength} needs a source to start from: pass `image` or `image_latents`.")
+        return None, None
+    t_start = int(max(num_inference_steps - min(num_inference_steps * strength, num_inference_steps), 0))      # (get_timesteps' arithmetic)
+    if num_inference_steps - t_start < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                         f"{num_inference_steps - t_start} which is < 1 and not appropriate for this pipeline.")
+
+    def fits(name, t, last):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[1] != tokens or t.shape[2] not in last or \
+                (batch is not None and t.shape[0] not in (1, batch)):
+            raise ValueError(f"`{name}` must be a tensor of shape [1|{batch}, {tokens}, {' | '.join(map(str, last))}] for these latents, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if image_latents is not None:
+        fits("image_latents", image_latents, (64,))
+    if latent_mask is not None:
+        fits("latent_mask", latent_mask, (64, 1))
+    if batch is None:
+        return None, None
+    dev = pipeline.device
+    if latent_mask is not None:
+        mask = latent_mask.to(device=dev, dtype=torch.float32)
+        lo, hi = torch.aminmax(mask)
+        lo, hi = float(lo), float(hi)
+        if not (0.0 <= lo and hi <= 1.0):                                                    # (a NaN fails both comparisons)
+            raise ValueError(f"`latent_mask` must be finite and lie in [0, 1] (1: repaint, 0: keep); its values span [{lo}, {hi}]")
+    elif mask_image is not None:
+        mask = pipeline.pack_mask(mask_image, batch, height, width).to(dev)
+        fits("mask_image (packed)", mask, (64,))
+    if image is not None:
+        image_latents = encode_images(pipeline, image, f16_overflow)[0].to(torch.float32)
+        fits("image (encoded)", image_latents, (64,))
+    image_latents = image_latents.to(device=dev, dtype=torch.float32).expand(batch, -1, -1).contiguous()
+    if mask is not None:
+        mask = mask.expand(batch, tokens, 64).contiguous()
+    return image_latents, mask
 
 
 def seed_everything(seed: int = 42):
@@ -121,17 +185,30 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     self = pipeline
     if brain_replace not in ("both", "per_stream"):
         raise ValueError(f"brain_replace must be 'both' (the reference rule) or 'per_stream', got {brain_replace!r}")
+    (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator, latents,
+     prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
+     callback_on_step_end_tensor_inputs, max_sequence_length) = prepare_params(**params)
+    height = height or self.default_sample_size * self.vae_scale_factor
+    width = width or self.default_sample_size * self.vae_scale_factor
+    # ---- img2img / inpaint arguments (diffusers FluxImg2ImgPipeline / FluxInpaintPipeline): checked, and the source encoded, before
+    # anything of the pipeline is touched. The source image is the first draw from the global generator, as in diffusers' prepare_latents.
+    image, image_latents, mask_image, latent_mask, strength = prepare_inpaint_params(**params)
+    if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
+        n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
+            prompt_embeds.shape[0] if prompt_embeds is not None else None
+        image_latents, inpaint_mask = _inpaint_source(
+            pipeline, image, image_latents, mask_image, latent_mask, strength, num_inference_steps,
+            latents.shape[0] if latents is not None else None if n_prompts is None else n_prompts * num_images_per_prompt,
+            latents.shape[1] if latents is not None else (int(height) // self.vae_scale_factor) * (int(width) // self.vae_scale_factor),
+            height, width, (model_config or {}).get("f16_overflow"))
+    else:
+        image_latents = inpaint_mask = None
     # the step-invariant conditioning cache of the transformer lives for the steps of ONE image: every tensor made below is
     # freed on return and its address may come back with different content on the next call
     if hasattr(pipeline.transformer, "invalidate_conditioning"):
         pipeline.transformer.invalidate_conditioning()
     if condition_scale != 1:
         pipeline.transformer.c_factor = float(condition_scale)
-    (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator, latents,
-     prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
-     callback_on_step_end_tensor_inputs, max_sequence_length) = prepare_params(**params)
-    height = height or self.default_sample_size * self.vae_scale_factor
-    width = width or self.default_sample_size * self.vae_scale_factor
     self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
                       callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
     self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
@@ -207,7 +284,15 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     cfg = self.scheduler.config
     mu = calculate_shift(latents.shape[1], cfg.base_image_seq_len, cfg.max_image_seq_len, cfg.base_shift, cfg.max_shift)
     timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas, mu=mu)
+    n_schedule = num_inference_steps
     num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
+    if image_latents is not None:
+        # the trajectory starts at sigma[t_start] from the source noised to that level; `latents` (the caller's, or the draw) is the noise
+        noise = latents.contiguous()
+        timesteps, num_inference_steps, th_left = self.get_timesteps(n_schedule, strength, device)
+        latents = self.scheduler.scale_noise(image_latents, n_schedule - num_inference_steps, noise)
+        num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
+    step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
     self._num_timesteps = len(timesteps)
     guidance = None
     if self.transformer.config.guidance_embeds:
@@ -219,7 +304,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     # the whole schedule is known here: hand it to the engine so the AdaLN modulation weights stream once per image
     # (host copy of the same fp32 values: a .tolist() on the device tensor would drain the stream here and keep the host from
     #  preparing this image while the GPU is still busy with the previous one)
-    th = getattr(self.scheduler, "timesteps_host", None)
+    th = getattr(self.scheduler, "timesteps_host", None) if image_latents is None else th_left
     if th is not None and latents.dtype == torch.float32 and len(th) == len(timesteps):
         sched_ts = (th / np.float32(1000)).tolist()
     else:
@@ -244,7 +329,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                     hidden_states=latents, timestep=timestep / 1000, guidance=guidance, pooled_projections=pooled_prompt_embeds,
                     encoder_hidden_states=prompt_embeds, txt_ids=text_ids, img_ids=latent_image_ids,
                     joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False, lx_schedule=(i, sched_ts))[0]
-                latents = self.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
+                latents = self.scheduler.step(noise_pred, t, latents, return_dict=False, **step_kwargs)[0]
                 if callback_on_step_end is not None:
                     scope = dict(locals())                                  # (a comprehension has its own locals() before 3.12)
                     callback_kwargs = {}
@@ -275,7 +360,9 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             else:
                 warnings.warn(what + "; recomputing this image with bf16 operands", RuntimeWarning, stacklevel=2)
                 pipeline.transformer.invalidate_conditioning()
-                timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, None, sigmas, mu=mu)      # (step index back to 0)
+                timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, n_schedule, device, None, sigmas, mu=mu)      # (step index back to 0)
+                if image_latents is not None:                 # (and on to t_start again: the same start latents, the same blend)
+                    timesteps, num_inference_steps, _ = self.get_timesteps(n_schedule, strength, device)
                 latents = denoise(start_latents, prompt_embeds, dict(model_config or {}, operands="bf16"))
                 operands_used = "bf16 (fp16 overflow fallback)"
 

@@ -1,6 +1,8 @@
 """`LxFluxPipeline`: the slice of diffusers' FluxPipeline that the reference's generate() touches
 (src/flux/generate.py:72-394), for MI355X.  Restated from diffusers==0.31.0 (train/requirements.txt:1): latent packing,
 latent image ids, calculate_shift, FlowMatchEulerDiscreteScheduler.  The Euler update runs in HIP (lx_euler_step).
+Beyond what the reference calls, from diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline: scale_noise, set_begin_index, get_timesteps,
+the packed latent mask (pack_mask) and the per-step blend (lx_scale_noise, lx_euler_step_blend).
 
 Text encoders (T5/CLIP) and the VAE are outside the denoise hot path ("next"): pass `prompt_embeds`,
 `pooled_prompt_embeds` and `output_type="latent"`, or plug callables in via `text_encoder=` / `vae=`.
@@ -38,7 +40,7 @@ class FlowMatchEulerDiscreteScheduler:
                                       base_shift=base_shift, max_shift=max_shift, base_image_seq_len=base_image_seq_len,
                                       max_image_seq_len=max_image_seq_len)
         self.timesteps = self.sigmas = None
-        self._step_index = None
+        self._step_index = self._begin_index = None
 
     def set_timesteps(self, num_inference_steps=None, device=None, sigmas=None, mu=None):
         if sigmas is None:
@@ -56,15 +58,52 @@ class FlowMatchEulerDiscreteScheduler:
         self.timesteps_host = sig * np.float32(self.config.num_train_timesteps)      # same fp32 values as self.timesteps, no device sync
         self.timesteps = torch.from_numpy(self.timesteps_host).to(device)
         self.sigmas = torch.from_numpy(self._sig_host).to(device)
-        self._step_index = 0
+        self._step_index = self._begin_index = 0
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False):
-        """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics)."""
+    def set_begin_index(self, begin_index: int = 0):
+        """diffusers' set_begin_index, called after set_timesteps (which puts it back to 0): the next step() is step `begin_index` of the
+        schedule (an img2img / inpaint trajectory that starts part-way, LxFluxPipeline.get_timesteps)."""
+        if self.timesteps is None or not 0 <= int(begin_index) < len(self.timesteps_host):
+            raise ValueError(f"set_begin_index({begin_index}): call set_timesteps first; the index must lie inside its schedule")
+        self._step_index = self._begin_index = int(begin_index)
+
+    def _sigma_index(self, sigma_index_or_timestep) -> int:
+        """A Python / numpy integer is an index into the schedule; anything else is one of its timesteps (exact match, as diffusers'
+        index_for_timestep). Looked up in the host copy of the schedule."""
+        s = sigma_index_or_timestep
+        if isinstance(s, (int, np.integer)) and not isinstance(s, bool):
+            if not 0 <= int(s) < len(self._sig_host):
+                raise ValueError(f"sigma index {int(s)} outside the schedule of {len(self._sig_host)} sigmas")
+            return int(s)
+        hit = np.nonzero(self.timesteps_host == np.float32(float(s)))[0]
+        if len(hit) == 0:
+            raise ValueError(f"timestep {float(s)} is not in the schedule")
+        return int(hit[0])
+
+    def scale_noise(self, sample: torch.Tensor, sigma_index_or_timestep, noise: torch.Tensor) -> torch.Tensor:
+        """diffusers' scale_noise: sigma * noise + (1 - sigma) * sample in fp32 (lx_scale_noise), sigma read from the host copy of the
+        schedule: the start of an img2img trajectory."""
+        if self.sigmas is None:
+            raise ValueError("scale_noise: call set_timesteps first")
+        sigma = float(self._sig_host[self._sigma_index(sigma_index_or_timestep)])
+        return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None):
+        """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
+        inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
+        level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend)."""
         i = self._step_index
         ds = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i]))
         x = sample.to(torch.float32).clone() if (sample.dtype != torch.float32 or not sample.is_contiguous()) else sample.clone()
         v = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
-        ops.euler_step(x, v.contiguous(), ds)
+        if inpaint is None:
+            ops.euler_step(x, v.contiguous(), ds)
+        else:
+            x0, z, m = inpaint
+            if not (x0.shape == z.shape == m.shape == x.shape):
+                raise ValueError(f"step(inpaint=...): image_latents {tuple(x0.shape)}, noise {tuple(z.shape)} and mask {tuple(m.shape)} must "
+                                 f"have the latents' shape {tuple(x.shape)}")
+            ops.euler_step_blend(x, v.contiguous(), ds, x0, z, m, float(self._sig_host[i + 1]))
         self._step_index += 1
         return (x.to(model_output.dtype),)
 
@@ -290,6 +329,48 @@ class LxFluxPipeline:
         ids[..., 1] += torch.arange(h2)[:, None]
         ids[..., 2] += torch.arange(w2)[None, :]
         return ids.reshape(h2 * w2, 3).to(device=device, dtype=dtype)
+
+    # ---- img2img / inpaint (diffusers FluxImg2ImgPipeline / FluxInpaintPipeline) ---------------------------
+    def get_timesteps(self, num_inference_steps, strength, device=None):
+        """diffusers' get_timesteps, after the scheduler's set_timesteps: the tail of the schedule that `strength` leaves. Returns
+        (timesteps[t_start:], num_inference_steps - t_start, timesteps_host[t_start:]) -- the third item is the host copy of the first, so
+        that callers can hand the remaining schedule on without a device read -- and sets the scheduler's begin index to t_start."""
+        init_timestep = min(num_inference_steps * strength, num_inference_steps)
+        t_start = int(max(num_inference_steps - init_timestep, 0))
+        if num_inference_steps - t_start < 1:
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                             f"{num_inference_steps - t_start} which is < 1 and not appropriate for this pipeline.")
+        sch = self.scheduler
+        sch.set_begin_index(t_start * sch.order)
+        return sch.timesteps[t_start * sch.order:], num_inference_steps - t_start, sch.timesteps_host[t_start * sch.order:]
+
+    @staticmethod
+    def pack_mask(mask, batch, height, width):
+        """A pixel mask (white / 1: repaint) -> the packed latent mask [batch, N, 64] fp32 of a height x width image, in diffusers' order
+        (mask_processor, then FluxInpaintPipeline.prepare_mask_latents): binarise at 0.5, nearest-neighbour resize to the unpacked latent
+        grid 2*(height//16) x 2*(width//16), repeat over the 16 latent channels, _pack_latents. `mask`: a PIL image (converted to "L"), a
+        numpy array or a tensor of shape [H, W], [1, H, W] or [1|batch, 1, H, W]; integer types are 0..255, bool and floating types 0..1.
+        Once per image in torch, on the mask's device (the CPU for PIL / numpy)."""
+        if hasattr(mask, "convert") and hasattr(mask, "size"):                 # PIL
+            mask = np.array(mask.convert("L"))
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.float32)
+        elif not mask.dtype.is_floating_point:
+            mask = mask.to(torch.float32) / 255.0
+        mask = mask.to(torch.float32)
+        if mask.dim() == 2:
+            mask = mask[None, None]
+        elif mask.dim() == 3 and mask.shape[0] == 1:
+            mask = mask[None]
+        if mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[0] not in (1, batch):
+            raise ValueError(f"mask_image must be [H, W], [1, H, W] or [1|{batch}, 1, H, W], got {tuple(mask.shape)}")
+        mask = (mask >= 0.5).to(torch.float32)
+        h, w = 2 * (int(height) // LxFluxPipeline.vae_scale_factor), 2 * (int(width) // LxFluxPipeline.vae_scale_factor)
+        mask = torch.nn.functional.interpolate(mask, size=(h, w), mode="nearest")
+        mask = mask.expand(batch, 1, h, w).repeat(1, 16, 1, 1)
+        return LxFluxPipeline._pack_latents(mask, batch, 16, h, w).contiguous()
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
         height = 2 * (int(height) // self.vae_scale_factor)

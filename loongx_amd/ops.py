@@ -595,6 +595,29 @@ def euler_step(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> None:
     check(lib.lx_euler_step(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), x.numel(), _stream()), "lx_euler_step")
 
 
+def scale_noise(x0: torch.Tensor, z: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = sigma*z + (1 - sigma)*x0 (lx_scale_noise): fp32, contiguous, one shape; `out` is allocated when not given."""
+    _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z")
+    out = torch.empty_like(x0, memory_format=torch.contiguous_format) if out is None else out
+    _req(out, torch.float32, "out")
+    assert x0.shape == z.shape == out.shape and x0.is_contiguous() and z.is_contiguous() and out.is_contiguous()
+    check(lib.lx_scale_noise(out.data_ptr(), x0.data_ptr(), z.data_ptr(), float(sigma), out.numel(), _stream()), "lx_scale_noise")
+    return out
+
+
+def euler_step_blend(x: torch.Tensor, v: torch.Tensor, dsigma: float, x0: torch.Tensor, z: torch.Tensor, m: torch.Tensor, sigma_next: float) -> None:
+    """x <- m*(x + dsigma*v) + (1 - m)*(sigma_next*z + (1 - sigma_next)*x0) in place (lx_euler_step_blend): x, x0, z, m fp32, v fp32 or
+    bf16, all contiguous with x's element count."""
+    _req(x, torch.float32, "x"); _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    n = x.numel()
+    assert v.numel() == n and x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_blend: one element count for all operands"
+    assert all(t.is_contiguous() for t in (x, v, x0, z, m)), "euler_step_blend: contiguous operands"
+    check(lib.lx_euler_step_blend(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), x0.data_ptr(), z.data_ptr(), m.data_ptr(),
+                                  float(sigma_next), n, _stream()), "lx_euler_step_blend")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
