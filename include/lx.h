@@ -541,6 +541,24 @@ int lx_scale_noise(float* out, const float* x0, const float* z, float sigma, siz
  * fp32 with n elements each; none of them may alias x. */
 int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float dsigma, const float* x0, const float* z, const float* m,
                         float sigma_next, size_t n, void* stream);
+/* One step under true classifier-free guidance (diffusers FluxPipeline: noise_pred = neg + true_cfg_scale * (pos - neg), then
+ * scheduler.step), both branches in one batch. x is fp32 [2n]: the latents of the positive half, then a copy for the negative half.
+ * v is [2n], bf16 or fp32: elements [0, n) are the positive branch's velocity, [n, 2n) the negative branch's. x0, z, m are all NULL (no
+ * blend) or all fp32 [n] (lx_euler_step_blend's blend, computed once and stored to both halves). Per element i < n, in this order:
+ *   d = vp - vn                        -- rounded on its own
+ *   g = fmaf(scale, d, vn)
+ *   e = fmaf(dsigma, g, x[i])          -- lx_euler_step on g
+ *   r = e                              -- without a blend
+ *   r = fmaf(m, e, (1 - m)*fmaf(sigma_next, z, (1 - sigma_next)*x0))   -- lx_euler_step_blend's three operations, bit-identical given e
+ *   x[i] = x[n + i] = r                -- only x[i] is read: both halves leave equal whatever x[n + i] held
+ * So vp == vn bit for bit gives g == vp exactly, whatever scale is (finite values; up to the sign of a zero), and the step is then
+ * lx_euler_step's, or lx_euler_step_blend's, bit for bit; with m == 0 the kept elements follow the source as in lx_euler_step_blend's
+ * contract (sigma_next == 0: exactly x0). Both halves are accessed 16 bytes at a time (8 for bf16 v) only when the second halves x + n
+ * and v + n are aligned as well as the first -- n % 4 == 0 and aligned bases; every other call goes element by element, same bits.
+ * LX_ERR_INVALID before any launch: NULL x or v; n == 0; a partly NULL (x0, z, m); x0, z or m overlapping x[0, 2n); fp32 v overlapping
+ * x[0, 2n); a scale that is not finite. */
+int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z, const float* m,
+                      float sigma_next, size_t n, void* stream);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

@@ -106,6 +106,16 @@ def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
     return kw
 
 
+def cfg_kwargs(true_cfg_scale=None, negative_prompt=None):
+    """--true_cfg_scale / --negative_prompt -> generate()'s true-CFG keywords (an addition; diffusers' FluxPipeline), each only when given."""
+    kw = {}
+    if true_cfg_scale is not None:
+        kw["true_cfg_scale"] = true_cfg_scale
+    if negative_prompt is not None:
+        kw["negative_prompt"] = negative_prompt
+    return kw
+
+
 def _signals(brain_data, img_file, device=None):
     out = {"eeg_data": None, "fnirs_data": None, "ppg_data": None, "motion_data": None}
     rec = brain_data.get(img_file) if brain_data else None
@@ -129,8 +139,9 @@ def load_captions(caption_path):
 
 
 def process_image_batch(rank, world_size, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta,
-                        target_size, seed, strength=None, mask_dir=None):
-    """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image."""
+                        target_size, seed, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None):
+    """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image; true_cfg_scale /
+    negative_prompt: cfg_kwargs, the same for every image."""
     from PIL import Image
     from loongx_amd.dist import shard_range
     start_idx, end_idx = shard_range(len(image_files), rank, world_size)
@@ -140,21 +151,22 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
         prompt = captions.get(img_file, "Edit this image")
         result_img = inference_single_image(model, condition_img, prompt, condition_type=condition_type, position_delta=position_delta,
                                             target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device),
-                                            **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None))
+                                            **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None),
+                                            **cfg_kwargs(true_cfg_scale, negative_prompt))
         result_img.save(os.path.join(output_dir, img_file))
         if rank == 0 and (idx - start_idx) % 10 == 0:
             print(f"Process {rank}: Completed {idx - start_idx}/{end_idx - start_idx} images")
 
 
 def batch_inference(model, input_dir, output_dir, caption_path=None, condition_type="SEED", target_size=512, position_delta=[0, -32],
-                    seed=42, brain_data_path=None, strength=None, mask_dir=None):
+                    seed=42, brain_data_path=None, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None):
     """inference.py:255-339: all captioned images of a directory on one GPU."""
     os.makedirs(output_dir, exist_ok=True)
     brain_data = load_brain_data(brain_data_path) if brain_data_path and os.path.exists(brain_data_path) else {}
     captions = load_captions(caption_path)
     image_files = [f for f in captions if f.endswith((".png", ".jpg", ".jpeg"))]
     process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed,
-                        strength=strength, mask_dir=mask_dir)
+                        strength=strength, mask_dir=mask_dir, true_cfg_scale=true_cfg_scale, negative_prompt=negative_prompt)
     print(f"Processed {len(image_files)} images. Results saved to {output_dir}")
 
 
@@ -261,7 +273,7 @@ def distributed_inference_worker(rank, world_size, args, config, model_loaded_ev
         t0 = time.time()
         process_image_batch(rank, world_size, model, image_files, args.input_dir, args.output_dir, captions, brain_data, args.condition_type,
                             [args.position_delta_x, args.position_delta_y], args.target_size, args.seed, strength=args.strength,
-                            mask_dir=args.mask_dir)
+                            mask_dir=args.mask_dir, true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt)
         n_total, n, dt = len(image_files), len(image_files) // world_size, time.time() - t0
     if world_size > 1:
         dist.barrier()
@@ -299,9 +311,15 @@ def main(argv=None):
     p.add_argument("--mask_dir", type=str, default=None,
                    help="inpaint: a directory with one mask per input file name; white is repainted, black keeps the input image (generate(mask_image=))")
     p.add_argument("--mask_path", type=str, default=None, help="(--single_image) the mask of that image")
+    p.add_argument("--true_cfg_scale", type=float, default=None,
+                   help="true classifier-free guidance: extrapolate away from --negative_prompt by this factor, > 1 (generate(true_cfg_scale=)); "
+                        "each step then runs one forward at twice the batch")
+    p.add_argument("--negative_prompt", type=str, default=None, help="the prompt to guide away from (generate(negative_prompt=))")
     args = p.parse_args(argv)
     if args.synthetic and (args.strength is not None or args.mask_dir or args.mask_path):
         p.error("--strength / --mask_dir / --mask_path edit an input image: not with --synthetic")
+    if args.synthetic and (args.true_cfg_scale is not None or args.negative_prompt is not None):
+        p.error("--true_cfg_scale / --negative_prompt need a text encoder for the negative prompt: not with --synthetic")
     config = get_config()
     config.setdefault("model", {})
     if args.operands:
@@ -317,7 +335,8 @@ def main(argv=None):
         result_img = inference_single_image(model, condition_img, args.prompt, condition_type=args.condition_type,
                                             position_delta=[args.position_delta_x, args.position_delta_y], target_size=args.target_size,
                                             seed=args.seed, **_signals(brain_data, name),
-                                            **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path))
+                                            **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path),
+                                            **cfg_kwargs(args.true_cfg_scale, args.negative_prompt))
         os.makedirs(args.output_dir, exist_ok=True)
         output_path = os.path.join(args.output_dir, name)
         result_img.save(output_path)
@@ -335,7 +354,8 @@ def main(argv=None):
             model = load_model(args.checkpoint, config)
             batch_inference(model, args.input_dir, args.output_dir, args.caption_path, condition_type=args.condition_type,
                             target_size=args.target_size, position_delta=[args.position_delta_x, args.position_delta_y], seed=args.seed,
-                            brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir)
+                            brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir,
+                            true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt)
     else:
         print(f"Running distributed inference on {world} GPUs")
         mp.set_start_method("spawn", force=True)

@@ -641,10 +641,13 @@ __global__ void euler_kernel(float* __restrict__ x, const void* __restrict__ v, 
 __device__ __forceinline__ float scale_noise1(float x0, float z, float sigma, float one_minus_sigma) {
   return fmaf(sigma, z, __fmul_rn(one_minus_sigma, x0));
 }
-__device__ __forceinline__ float euler_blend1(float x, float v, float ds, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
-  const float e = fmaf(ds, v, x);
+// the stepped value e blended with the source noised to the next level
+__device__ __forceinline__ float blend1(float e, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
   const float r = scale_noise1(x0, z, sigma_next, one_minus_sigma);
   return fmaf(m, e, __fmul_rn(__fsub_rn(1.f, m), r));
+}
+__device__ __forceinline__ float euler_blend1(float x, float v, float ds, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
+  return blend1(fmaf(ds, v, x), x0, z, m, sigma_next, one_minus_sigma);
 }
 
 template <int VEC>
@@ -691,6 +694,53 @@ __global__ __launch_bounds__(256) void euler_blend_kernel(float* __restrict__ x,
         const float vk = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[k]) : ((const float*)v)[k];
         x[k] = euler_blend1(x[k], vk, ds, x0[k], z[k], m[k], sigma_next, one_minus_sigma);
       }
+    }
+  }
+}
+
+// ---- the guided step (lx_euler_step_cfg) --------------------------------------------------------------------------------------------
+// x and v hold two halves of n elements, [positive; negative]. g = vn + scale (vp - vn), the Euler step on g from the positive half of x,
+// the inpaint blend where BLEND, and the result stored to both halves: the order of include/lx.h, one rounding per named operation.
+// VEC = 4 reads and writes both halves 16 bytes at a time (8 for bf16 v). The host takes it only when the second halves x + n and v + n
+// are aligned as well as the first, which needs n % 4 == 0: there is no element tail on that path.
+__device__ __forceinline__ float euler_cfg1(float x, float vp, float vn, float ds, float scale) {
+  return fmaf(ds, fmaf(scale, __fsub_rn(vp, vn), vn), x);
+}
+__device__ __forceinline__ f32x4 load_v4(const void* __restrict__ v, int v_bf16, size_t i) {
+  if (v_bf16) {
+    const u32x2 p = *(const u32x2*)((const uint16_t*)v + i);
+    return f32x4{bf16_to_f32((uint16_t)(p[0] & 0xffffu)), bf16_to_f32((uint16_t)(p[0] >> 16)),
+                 bf16_to_f32((uint16_t)(p[1] & 0xffffu)), bf16_to_f32((uint16_t)(p[1] >> 16))};
+  }
+  return *(const f32x4*)((const float*)v + i);
+}
+
+template <int VEC, bool BLEND>
+__global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, float scale,
+                                                        const float* __restrict__ x0, const float* __restrict__ z,
+                                                        const float* __restrict__ m, float sigma_next, float one_minus_sigma, size_t n) {
+  const size_t items = n / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4) {
+      const f32x4 vp = load_v4(v, v_bf16, i), vn = load_v4(v, v_bf16, n + i);
+      f32x4 o = *(const f32x4*)(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = euler_cfg1(o[j], vp[j], vn[j], ds, scale);
+      if (BLEND) {
+        const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], a[j], b[j], mm[j], sigma_next, one_minus_sigma);
+      }
+      *(f32x4*)(x + i) = o;
+      *(f32x4*)(x + n + i) = o;
+    } else {
+      const float vp = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[i]) : ((const float*)v)[i];
+      const float vn = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[n + i]) : ((const float*)v)[n + i];
+      float o = euler_cfg1(x[i], vp, vn, ds, scale);
+      if (BLEND) o = blend1(o, x0[i], z[i], m[i], sigma_next, one_minus_sigma);
+      x[i] = o;
+      x[n + i] = o;
     }
   }
 }
@@ -1079,6 +1129,44 @@ extern "C" int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float
   if (vec) hipLaunchKernelGGL(euler_blend_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
   else hipLaunchKernelGGL(euler_blend_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
   LX_LAUNCH_CHECK("lx_euler_step_blend");
+  return LX_OK;
+}
+
+// [a, a + na) and [b, b + nb) bytes share an address
+static bool byte_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+
+template <int VEC>
+static void launch_euler_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z, const float* m,
+                             float sigma_next, size_t n, hipStream_t stream) {
+  const size_t items = n / VEC;
+  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  const float oms = 1.0f - sigma_next;
+  if (m) hipLaunchKernelGGL((euler_cfg_kernel<VEC, true>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, oms, n);
+  else hipLaunchKernelGGL((euler_cfg_kernel<VEC, false>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, oms, n);
+}
+
+extern "C" int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z,
+                                 const float* m, float sigma_next, size_t n, void* stream) {
+  LX_CHECK_ARG(x && v, "lx_euler_step_cfg: NULL x or v");
+  LX_CHECK_ARG(n > 0, "lx_euler_step_cfg: n == 0");
+  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_cfg: x0, z and m go together (all NULL: no blend)");
+  uint32_t scale_bits;
+  __builtin_memcpy(&scale_bits, &scale, sizeof scale_bits);
+  LX_CHECK_ARG((scale_bits & 0x7f800000u) != 0x7f800000u, "lx_euler_step_cfg: scale is not finite");
+  const size_t xbytes = 2 * n * sizeof(float), hbytes = n * sizeof(float);
+  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, hbytes) && !byte_ranges_overlap(x, xbytes, z, hbytes) &&
+                      !byte_ranges_overlap(x, xbytes, m, hbytes)),
+               "lx_euler_step_cfg: x0, z and m may not alias x[0, 2n) (it is updated in place)");
+  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_cfg: v may not alias x[0, 2n)");
+  // both halves of every operand: x + n and v + n are aligned only where n % 4 == 0
+  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
+  const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 && ((uintptr_t)v & v_align) == 0;
+  if (vec) launch_euler_cfg<4>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
+  else launch_euler_cfg<1>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
+  LX_LAUNCH_CHECK("lx_euler_step_cfg");
   return LX_OK;
 }
 

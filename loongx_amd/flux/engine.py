@@ -140,6 +140,9 @@ class DiTEngine:
         # lx_lora_scale_rows applies to the adapter scratch (TLs / tmod) right after it is written. None = every factor is 1: no such
         # launch anywhere. `lora_w_ns`: the same without lora_scale (the e4m3 down-projection takes lora_scale as its scalar argument).
         self.adapter_weights: Dict[str, object] = {}
+        # generate() under true CFG sets this to 2 for the steps of one call: the conditioning then holds [positive; negative] halves of
+        # the same images, and a per-image weight table of half its batch applies to each half.
+        self.adapter_weight_tiles = 1
         self.lora_w: Optional[torch.Tensor] = None
         self.lora_w_ns: Optional[torch.Tensor] = None
         self._lora_w_bufs: Dict = {}     # (B, R, which) -> the table's buffer: one address per shape, so step graphs can hold it
@@ -427,7 +430,7 @@ class DiTEngine:
 
     def adapter_weights_key(self):
         """What the adapter weights contribute to a conditioning's identity (tranformer_forward's cache key)."""
-        return tuple(sorted(self.adapter_weights.items()))
+        return tuple(sorted(self.adapter_weights.items())) + ((self.adapter_weight_tiles,) if self.adapter_weight_tiles != 1 else ())
 
     def _lora_tables(self, B: int) -> None:
         """lora_w / lora_w_ns of a conditioning with B images (see __init__), in engine-owned buffers whose address depends on the
@@ -438,6 +441,8 @@ class DiTEngine:
         rows, ones = [[] for _ in range(B)], True
         for name in self.w.active:
             w = self.adapter_weights.get(name, 1.0)
+            if isinstance(w, tuple) and len(w) * self.adapter_weight_tiles == B:
+                w = w * self.adapter_weight_tiles
             if isinstance(w, tuple) and len(w) != B:
                 raise ValueError(f"adapter {name!r}: {len(w)} per-image weights for a batch of {B} images")
             for b in range(B):

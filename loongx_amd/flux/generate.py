@@ -12,6 +12,10 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       (block.py:275-276, 336-337) the kernels saturate AND count; generate() reads the counter once per image and applies
       model_config["f16_overflow"]: "raise" (default; F16OverflowError), "warn", or "fallback" (the image is computed again from the
       same start latents with bf16 operands).
+  Q7  true classifier-free guidance (negative_prompt[_embeds], true_cfg_scale > 1; diffusers' FluxPipeline, the reference has none): the
+      brain signals act on the POSITIVE branch only. The negative embeddings are used as given -- never fused with, gated by or replaced
+      by brain embeddings: under brain_replace both branches would otherwise carry the same embedding and guidance would do nothing. Both
+      branches run as one forward at batch 2B per step, [positive; negative], and lx_euler_step_cfg steps both halves.
 """
 from __future__ import annotations
 
@@ -53,6 +57,21 @@ def vae_f16_overflow(vae, policy: Optional[str]):
         vae.f16_overflow = own
 
 
+@contextlib.contextmanager
+def adapter_weight_tiles(engine, tiles: int):
+    """A guided call runs [positive; negative] halves of the same images in one batch: inside the block a per-image adapter weight table
+    (set_adapters(names, [w per image])) of length B applies to each of the `tiles` parts of a conditioning with tiles x B images. Told to
+    the engine for the steps of one call, the way c_factor is; tiles == 1 or no engine: a no-op."""
+    if engine is None or tiles == 1:
+        yield
+        return
+    engine.adapter_weight_tiles = tiles
+    try:
+        yield
+    finally:
+        engine.adapter_weight_tiles = 1
+
+
 def get_config(config_path: str = None):
     config_path = config_path or os.environ.get("XFL_CONFIG")
     if not config_path:
@@ -70,9 +89,13 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
                    callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
                    image=None, image_latents: Optional[torch.Tensor] = None, mask_image=None,
-                   latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0, **kwargs):
-    """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline are named here
-    (so they are not among the swallowed **kwargs) and returned by prepare_inpaint_params."""
+                   latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0,
+                   negative_prompt: Union[str, List[str]] = None, negative_prompt_2=None,
+                   negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
+                   true_cfg_scale: float = 1.0, **kwargs):
+    """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline and the true-CFG
+    keywords of its FluxPipeline are named here (so they are not among the swallowed **kwargs) and returned by prepare_inpaint_params /
+    prepare_cfg_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
@@ -81,6 +104,49 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
 def prepare_inpaint_params(image=None, image_latents: Optional[torch.Tensor] = None, mask_image=None,
                            latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0, **kwargs):
     return image, image_latents, mask_image, latent_mask, strength
+
+
+def prepare_cfg_params(negative_prompt=None, negative_prompt_2=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                       true_cfg_scale: float = 1.0, **kwargs):
+    return negative_prompt, negative_prompt_2, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale
+
+
+def _fits_positive(name, neg, pos):
+    """negative embeddings differ from the positive ones in nothing but a batch of 1"""
+    if not isinstance(neg, torch.Tensor) or neg.dim() != pos.dim() or neg.shape[1:] != pos.shape[1:] or neg.shape[0] not in (1, pos.shape[0]):
+        raise ValueError(f"`{name}` must have the positive embeddings' shape {tuple(pos.shape)} (or a batch of 1), got "
+                         f"{tuple(neg.shape) if isinstance(neg, torch.Tensor) else type(neg).__name__}")
+
+
+def _true_cfg(negative_prompt, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale, prompt, prompt_embeds,
+              pooled_prompt_embeds) -> bool:
+    """generate()'s true-CFG arguments -> whether the call is guided (diffusers' rule: true_cfg_scale > 1 and a negative prompt given). Every
+    refusal is a ValueError on the host, before anything of the pipeline is touched; half a request is one RuntimeWarning and the plain call."""
+    s = true_cfg_scale
+    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s):
+        raise ValueError(f"true_cfg_scale must be a finite number, got {s!r}")
+    if negative_prompt is not None and negative_prompt_embeds is not None:
+        raise ValueError("Cannot forward both `negative_prompt` and `negative_prompt_embeds`.")
+    if (negative_prompt_embeds is None) != (negative_pooled_prompt_embeds is None):
+        raise ValueError("`negative_prompt_embeds` and `negative_pooled_prompt_embeds` have to be passed together.")
+    n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
+        prompt_embeds.shape[0] if prompt_embeds is not None else None
+    if negative_prompt is not None:
+        if not isinstance(negative_prompt, (str, list)):
+            raise ValueError(f"`negative_prompt` has to be of type `str` or `list` but is {type(negative_prompt)}")
+        if isinstance(negative_prompt, list) and n_prompts is not None and len(negative_prompt) not in (1, n_prompts):
+            raise ValueError(f"`negative_prompt` has {len(negative_prompt)} entries for a batch of {n_prompts} prompts: one, or one per prompt")
+    if negative_prompt_embeds is not None and prompt_embeds is not None and pooled_prompt_embeds is not None:
+        _fits_positive("negative_prompt_embeds", negative_prompt_embeds, prompt_embeds)
+        _fits_positive("negative_pooled_prompt_embeds", negative_pooled_prompt_embeds, pooled_prompt_embeds)
+    has_negative = negative_prompt is not None or negative_prompt_embeds is not None
+    if float(s) > 1 and not has_negative:
+        warnings.warn(f"true_cfg_scale={s} without a negative prompt: nothing to guide away from, running the plain call",
+                      RuntimeWarning, stacklevel=3)
+    elif has_negative and not float(s) > 1:
+        warnings.warn(f"a negative prompt with true_cfg_scale={s} (<= 1): guidance is off, running the plain call",
+                      RuntimeWarning, stacklevel=3)
+    return float(s) > 1 and has_negative
 
 
 def _inpaint_source(pipeline, image, image_latents, mask_image, latent_mask, strength, num_inference_steps, batch, tokens, height, width,
@@ -193,6 +259,10 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     # ---- img2img / inpaint arguments (diffusers FluxImg2ImgPipeline / FluxInpaintPipeline): checked, and the source encoded, before
     # anything of the pipeline is touched. The source image is the first draw from the global generator, as in diffusers' prepare_latents.
     image, image_latents, mask_image, latent_mask, strength = prepare_inpaint_params(**params)
+    # ---- true classifier-free guidance (diffusers FluxPipeline): its host-side refusals come first, with the inpaint ones
+    negative_prompt, negative_prompt_2, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale = prepare_cfg_params(**params)
+    do_true_cfg = _true_cfg(negative_prompt, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale, prompt, prompt_embeds,
+                            pooled_prompt_embeds)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
             prompt_embeds.shape[0] if prompt_embeds is not None else None
@@ -223,6 +293,11 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
         prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
         num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length, lora_scale=lora_scale)
+    if do_true_cfg:
+        negative_prompt_embeds, negative_pooled_prompt_embeds, _ = self.encode_prompt(
+            prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
+            pooled_prompt_embeds=negative_pooled_prompt_embeds, device=device, num_images_per_prompt=num_images_per_prompt,
+            max_sequence_length=max_sequence_length, lora_scale=lora_scale)
 
     # ---- CS3 encoders + DGF fusion: once per image, outside the loop (generate.py:168-258) ----------
     if use_brain_condition and any(c is not None for c in (additional_condition1, additional_condition2,
@@ -256,6 +331,18 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                 pooled_prompt_embeds = pooled_prompt_embeds_brain.expand(pooled_prompt_embeds.shape[0], -1)
         elif prompt_embeds_brain is not None and pooled_prompt_embeds_brain is not None:
             prompt_embeds, pooled_prompt_embeds = prompt_embeds_brain, pooled_prompt_embeds_brain
+
+    # ---- true CFG: the negative branch is the second half of ONE batch of 2·B·n, built here once per image. Its embeddings are used as
+    # given -- the brain signals above act on the positive half only (under brain_replace both halves would otherwise carry the same
+    # embedding and guidance would do nothing)
+    if do_true_cfg:
+        if negative_prompt_embeds.shape[0] != prompt_embeds.shape[0]:           # (one negative prompt for the whole batch)
+            negative_prompt_embeds = negative_prompt_embeds[:1].expand(prompt_embeds.shape[0], -1, -1)
+            negative_pooled_prompt_embeds = negative_pooled_prompt_embeds[:1].expand(pooled_prompt_embeds.shape[0], -1)
+        _fits_positive("negative_prompt_embeds", negative_prompt_embeds, prompt_embeds)
+        _fits_positive("negative_pooled_prompt_embeds", negative_pooled_prompt_embeds, pooled_prompt_embeds)
+        prompt_embeds = torch.cat([prompt_embeds, negative_prompt_embeds.to(prompt_embeds.dtype)])
+        pooled_prompt_embeds = torch.cat([pooled_prompt_embeds, negative_pooled_prompt_embeds.to(pooled_prompt_embeds.dtype)])
 
     # ---- latents + condition tokens ----------------------------------------------------------------------
     num_channels_latents = self.transformer.config.in_channels // 4
@@ -293,6 +380,17 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         latents = self.scheduler.scale_noise(image_latents, n_schedule - num_inference_steps, noise)
         num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
     step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
+    n_images = latents.shape[0]
+    if do_true_cfg:
+        # the start latents twice ([positive; negative]; the draw above stays [B·n, ...], so the generator is consumed as in the plain call),
+        # the condition tokens and a [B·n] attention mask for both halves; image_latents / noise / mask stay [B·n, ...] (lx_euler_step_cfg)
+        step_kwargs["true_cfg_scale"] = float(true_cfg_scale)
+        latents = torch.cat([latents, latents])
+        if use_condition:
+            condition_latents = condition_latents.repeat(2 * n_images // condition_latents.shape[0], 1, 1)
+        user_mask = (self.joint_attention_kwargs or {}).get("attention_mask")
+        if isinstance(user_mask, torch.Tensor) and user_mask.dim() == 4 and user_mask.shape[0] == n_images and n_images > 1:
+            self._joint_attention_kwargs = dict(self.joint_attention_kwargs, attention_mask=torch.cat([user_mask, user_mask]))
     self._num_timesteps = len(timesteps)
     guidance = None
     if self.transformer.config.guidance_embeds:
@@ -316,7 +414,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     start_latents, operands_used = latents, None
 
     def denoise(latents, prompt_embeds, model_config):
-        with self.progress_bar(total=num_inference_steps) as progress_bar:
+        with adapter_weight_tiles(engine, 2 if do_true_cfg else 1), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
                     continue
@@ -332,15 +430,22 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                 latents = self.scheduler.step(noise_pred, t, latents, return_dict=False, **step_kwargs)[0]
                 if callback_on_step_end is not None:
                     scope = dict(locals())                                  # (a comprehension has its own locals() before 3.12)
+                    if do_true_cfg:
+                        scope["latents"] = shown = latents[:n_images]       # (the halves are equal: a callback sees the images' own)
                     callback_kwargs = {}
                     for k in callback_on_step_end_tensor_inputs:
                         callback_kwargs[k] = scope[k]
                     callback_outputs = callback_on_step_end(self, i, t, callback_kwargs)
-                    latents = callback_outputs.pop("latents", latents)
+                    if do_true_cfg:
+                        given = callback_outputs.pop("latents", shown)
+                        if given is not shown:                              # (its latents go to both halves: a copy, made only when it returns some)
+                            latents = torch.cat([given, given])
+                    else:
+                        latents = callback_outputs.pop("latents", latents)
                     prompt_embeds = callback_outputs.pop("prompt_embeds", prompt_embeds)
                 if i == len(timesteps) - 1 or ((i + 1) > num_warmup_steps and (i + 1) % self.scheduler.order == 0):
                     progress_bar.update()
-        return latents
+        return latents[:n_images] if do_true_cfg else latents
 
     latents = denoise(start_latents, prompt_embeds, model_config)
     if engine is not None and engine.f16:

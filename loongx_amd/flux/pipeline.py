@@ -88,21 +88,33 @@ class FlowMatchEulerDiscreteScheduler:
         sigma = float(self._sig_host[self._sigma_index(sigma_index_or_timestep)])
         return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None):
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None):
         """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
         inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
-        level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend)."""
+        level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend).
+        true_cfg_scale = s: sample and model_output have a leading dimension 2B, [positive; negative]; both halves of prev are the step of
+        the positive half along neg + s * (pos - neg) (diffusers' FluxPipeline true CFG), in one launch (lx_euler_step_cfg). inpaint then has
+        the shape of one half."""
         i = self._step_index
         ds = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i]))
         x = sample.to(torch.float32).clone() if (sample.dtype != torch.float32 or not sample.is_contiguous()) else sample.clone()
         v = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
-        if inpaint is None:
+        half = tuple(x.shape)
+        if true_cfg_scale is not None:
+            if x.dim() < 1 or x.shape[0] % 2 or x.shape[0] == 0 or v.shape != x.shape:
+                raise ValueError(f"step(true_cfg_scale=...): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one shape "
+                                 "with an even leading dimension, [positive; negative]")
+            half = (x.shape[0] // 2,) + tuple(x.shape[1:])
+        if inpaint is not None:
+            x0, z, m = inpaint
+            if not (tuple(x0.shape) == tuple(z.shape) == tuple(m.shape) == half):
+                raise ValueError(f"step(inpaint=...): image_latents {tuple(x0.shape)}, noise {tuple(z.shape)} and mask {tuple(m.shape)} must "
+                                 f"have the latents' shape {half}")
+        if true_cfg_scale is not None:
+            ops.euler_step_cfg(x, v.contiguous(), ds, float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
+        elif inpaint is None:
             ops.euler_step(x, v.contiguous(), ds)
         else:
-            x0, z, m = inpaint
-            if not (x0.shape == z.shape == m.shape == x.shape):
-                raise ValueError(f"step(inpaint=...): image_latents {tuple(x0.shape)}, noise {tuple(z.shape)} and mask {tuple(m.shape)} must "
-                                 f"have the latents' shape {tuple(x.shape)}")
             ops.euler_step_blend(x, v.contiguous(), ds, x0, z, m, float(self._sig_host[i + 1]))
         self._step_index += 1
         return (x.to(model_output.dtype),)

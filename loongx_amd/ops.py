@@ -618,6 +618,26 @@ def euler_step_blend(x: torch.Tensor, v: torch.Tensor, dsigma: float, x0: torch.
                                   float(sigma_next), n, _stream()), "lx_euler_step_blend")
 
 
+def euler_step_cfg(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale: float, inpaint=None, sigma_next: float = 0.0) -> None:
+    """The step under true classifier-free guidance, in place (lx_euler_step_cfg): x fp32 and v fp32 or bf16 hold [positive; negative]
+    halves of n elements each; both halves of x become x[:n] + dsigma * (vn + scale * (vp - vn)). inpaint = (x0, z, m), fp32 with n
+    elements each: blended with the source at sigma_next as euler_step_blend does, once, for both halves. All contiguous."""
+    _req(x, torch.float32, "x")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    n = x.numel() // 2
+    assert x.numel() == 2 * n and v.numel() == 2 * n, "euler_step_cfg: x and v hold two halves of one element count"
+    x0 = z = m = None
+    if inpaint is not None:
+        x0, z, m = inpaint
+        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
+        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_cfg: x0, z and m have the element count of one half"
+    assert all(t.is_contiguous() for t in (x, v, x0, z, m) if t is not None), "euler_step_cfg: contiguous operands"
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    check(lib.lx_euler_step_cfg(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), float(scale), ptr(x0), ptr(z), ptr(m),
+                                float(sigma_next), n, _stream()), "lx_euler_step_cfg")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
