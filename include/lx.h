@@ -281,6 +281,14 @@ int lx_ln_modulate_lora_segs(const float* X, int ldx, const lx_ln_seg* seg, int 
 int lx_ln_modulate_lora_f16_segs(const float* X, int ldx, const lx_ln_seg* seg, int n_seg, int mod_ld, void* Y, int ldy, int D,
                                  float eps, const void* Adown, int R, float* T, int ldt, int lora_row0, int lora_rows,
                                  int32_t* f16_ovf, void* stream);
+/* Step-cache probe. For rows [0, M) of X (fp32, ldx): m = LN(x) * (1 + scale[b]) + shift[b], b = row / rows_per_batch,
+ * exactly lx_ln_modulate's fp32 value before its 16-bit store. row_sums[row] = { Σ_c |m − P[row,c]|, Σ_c |P[row,c]| } with P as found;
+ * then P[row,:] = m. sums[0..1] (double) = the row values added in row order. X is not written.
+ * One wave per row and a second one-wave launch for the totals: no atomics, the sums are the same bits from run to run.
+ * D % 4 == 0, D <= 16384; ldx, ldp, mod_ld multiples of 4 and >= D; X, shift, scale, P 16-byte aligned, row_sums and sums 8-byte;
+ * P may not overlap X. Everything else LX_ERR_INVALID, before any launch. */
+int lx_ln_modulate_delta(const float* X, int ldx, const float* shift, const float* scale, int mod_ld, float* P, int ldp,
+                         int M, int D, int rows_per_batch, float eps, float* row_sums /* [M,2] */, double* sums /* [2] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-head RMSNorm (weight, eps) + interleaved-pair RoPE on Q and K, in place, and V transposed into the

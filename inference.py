@@ -86,7 +86,15 @@ def inference_single_image(model, condition_img, prompt, condition_type="SEED", 
                       model_config=model.model_config, default_lora=True, additional_condition1=eeg_data,
                       additional_condition2=fnirs_data, additional_condition3=ppg_data, additional_condition4=motion_data,
                       use_brain_condition=use_brain_condition, fuse_flag=False, **kw, **generate_kwargs)
+    _print_step_cache(result)
     return result.images[0]
+
+
+def _print_step_cache(result):
+    """--step_cache_thresh: how many of the image's denoise steps ran their blocks (generate()'s lx_step_cache report)"""
+    rep = getattr(result, "lx_step_cache", None)
+    if rep is not None:
+        print(f"step cache: computed {len(rep['computed'])} of {rep['steps']} steps (threshold {rep['thresh']:g})")
 
 
 def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
@@ -193,6 +201,7 @@ def inference_single(model, item, condition_type, position_delta, target_size, u
                    model_config=model.model_config, default_lora=True, additional_condition1=sig["eeg"],
                    additional_condition2=sig["fnirs"], additional_condition3=sig["ppg"], additional_condition4=sig["motion"],
                    use_brain_condition=sig["eeg"] is not None or sig["fnirs"] is not None, fuse_flag=False)      # inference.py:99-117
+    _print_step_cache(out)
     return out.images[0]
 
 
@@ -315,6 +324,9 @@ def main(argv=None):
                    help="true classifier-free guidance: extrapolate away from --negative_prompt by this factor, > 1 (generate(true_cfg_scale=)); "
                         "each step then runs one forward at twice the batch")
     p.add_argument("--negative_prompt", type=str, default=None, help="the prompt to guide away from (generate(negative_prompt=))")
+    p.add_argument("--step_cache_thresh", type=float, default=None,
+                   help="step caching (TeaCache; model_config['step_cache_thresh']): skip the blocks of denoise steps whose accumulated input "
+                        "distance stays under this threshold, > 0 (about 0.25 .. 0.8; larger skips more); prints the computed steps per image")
     args = p.parse_args(argv)
     if args.synthetic and (args.strength is not None or args.mask_dir or args.mask_path):
         p.error("--strength / --mask_dir / --mask_path edit an input image: not with --synthetic")
@@ -325,6 +337,8 @@ def main(argv=None):
     if args.operands:
         config["model"]["operands"] = args.operands
     config["model"]["f16_overflow"] = args.f16_overflow
+    if args.step_cache_thresh is not None:
+        config["model"]["step_cache_thresh"] = args.step_cache_thresh
 
     if args.single_image and args.prompt and not args.synthetic:
         from PIL import Image

@@ -798,6 +798,59 @@ __global__ __launch_bounds__(256) void lora_scale_rows_kernel(float* __restrict_
   }
 }
 
+// ---- step-cache probe (lx_ln_modulate_delta) ----------------------------------------------------------------------------------------
+// One wave per row, the three-pass row body of row_common.h: m = LN(x) * (1 + scale) + shift as ln_emit computes it, kept in fp32. While a
+// chunk of m is at hand the lane reads the same chunk of P (the previous step's m), adds |m - P| and |P| to its two sums and stores m over
+// it; lane sums run in chunk order, across lanes wave_sum's tree, lane 0 stores the row's pair. Nothing crosses a wave: no LDS, no atomics.
+__global__ __launch_bounds__(256) void ln_modulate_delta_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ shift,
+                                                                const float* __restrict__ scale, int mod_ld, float* __restrict__ P, int ldp,
+                                                                int M, int D, int rows_per_batch, float eps, float* __restrict__ row_sums) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int lane = threadIdx.x & 63;
+  const float* xr = X + (size_t)row * ldx;
+  float mean, rstd;
+  ln_row_stats(xr, D, lane, mean, rstd, eps);
+  const int b = row / rows_per_batch;
+  float* pr = P + (size_t)row * ldp;
+  float s1 = 0.f, s2 = 0.f;
+  ln_emit(xr, scale + (size_t)b * mod_ld, shift + (size_t)b * mod_ld, D, lane, mean, rstd, [&](int c, const float (&o)[4]) {
+    const f32x4 p = *(const f32x4*)(pr + c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      s1 += fabsf(o[k] - p[k]);
+      s2 += fabsf(p[k]);
+    }
+    *(f32x4*)(pr + c) = f32x4{o[0], o[1], o[2], o[3]};
+  });
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  if (lane == 0) *(f32x2*)(row_sums + 2 * (size_t)row) = f32x2{s1, s2};
+}
+
+// The M row pairs added in row order, in double, by ONE wave: a lane loads the pair of row r0 + lane, the wave then walks its 64 lanes in
+// order (v_readlane: every lane carries the same running sums). The order is fixed by construction, so the totals are the same bits from
+// run to run; rows past M add +0.
+__global__ __launch_bounds__(64) void row_pairs_total_kernel(const float* __restrict__ row_sums, int M, double* __restrict__ sums) {
+  const int lane = threadIdx.x;
+  double a = 0.0, b = 0.0;
+  for (int r0 = 0; r0 < M; r0 += 64) {
+    f32x2 v = {0.f, 0.f};
+    if (r0 + lane < M) v = *(const f32x2*)(row_sums + 2 * (size_t)(r0 + lane));
+    const float f0 = v[0], f1 = v[1];      // (plain floats first: __builtin_bit_cast of a vector-element lvalue reads element 0 for both)
+    const int v0 = __builtin_bit_cast(int, f0), v1 = __builtin_bit_cast(int, f1);
+#pragma unroll
+    for (int l = 0; l < 64; ++l) {
+      a += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(v0, l));
+      b += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(v1, l));
+    }
+  }
+  if (lane == 0) {
+    sums[0] = a;
+    sums[1] = b;
+  }
+}
+
 }  // namespace
 
 // The five lx_ln_modulate* entry points. `name` is the one that was called: it reports the segment count and f16_ovf; everything else
@@ -1167,6 +1220,24 @@ extern "C" int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float d
   if (vec) launch_euler_cfg<4>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
   else launch_euler_cfg<1>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
   LX_LAUNCH_CHECK("lx_euler_step_cfg");
+  return LX_OK;
+}
+
+extern "C" int lx_ln_modulate_delta(const float* X, int ldx, const float* shift, const float* scale, int mod_ld, float* P, int ldp, int M, int D,
+                                    int rows_per_batch, float eps, float* row_sums, double* sums, void* stream) {
+  LX_CHECK_ARG(X && shift && scale && P && row_sums && sums, "lx_ln_modulate_delta: NULL operand");
+  LX_CHECK_ARG(M > 0 && rows_per_batch > 0, "lx_ln_modulate_delta: M=%d and rows_per_batch=%d must be > 0", M, rows_per_batch);
+  LX_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 16384, "lx_ln_modulate_delta: D=%d must be a multiple of 4 and <= 16384", D);
+  LX_CHECK_ARG(ldx % 4 == 0 && ldp % 4 == 0 && mod_ld % 4 == 0 && ldx >= D && ldp >= D && mod_ld >= D,
+               "lx_ln_modulate_delta: ldx/ldp/mod_ld must be multiples of 4 and >= D");
+  LX_CHECK_ARG((((uintptr_t)X | (uintptr_t)shift | (uintptr_t)scale | (uintptr_t)P) & 15) == 0 &&
+                   (((uintptr_t)row_sums | (uintptr_t)sums) & 7) == 0, "lx_ln_modulate_delta: misaligned operand");
+  const size_t xbytes = ((size_t)(M - 1) * ldx + D) * sizeof(float), pbytes = ((size_t)(M - 1) * ldp + D) * sizeof(float);
+  LX_CHECK_ARG(!byte_ranges_overlap(X, xbytes, P, pbytes), "lx_ln_modulate_delta: P may not overlap X");
+  hipLaunchKernelGGL(ln_modulate_delta_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, shift, scale, mod_ld, P, ldp, M, D,
+                     rows_per_batch, eps, row_sums);
+  hipLaunchKernelGGL(row_pairs_total_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)row_sums, M, sums);
+  LX_LAUNCH_CHECK("lx_ln_modulate_delta");
   return LX_OK;
 }
 

@@ -24,6 +24,7 @@ import torch
 from .. import ops
 from ..ops import LX_EPI_RESID_F32, LX_EPI_STORE_F32
 from .modes import E4M3Mode, Mode16, SplitMode
+from .step_cache import StepCacheState, normalise_model_config, step_cache_config
 from .weights import FluxConfig, PackedWeights
 
 NEG_INF = float("-inf")
@@ -187,6 +188,13 @@ class DiTEngine:
         self.KC = self.VTC = None        # [layers, M, D] keys / [layers, B, H, 128, vt_ld] V^T, allocated on first use
         self.KC2 = self.VTC2 = None      # precise mode's: [layers, M, 2D] key pairs (hi | lo) / [layers, 2, B, H, 128, vt_ld] V^T pairs
         self.KC8 = self.VTC8 = None      # attn_fp8's: [layers, M, D] e4m3 keys / [layers, B, H, 128, vt_ld] e4m3 V^T (half the bf16 images)
+        # Step cache (model_config step_cache_thresh; step_cache.py has the rule): decided per conditioning (set_conditioning). With it on a
+        # step is three parts -- probe, body, reuse (_forward_step_cache) -- and the host reads one pair of doubles between the first and the
+        # next. The buffers exist only once a conditioning has asked for them, and then until the shape changes (step graphs hold them):
+        #   sc_m fp32 [B*N, D]: the image stream's norm1 input of double block 0 at the previous step;  sc_R fp32 [B*N, D]: X0 during a
+        #   computed step's blocks, then the residual X_img - X0 that skipped steps add;  sc_rows / sc_sums / sc_host: the probe's sums.
+        self.step_cache: Optional[StepCacheState] = None
+        self.sc_m = self.sc_R = self.sc_rows = self.sc_sums = self.sc_host = None
         # (Round 5 removed three measured-negative options that lived here as environment switches: the q/k/v adapters' down-projection
         # inside ln_modulate (LX_LN_LORA: -1.1 %; it could absorb the 57 launches per step that read the AdaLN-normalised stream, not the 75
         # that read an attention output or a GELU hidden), adapter rows on merged weights W' = W + s B A (LX_LORA_MERGE: +11.5 GB, the GEMMs
@@ -252,6 +260,8 @@ class DiTEngine:
         self.cond_ready = False
         self.KC = self.VTC = self.KC2 = self.VTC2 = self.KC8 = self.VTC8 = None      # per-layer key / V^T images of the condition cache: shape-bound
         self.cond_cache = self.cond_cached = False
+        self.step_cache = None
+        self.sc_m = self.sc_R = self.sc_rows = self.sc_sums = None      # the step cache's buffers: shape-bound
         self.XN2 = self.Y32 = self.YA = self.lat2 = None          # precise-mode buffers, allocated by _setup_precise()
         self.XN8 = self.Y8 = None                                  # fp8-GEMM operand images, allocated by _setup_fp8()
 
@@ -391,7 +401,7 @@ class DiTEngine:
 
     def drop_conditioning(self) -> None:
         """LxFluxTransformer.invalidate_conditioning: the conditioning is over, its mask and its prepared schedule go with it."""
-        self.cond_ready, self.cond_mask, self.sched = False, None, None
+        self.cond_ready, self.cond_mask, self.sched, self.step_cache = False, None, None, None
 
     def set_adapter_weights(self, weights: Optional[Dict]) -> None:
         """{adapter name: w}: w a float, or one float per image of the conditioning (a sequence or 1-D tensor of length B, checked by
@@ -750,7 +760,8 @@ class DiTEngine:
         B, T = prompt_embeds.shape[0], prompt_embeds.shape[1]
         N = img_ids.shape[0]
         C = 0 if condition_latents is None else condition_latents.shape[1]
-        self.cond_mask, self.cond_ready = None, False
+        self.cond_mask, self.cond_ready, self.step_cache = None, False, None
+        step_cache = step_cache_config(model_config)          # (a bad threshold or coefficient list: ValueError)
         refuse_wide_lora_modes(w, model_config, self.precise_default)
         self._lora_tables(B)             # (a per-image adapter weight of another length than B: ValueError)
         mask = None
@@ -761,6 +772,9 @@ class DiTEngine:
         self.setup(B, T, N, C)
         self.gemm_ws()                   # allocated here, outside any stream capture
         self._select_mode(model_config, c_factor)
+        normalise_model_config(self.model_config)             # (it goes into the step graphs' key, which is hashed)
+        if step_cache is not None:
+            self._setup_step_cache()
         if self.model_config.get("add_cond_attn", False) and C and C != N:
             raise ValueError("add_cond_attn adds the condition attention output onto the image stream: needs C == N")
         f32 = torch.float32
@@ -800,6 +814,7 @@ class DiTEngine:
         self.cond_ready = True
         self.cond_cached = False          # a new condition stream: the per-layer key / value images are stale
         self.sched = None
+        self.step_cache = StepCacheState(*step_cache) if step_cache is not None else None
 
     # ------------------------------------------------------------------------------------------ arithmetic mode
     def _select_mode(self, model_config: Optional[Dict], c_factor: Optional[float], gemm_fp8: bool = True) -> None:
@@ -1051,12 +1066,15 @@ class DiTEngine:
 
     def _forward_eager(self, latents: torch.Tensor, timestep: torch.Tensor, mods_ready: bool = False) -> torch.Tensor:
         self.embed_step_inputs(latents, timestep, mods_ready)
+        self._blocks()
+        return self.final_layer()
+
+    def _blocks(self) -> None:
         for i in range(self.cfg.num_layers):
             self.double_block(i)
         last = self.cfg.num_single_layers - 1
         for j in range(self.cfg.num_single_layers):
             self.single_block(j, image_out_only=(j == last))
-        return self.final_layer()
 
     def forward(self, latents: torch.Tensor, timestep: torch.Tensor, step_index: Optional[int] = None) -> torch.Tensor:
         """latents fp32 [B,N,in_channels], timestep [B] in 0..1 -> velocity fp32 [B,N,in_channels] (engine-owned buffer).
@@ -1066,7 +1084,8 @@ class DiTEngine:
         the launch-bound gaps between the short kernels disappear.  LX_GRAPH=0 disables capture.
 
         `step_index`: position of `timestep` in the schedule given to prepare_schedule(); the step then takes its
-        modulation vectors from that table instead of re-streaming the modulation weights."""
+        modulation vectors from that table instead of re-streaming the modulation weights. A conditioning with the step cache on
+        (model_config step_cache_thresh) needs it: the step then runs as _forward_step_cache's three parts."""
         if not self.cond_ready:
             raise RuntimeError("call set_conditioning() before forward()")
         pre = step_index is not None and self.sched is not None
@@ -1096,6 +1115,8 @@ class DiTEngine:
                 else:
                     self.KC = torch.zeros(nl, self.M, D, dtype=bf16, device=self.device)
                     self.VTC = torch.zeros((nl,) + vts, dtype=bf16, device=self.device)
+        if self.step_cache is not None:
+            return self._forward_step_cache(latents, step_index, pre, not self.use_graph or timed, skip)
         if not self.use_graph or timed:
             if pre:
                 self.mods.copy_(self.sched[1][step_index])
@@ -1108,22 +1129,10 @@ class DiTEngine:
             return out
         self.g_lat.copy_(latents.reshape(self.g_lat.shape))
         self.g_t.copy_(timestep.to(device=self.device, dtype=torch.float32).reshape(-1))
-        # The captured launches reference only engine-owned buffers, so one graph serves every image with the same
-        # shape and code path (LoRA rows, attention bias table, add_cond_attn ...): key it on exactly those.
-        key = (self.shape, tuple(sorted(self.model_config.items())), self.c_factor, pre, self.pair_plan, self.precise, self.gemm_fp8, self.f16,
-               getattr(self.w, "q_log2_version", 0),      # (a weight broadcast refreshes the scaled norm_q tensors and the per-layer bounds)
-               getattr(self.w, "weights_version", 0),     # (... and moves this one unconditionally: dist.broadcast_packed_weights)
-               self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, self._w16_gen if self.f16 else 0,
-               # the adapter set (its tensors' addresses are in the launches) and whether the adapter-weight tables exist (their launches)
-               getattr(self.w, "lora_version", 0), tuple(None if t is None else t.data_ptr() for t in (self.lora_w, self.lora_w_ns)),
-               # the masked launches hold the workspace's address and the mask's tile geometry (dtype, broadcast dims), never the mask itself:
-               # a new mask of the same form is a new prep into the same workspace (set_conditioning), which the same graph then reads
-               None if self.cond_mask is None else (self._mask_ws.data_ptr(), self.cond_mask.dtype, tuple(self.cond_mask.shape[:3])))
+        key = self._graph_key(pre, skip)
         g = self.graphs.get(key)
         if g is None:
-            mode = (self.precise, self.gemm_fp8, self.f16, bool(self.model_config.get("attn_fp8", False)), self.latent_lora, self.C > 0, skip,
-                    self.lora_w is not None or self.lora_w_ns is not None,
-                    None if self.cond_mask is None else self.cond_mask.dtype == torch.bool)      # (the bit and the bias form of the masked kernel)
+            mode = self._warm_mode(skip)
             self.cond_skip = skip
             try:
                 if mode not in self._warmed:                          # lazy code-object loads / buffer allocations must not happen inside capture
@@ -1143,6 +1152,134 @@ class DiTEngine:
         g.replay()
         self.cond_cached = self.cond_cache
         return self.out.view(self.B, self.N, self.cfg.in_channels)
+
+    def _graph_key(self, pre: bool, skip: bool):
+        """The captured launches reference only engine-owned buffers, so one graph serves every image with the same shape and code path
+        (LoRA rows, attention bias table, add_cond_attn ...): key it on exactly those."""
+        return (self.shape, tuple(sorted(self.model_config.items())), self.c_factor, pre, self.pair_plan, self.precise, self.gemm_fp8, self.f16,
+                getattr(self.w, "q_log2_version", 0),      # (a weight broadcast refreshes the scaled norm_q tensors and the per-layer bounds)
+                getattr(self.w, "weights_version", 0),     # (... and moves this one unconditionally: dist.broadcast_packed_weights)
+                self.cond_cache, skip, self.ln_lora, self.qkv_epilogue, self._w16_gen if self.f16 else 0,
+                # the adapter set (its tensors' addresses are in the launches) and whether the adapter-weight tables exist (their launches)
+                getattr(self.w, "lora_version", 0), tuple(None if t is None else t.data_ptr() for t in (self.lora_w, self.lora_w_ns)),
+                # the masked launches hold the workspace's address and the mask's tile geometry (dtype, broadcast dims), never the mask itself:
+                # a new mask of the same form is a new prep into the same workspace (set_conditioning), which the same graph then reads
+                None if self.cond_mask is None else (self._mask_ws.data_ptr(), self.cond_mask.dtype, tuple(self.cond_mask.shape[:3])),
+                self.step_cache is not None)               # (the entry is then the step's three parts: _forward_step_cache)
+
+    def _warm_mode(self, skip: bool):
+        """The kernel set of a forward, as the `_warmed` set remembers it."""
+        return (self.precise, self.gemm_fp8, self.f16, bool(self.model_config.get("attn_fp8", False)), self.latent_lora, self.C > 0, skip,
+                self.lora_w is not None or self.lora_w_ns is not None,
+                None if self.cond_mask is None else self.cond_mask.dtype == torch.bool,      # (the bit and the bias form of the masked kernel)
+                self.step_cache is not None)
+
+    # ------------------------------------------------------------------------------------------ step cache
+    def _setup_step_cache(self) -> None:
+        """The step cache's buffers (see __init__), allocated by set_conditioning(), outside any capture."""
+        if self.sc_m is None:
+            rows, D, dev = self.B * self.N, self.cfg.inner_dim, self.device
+            self.sc_m = torch.zeros(rows, D, dtype=torch.float32, device=dev)
+            self.sc_R = torch.zeros(rows, D, dtype=torch.float32, device=dev)
+            self.sc_rows = torch.zeros(rows, 2, dtype=torch.float32, device=dev)
+            self.sc_sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        if self.sc_host is None:
+            self.sc_host = torch.zeros(2, dtype=torch.float64).pin_memory()
+
+    def _sc_probe(self, latents: torch.Tensor) -> None:
+        """Part 1 of a step (self.mods holds the step's row of the schedule table): x_embedder(latents) into the image rows of X, and the
+        distance of double block 0's image norm1 input from the previous step's (lx_ln_modulate_delta: sc_m is replaced, sc_sums written)."""
+        D, b, x = self.cfg.inner_dim, self.cfg.mod_base_double(0), self.rows(self.X, "img")
+        self.mode.embed(latents.reshape(self.B * self.N, -1), "x_embedder", x, lora=self.latent_lora, step=True)
+        ops.ln_modulate_delta(x, self.mods[:, b:], self.mods[:, b + D:], self.sc_m, self.N, self.sc_rows, self.sc_sums, mod_ld=self.mods.stride(0))
+
+    def _sc_body(self) -> torch.Tensor:
+        """Part 2, a computed step: what _forward_eager runs after the image embed, with X0 = the embedded image rows kept (in sc_R) and
+        replaced by the residual R = fl32(X_img - X0) once the blocks are through."""
+        x = self.rows(self.X, "img")
+        self.rows(self.X, "txt").copy_(self.X_txt_init)
+        if self.C and not self.cond_skip:
+            self.rows(self.X, "cond").copy_(self.X_cond_init)
+        self.sc_R.copy_(x)
+        self._blocks()
+        torch.sub(x, self.sc_R, out=self.sc_R)
+        return self.final_layer()
+
+    def _sc_reuse(self) -> torch.Tensor:
+        """Part 2, a skipped step: X_img = fl32(X0 + R) on the freshly embedded image rows. No block runs; the text and condition rows are
+        not read by the final layer."""
+        x = self.rows(self.X, "img")
+        torch.add(x, self.sc_R, out=x)
+        return self.final_layer()
+
+    def _sc_rel(self) -> float:
+        """The probe's two sums -> rel: one 16-byte synchronous read through the pinned host mirror."""
+        self.sc_host.copy_(self.sc_sums, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        s1, s2 = float(self.sc_host[0]), float(self.sc_host[1])
+        return s1 / s2 if s2 > 0.0 else float("inf")
+
+    def _forward_step_cache(self, latents: torch.Tensor, step_index: Optional[int], pre: bool, eager: bool, skip: bool) -> torch.Tensor:
+        """forward() with the step cache on: probe, the host's decision (step_cache.py), then the blocks or the cached residual. The three
+        parts are launched eagerly (`eager`) or replayed from one graph entry (probe, body, reuse) under the conditioning's graph key."""
+        sc = self.step_cache
+        if not pre:
+            raise ValueError("step_cache_thresh needs the schedule: pass step_index to forward() after prepare_schedule() "
+                             "(tranformer_forward: lx_schedule=(i, timesteps))")
+        if step_index == 0:
+            sc.reset()
+        if not eager:
+            self.g_lat.copy_(latents.reshape(self.g_lat.shape))
+            latents = self.g_lat
+        self.mods.copy_(self.sched[1][step_index])
+        self.cond_skip = skip
+        try:
+            parts = None
+            if not eager:
+                key = self._graph_key(pre, skip)
+                parts = self.graphs.get(key)
+                if parts is None:
+                    mode = self._warm_mode(skip)
+                    if mode not in self._warmed:           # all three parts once, eagerly; what the rule carries over (m, R) is put back
+                        keep = None if step_index == 0 else (self.sc_m.clone(), self.sc_R.clone())
+                        self._sc_probe(latents)
+                        self._sc_body()
+                        self._sc_probe(latents)
+                        self._sc_reuse()
+                        torch.cuda.synchronize(self.device)
+                        if keep is not None:
+                            self.sc_m.copy_(keep[0])
+                            self.sc_R.copy_(keep[1])
+                        self._warmed.add(mode)
+                    if len(self.graphs) >= 4:
+                        self.graphs.clear()
+                    parts = []
+                    for part in (lambda: self._sc_probe(self.g_lat), self._sc_body, self._sc_reuse):
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            part()
+                        parts.append(g)
+                    parts = self.graphs[key] = tuple(parts)
+            if parts is None:
+                self._sc_probe(latents)
+            else:
+                parts[0].replay()
+            rel = self._sc_rel() if step_index > 0 else None
+            compute = sc.step(step_index, len(self.sched[0]), rel)
+            if parts is None:
+                self._sc_body() if compute else self._sc_reuse()
+            else:
+                parts[1 if compute else 2].replay()
+        finally:
+            self.cond_skip = False
+        if compute:
+            self.cond_cached = self.cond_cache          # (a skipped step touches none of the per-layer condition images)
+        return self.out.view(self.B, self.N, self.cfg.in_channels)
+
+    def step_cache_report(self) -> Optional[Dict]:
+        """What the step cache decided for the forwards of this conditioning since its last step 0: steps (forwards seen), indices, computed
+        (indices whose blocks ran), rel (per forward, None at step 0), acc (after each forward), thresh, coefficients. None: the cache is off."""
+        return None if self.step_cache is None else self.step_cache.report()
 
     def _cond_cache_ok(self) -> bool:
         """The condition stream is step-invariant and this kernel set can keep its keys / values per layer: condition queries
@@ -1209,6 +1346,7 @@ class DiTEngine:
         self.graphs = {}
         self.cond_mask = None                                      # (a conditioning's mask does not outlive it; block-level calls bring their own)
         self.cond_cache = self.cond_cached = False                # block-level use: every call computes all three streams
+        self.step_cache = None
         self._select_mode(model_config, c_factor, gemm_fp8=False)
         self.attn_bias = self._attn_bias()
         self._setup_nomax()

@@ -16,6 +16,8 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       brain signals act on the POSITIVE branch only. The negative embeddings are used as given -- never fused with, gated by or replaced
       by brain embeddings: under brain_replace both branches would otherwise carry the same embedding and guidance would do nothing. Both
       branches run as one forward at batch 2B per step, [positive; negative], and lx_euler_step_cfg steps both halves.
+  Q8  step caching (model_config["step_cache_thresh"]; TeaCache, diffusers has none built in): opt-in, the loop below is unchanged -- the
+      engine decides per forward whether the blocks run (step_cache.py) and the output carries its report as `lx_step_cache`.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ import yaml
 from .condition import Condition
 from .pipeline import FluxPipelineOutput, calculate_shift, retrieve_timesteps
 from .pipeline_tools import encode_images
+from .step_cache import step_cache_config
 from .transformer import tranformer_forward
 
 
@@ -263,6 +266,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     negative_prompt, negative_prompt_2, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale = prepare_cfg_params(**params)
     do_true_cfg = _true_cfg(negative_prompt, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale, prompt, prompt_embeds,
                             pooled_prompt_embeds)
+    step_cache_config(model_config)          # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
             prompt_embeds.shape[0] if prompt_embeds is not None else None
@@ -411,9 +415,10 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     policy = str((model_config or {}).get("f16_overflow", "raise"))
     if policy not in F16_OVERFLOW_POLICIES:
         raise ValueError(f'model_config["f16_overflow"] = {policy!r}: one of {F16_OVERFLOW_POLICIES}')
-    start_latents, operands_used = latents, None
+    start_latents, operands_used, step_cache_report = latents, None, None
 
     def denoise(latents, prompt_embeds, model_config):
+        nonlocal step_cache_report
         with adapter_weight_tiles(engine, 2 if do_true_cfg else 1), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
@@ -445,6 +450,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                     prompt_embeds = callback_outputs.pop("prompt_embeds", prompt_embeds)
                 if i == len(timesteps) - 1 or ((i + 1) > num_warmup_steps and (i + 1) % self.scheduler.order == 0):
                     progress_bar.update()
+        # what the step cache decided for this trajectory (None when off): read here, the conditioning it belongs to ends with the image
+        step_cache_report = engine.step_cache_report() if hasattr(engine, "step_cache_report") else None
         return latents[:n_images] if do_true_cfg else latents
 
     latents = denoise(start_latents, prompt_embeds, model_config)
@@ -498,4 +505,4 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             pipeline.transformer.engine.check_status(sync=False)
     if not return_dict:
         return (image,)
-    return FluxPipelineOutput(images=image, lx_operands=operands_used)
+    return FluxPipelineOutput(images=image, lx_operands=operands_used, lx_step_cache=step_cache_report)

@@ -15,6 +15,7 @@ import torch
 
 from .block import LxBlock
 from .engine import DiTEngine, mask_argument
+from .step_cache import normalise_model_config, step_cache_config
 from .weights import FluxConfig, PackedWeights, pack_state_dict, synthetic_weights
 
 
@@ -120,7 +121,10 @@ def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.
     over the concatenated [text | image | condition] sequence of length S, bool (True = attend) or additive float, broadcastable as
     [1|B, 1|H, 1|S, S] (rank 2..4), on the device -- applied in all attention launches of the forward. Per image: B is the batch of
     hidden_states. Used under the reference's rules only (union_cond_attn, no independent_condition, no c_factor: block.py:106-128);
-    otherwise the reference's own mask replaces it. precise and attn_fp8 modes raise NotImplementedError."""
+    otherwise the reference's own mask replaces it. precise and attn_fp8 modes raise NotImplementedError.
+    model_config["step_cache_thresh"] (step_cache.py; with "step_cache_coefficients"): the forwards of this conditioning skip their blocks
+    where the rule allows it. Needs lx_schedule=(i, timesteps) with every call; without it, or with a bad value, ValueError before anything
+    is conditioned. transformer.engine.step_cache_report() tells what was decided."""
     (hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
      joint_attention_kwargs, controlnet_block_samples, controlnet_single_block_samples, return_dict) = prepare_params(**params)
     try:
@@ -141,7 +145,13 @@ def tranformer_forward(transformer: LxFluxTransformer, condition_latents: torch.
         raise ValueError("guidance_embeds=True transformer called without guidance")
     if not eng.cfg.guidance_embeds:
         guidance = None
-    mc = dict(model_config or {})
+    mc = normalise_model_config(dict(model_config or {}))          # (a YAML list of step-cache coefficients becomes a tuple: the keys hash it)
+    try:
+        if step_cache_config(mc) is not None and params.get("lx_schedule") is None:
+            raise ValueError("model_config step_cache_thresh needs the schedule: pass lx_schedule=(i, timesteps) with every call")
+    except ValueError:
+        transformer.invalidate_conditioning()              # as the mask refusals: a refused call leaves no conditioning behind
+        raise
     key = (_tkey(encoder_hidden_states), _tkey(pooled_projections), _tkey(guidance), _tkey(txt_ids), _tkey(img_ids),
            _tkey(condition_latents), _tkey(condition_ids), float(c_t), tuple(sorted(mc.items())), transformer.c_factor,
            hidden_states.shape[0], getattr(eng.w, "weights_version", 0), getattr(eng.w, "lora_version", 0),      # (a weight broadcast or a new

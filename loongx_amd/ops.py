@@ -328,6 +328,18 @@ def ln_modulate(X, shift, scale, Y, rows_per_batch, eps=1e-6, mod_ld=None, f16_o
                              rows_per_batch, eps, _stream()), "lx_ln_modulate")
 
 
+def ln_modulate_delta(X, shift, scale, P, rows_per_batch, row_sums, sums, eps=1e-6, mod_ld=None) -> None:
+    """The step-cache probe (lx_ln_modulate_delta): m = LN(X) * (1 + scale) + shift in fp32, row_sums[row] = (sum |m - P|, sum |P|) against
+    P as found, then P = m; sums (float64 [2]) = the row pairs added in row order. X, P fp32 [M, D] (row strides free), row_sums fp32
+    [M, 2] contiguous."""
+    _req(X, torch.float32, "X"); _req(shift, torch.float32, "shift"); _req(scale, torch.float32, "scale"); _req(P, torch.float32, "P")
+    _req(row_sums, torch.float32, "row_sums"); _req(sums, torch.float64, "sums")
+    assert P.shape == X.shape and row_sums.is_contiguous() and row_sums.numel() >= 2 * X.shape[0] and sums.is_contiguous() and sums.numel() >= 2
+    check(lib.lx_ln_modulate_delta(X.data_ptr(), X.stride(0), shift.data_ptr(), scale.data_ptr(),
+                                   shift.stride(0) if mod_ld is None else mod_ld, P.data_ptr(), P.stride(0), X.shape[0], X.shape[1],
+                                   rows_per_batch, eps, row_sums.data_ptr(), sums.data_ptr(), _stream()), "lx_ln_modulate_delta")
+
+
 def qkv_prep(QKV, q_col, k_col, v_col, row0, n_rows, rows_per_batch, H, wq, wk, cos, sin, VT, vt_pos0, eps=1e-6) -> None:
     _req(QKV, torch.bfloat16, "QKV")
     check(lib.lx_qkv_prep(QKV.data_ptr(), QKV.stride(0), q_col, k_col, v_col, row0, n_rows, rows_per_batch, H, _p(wq), _p(wk), eps,
