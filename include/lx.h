@@ -567,6 +567,28 @@ int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float dsigma, co
  * x[0, 2n); a scale that is not finite. */
 int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z, const float* m,
                       float sigma_next, size_t n, void* stream);
+/* One step under guidance along the brain signal nested inside true classifier-free guidance (generate's brain_guidance_scale with
+ * true_cfg_scale), three branches in one batch. x is fp32 [3n]: the latents, then two copies. v is [3n], bf16 or fp32, laid out
+ * [full; text; negative]: elements [0, n) are the velocity of the branch with the brain-conditioned embeddings, [n, 2n) of the branch with
+ * the text embeddings alone, [2n, 3n) of the negative branch. x0, z, m are all NULL (no blend) or all fp32 [n] (lx_euler_step_blend's
+ * blend, computed once and stored to all three parts). Per element i < n, in this order:
+ *   db = vF - vT                       -- rounded on its own
+ *   gb = fmaf(scale_brain, db, vT)     -- the text velocity pushed along the brain signal
+ *   dt = gb - vN                       -- rounded on its own
+ *   g  = fmaf(scale_text, dt, vN)      -- lx_euler_step_cfg's g on (gb, vN)
+ *   e  = fmaf(dsigma, g, x[i])         -- lx_euler_step on g
+ *   r  = e                             -- without a blend
+ *   r  = fmaf(m, e, (1 - m)*fmaf(sigma_next, z, (1 - sigma_next)*x0))   -- lx_euler_step_blend's three operations, bit-identical given e
+ *   x[i] = x[n + i] = x[2n + i] = r    -- only x[i] is read: all parts leave equal whatever x[n + i] and x[2n + i] held
+ * So vF == vT bit for bit gives gb == vT exactly, whatever scale_brain is (finite values; up to the sign of a zero), and the launch then
+ * equals lx_euler_step_cfg on [T; N] with scale_text bit for bit; if vT == vN as well it is lx_euler_step's, or lx_euler_step_blend's.
+ * With m == 0 the kept elements follow the source as in lx_euler_step_blend's contract (sigma_next == 0: exactly x0). All parts are
+ * accessed 16 bytes at a time (8 for bf16 v) only when every part of x and of v is aligned -- n % 4 == 0 and aligned bases; every other
+ * call goes element by element, same bits. Plain vector stores, no atomics.
+ * LX_ERR_INVALID before any launch: NULL x or v; n == 0 (or 3n floats past the address space); a partly NULL (x0, z, m); x0, z or m
+ * overlapping x[0, 3n); fp32 v overlapping x[0, 3n); a scale that is not finite. */
+int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
+                       const float* z, const float* m, float sigma_next, size_t n, void* stream);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

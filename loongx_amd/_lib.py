@@ -145,6 +145,7 @@ _SIGS = {
     "lx_scale_noise": (C.c_int, [_P, _P, _P, _F, _Z, _P]),
     "lx_euler_step_blend": (C.c_int, [_P, _P, _I, _F, _P, _P, _P, _F, _Z, _P]),
     "lx_euler_step_cfg": (C.c_int, [_P, _P, _I, _F, _F, _P, _P, _P, _F, _Z, _P]),
+    "lx_euler_step_cfg3": (C.c_int, [_P, _P, _I, _F, _F, _F, _P, _P, _P, _F, _Z, _P]),
     "lx_convert": (C.c_int, [_P, _I, _P, _I, _Z, _P]),
     "lx_s4_scan": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "lx_s4_conv": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),

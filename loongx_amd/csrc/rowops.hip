@@ -745,7 +745,52 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, c
   }
 }
 
-__global__ void convert_kernel(void* __restrict__ dst, int dst_bf16, const void* __restrict__ src, int src_bf16, size_t n) {
+// ---- the twice-guided step (lx_euler_step_cfg3) ---------------------------------------------------------------------------------------
+// x and v hold three parts of n elements, [full; text; negative]. gb = vt + scale_brain (vf - vt), g = vn + scale_text (gb - vn), the Euler
+// step on g from the first part of x, the inpaint blend where BLEND, and the result stored to all three parts: the order of include/lx.h,
+// one rounding per named operation. VEC = 4 as in euler_cfg_kernel: the host takes it only when all three parts of x and of v are aligned
+// (n % 4 == 0), so that path has no element tail. vf == vt bit for bit makes gb == vt exactly (0 * scale_brain + vt; the scale is finite),
+// and what is left is euler_cfg1 on (vt, vn).
+__device__ __forceinline__ float euler_cfg3_1(float x, float vf, float vt, float vn, float ds, float scale_brain, float scale_text) {
+  const float gb = fmaf(scale_brain, __fsub_rn(vf, vt), vt);
+  return fmaf(ds, fmaf(scale_text, __fsub_rn(gb, vn), vn), x);
+}
+__device__ __forceinline__ float load_v1(const void* __restrict__ v, int v_bf16, size_t i) {
+  return v_bf16 ? bf16_to_f32(((const uint16_t*)v)[i]) : ((const float*)v)[i];
+}
+
+template <int VEC, bool BLEND>
+__global__ __launch_bounds__(256) void euler_cfg3_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds,
+                                                         float scale_brain, float scale_text, const float* __restrict__ x0,
+                                                         const float* __restrict__ z, const float* __restrict__ m, float sigma_next,
+                                                         float one_minus_sigma, size_t n) {
+  const size_t items = n / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4) {
+      const f32x4 vf = load_v4(v, v_bf16, i), vt = load_v4(v, v_bf16, n + i), vn = load_v4(v, v_bf16, 2 * n + i);
+      f32x4 o = *(const f32x4*)(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = euler_cfg3_1(o[j], vf[j], vt[j], vn[j], ds, scale_brain, scale_text);
+      if (BLEND) {
+        const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], a[j], b[j], mm[j], sigma_next, one_minus_sigma);
+      }
+      *(f32x4*)(x + i) = o;
+      *(f32x4*)(x + n + i) = o;
+      *(f32x4*)(x + 2 * n + i) = o;
+    } else {
+      float o = euler_cfg3_1(x[i], load_v1(v, v_bf16, i), load_v1(v, v_bf16, n + i), load_v1(v, v_bf16, 2 * n + i), ds, scale_brain, scale_text);
+      if (BLEND) o = blend1(o, x0[i], z[i], m[i], sigma_next, one_minus_sigma);
+      x[i] = o;
+      x[n + i] = o;
+      x[2 * n + i] = o;
+    }
+  }
+}
+
+__global__ void convert_kernel(void* __restrict__ dst, int dst_bf16,const void* __restrict__ src, int src_bf16, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float v = src_bf16 ? bf16_to_f32(((const uint16_t*)src)[i]) : ((const float*)src)[i];
@@ -1220,6 +1265,43 @@ extern "C" int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float d
   if (vec) launch_euler_cfg<4>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
   else launch_euler_cfg<1>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
   LX_LAUNCH_CHECK("lx_euler_step_cfg");
+  return LX_OK;
+}
+
+template <int VEC>
+static void launch_euler_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
+                              const float* z, const float* m, float sigma_next, size_t n, hipStream_t stream) {
+  const size_t items = n / VEC;
+  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  const float oms = 1.0f - sigma_next;
+  if (m) hipLaunchKernelGGL((euler_cfg3_kernel<VEC, true>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, oms, n);
+  else hipLaunchKernelGGL((euler_cfg3_kernel<VEC, false>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, oms, n);
+}
+
+static bool f32_is_finite(float f) {
+  uint32_t bits;
+  __builtin_memcpy(&bits, &f, sizeof bits);
+  return (bits & 0x7f800000u) != 0x7f800000u;
+}
+
+extern "C" int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
+                                  const float* z, const float* m, float sigma_next, size_t n, void* stream) {
+  LX_CHECK_ARG(x && v, "lx_euler_step_cfg3: NULL x or v");
+  LX_CHECK_ARG(n > 0, "lx_euler_step_cfg3: n == 0");
+  LX_CHECK_ARG(n <= SIZE_MAX / (3 * sizeof(float)), "lx_euler_step_cfg3: 3n elements do not fit an address");
+  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_cfg3: x0, z and m go together (all NULL: no blend)");
+  LX_CHECK_ARG(f32_is_finite(scale_brain) && f32_is_finite(scale_text), "lx_euler_step_cfg3: scale_brain or scale_text is not finite");
+  const size_t xbytes = 3 * n * sizeof(float), pbytes = n * sizeof(float);
+  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, pbytes) && !byte_ranges_overlap(x, xbytes, z, pbytes) &&
+                      !byte_ranges_overlap(x, xbytes, m, pbytes)),
+               "lx_euler_step_cfg3: x0, z and m may not alias x[0, 3n) (it is updated in place)");
+  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_cfg3: v may not alias x[0, 3n)");
+  // all three parts of every operand: x + n, x + 2n, v + n and v + 2n are aligned only where n % 4 == 0
+  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
+  const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 && ((uintptr_t)v & v_align) == 0;
+  if (vec) launch_euler_cfg3<4>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
+  else launch_euler_cfg3<1>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
+  LX_LAUNCH_CHECK("lx_euler_step_cfg3");
   return LX_OK;
 }
 

@@ -18,6 +18,12 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       branches run as one forward at batch 2B per step, [positive; negative], and lx_euler_step_cfg steps both halves.
   Q8  step caching (model_config["step_cache_thresh"]; TeaCache, diffusers has none built in): opt-in, the loop below is unchanged -- the
       engine decides per forward whether the blocks run (step_cache.py) and the output carries its report as `lx_step_cache`.
+  Q9  guidance along the brain signal (brain_guidance_scale > 1; InstructPix2Pix's second scale with the brain embedding as the
+      instruction channel, neither the reference nor diffusers has it): a text-only branch T carries the embeddings as encode_prompt left
+      them, the full branch F what the brain section made of them, and the velocity is nested so that each scale alone is what exists:
+      v_b = v_T + s_b (v_F - v_T), then g = v_N + s_t (v_b - v_N) under true CFG. On only where the signals changed an embedding (decided by
+      tensor identity); otherwise one RuntimeWarning and the call without it. One forward per step at batch k·B·n, [F; T], [F; N] or
+      [F; T; N]; lx_euler_step_cfg steps two branches, lx_euler_step_cfg3 three.
 """
 from __future__ import annotations
 
@@ -62,9 +68,9 @@ def vae_f16_overflow(vae, policy: Optional[str]):
 
 @contextlib.contextmanager
 def adapter_weight_tiles(engine, tiles: int):
-    """A guided call runs [positive; negative] halves of the same images in one batch: inside the block a per-image adapter weight table
-    (set_adapters(names, [w per image])) of length B applies to each of the `tiles` parts of a conditioning with tiles x B images. Told to
-    the engine for the steps of one call, the way c_factor is; tiles == 1 or no engine: a no-op."""
+    """A guided call runs the branches of the same images ([positive; negative], [full; text; negative]) in one batch: inside the block a
+    per-image adapter weight table (set_adapters(names, [w per image])) of length B applies to each of the `tiles` parts of a conditioning
+    with tiles x B images. Told to the engine for the steps of one call, the way c_factor is; tiles == 1 or no engine: a no-op."""
     if engine is None or tiles == 1:
         yield
         return
@@ -95,10 +101,10 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0,
                    negative_prompt: Union[str, List[str]] = None, negative_prompt_2=None,
                    negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
-                   true_cfg_scale: float = 1.0, **kwargs):
-    """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline and the true-CFG
-    keywords of its FluxPipeline are named here (so they are not among the swallowed **kwargs) and returned by prepare_inpaint_params /
-    prepare_cfg_params."""
+                   true_cfg_scale: float = 1.0, brain_guidance_scale: float = 1.0, **kwargs):
+    """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline, the true-CFG
+    keywords of its FluxPipeline and this project's brain_guidance_scale are named here (so they are not among the swallowed **kwargs) and
+    returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
@@ -112,6 +118,22 @@ def prepare_inpaint_params(image=None, image_latents: Optional[torch.Tensor] = N
 def prepare_cfg_params(negative_prompt=None, negative_prompt_2=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                        true_cfg_scale: float = 1.0, **kwargs):
     return negative_prompt, negative_prompt_2, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale
+
+
+def prepare_brain_cfg_params(brain_guidance_scale: float = 1.0, **kwargs):
+    return brain_guidance_scale
+
+
+def _brain_cfg(brain_guidance_scale) -> bool:
+    """generate()'s brain_guidance_scale -> whether guidance along the brain signal is asked for (s_b > 1; whether it is ON is known only
+    after the brain section: the signals have to change an embedding). A refusal is a ValueError on the host, before anything of the
+    pipeline is touched; a scale in [0, 1) is one RuntimeWarning and the plain call, as true_cfg_scale <= 1 is."""
+    s = brain_guidance_scale
+    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s) or float(s) < 0:
+        raise ValueError(f"brain_guidance_scale must be a finite number >= 0, got {s!r}")
+    if float(s) < 1:
+        warnings.warn(f"brain_guidance_scale={s} (< 1): guidance is off, running the plain call", RuntimeWarning, stacklevel=3)
+    return float(s) > 1
 
 
 def _fits_positive(name, neg, pos):
@@ -266,6 +288,9 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     negative_prompt, negative_prompt_2, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale = prepare_cfg_params(**params)
     do_true_cfg = _true_cfg(negative_prompt, negative_prompt_embeds, negative_pooled_prompt_embeds, true_cfg_scale, prompt, prompt_embeds,
                             pooled_prompt_embeds)
+    # ---- guidance along the brain signal (Q9): the scale is checked here; whether it is on is known after the brain section
+    brain_guidance_scale = prepare_brain_cfg_params(**params)
+    want_brain_cfg = _brain_cfg(brain_guidance_scale)
     step_cache_config(model_config)          # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
@@ -302,10 +327,12 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
             pooled_prompt_embeds=negative_pooled_prompt_embeds, device=device, num_images_per_prompt=num_images_per_prompt,
             max_sequence_length=max_sequence_length, lora_scale=lora_scale)
+    text_prompt_embeds, text_pooled_prompt_embeds = prompt_embeds, pooled_prompt_embeds      # (branch T of brain guidance: the text alone)
 
     # ---- CS3 encoders + DGF fusion: once per image, outside the loop (generate.py:168-258) ----------
-    if use_brain_condition and any(c is not None for c in (additional_condition1, additional_condition2,
-                                                           additional_condition3, additional_condition4)):
+    brain_ran = use_brain_condition and any(c is not None for c in (additional_condition1, additional_condition2,
+                                                                    additional_condition3, additional_condition4))
+    if brain_ran:
         f32 = torch.float32
         eeg = _signal(additional_condition1, device, f32, model.eeg_fixed_length, model)
         fnirs = _signal(additional_condition2, device, f32, model.fnirs_fixed_length, model)
@@ -336,8 +363,28 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         elif prompt_embeds_brain is not None and pooled_prompt_embeds_brain is not None:
             prompt_embeds, pooled_prompt_embeds = prompt_embeds_brain, pooled_prompt_embeds_brain
 
-    # ---- true CFG: the negative branch is the second half of ONE batch of 2·B·n, built here once per image. Its embeddings are used as
-    # given -- the brain signals above act on the positive half only (under brain_replace both halves would otherwise carry the same
+    # ---- guidance along the brain signal (Q9): on only where the signals changed an embedding (by identity: the brain section rebinds
+    # what it replaces or fuses). Branch T, the text alone, then sits between the full branch and the negative one: [F; T], [F; N] or
+    # [F; T; N] in ONE batch of k·B·n. The signals act on branch F only.
+    do_brain_cfg = bool(want_brain_cfg and brain_ran and (prompt_embeds is not text_prompt_embeds or
+                                                          pooled_prompt_embeds is not text_pooled_prompt_embeds))
+    if want_brain_cfg and not do_brain_cfg:
+        warnings.warn(f"brain_guidance_scale={brain_guidance_scale} but the brain signals change no embedding (no signals, "
+                      "use_brain_condition=False, or brain_replace='both' with one side missing): nothing to guide along, running without "
+                      "brain guidance", RuntimeWarning, stacklevel=2)
+    if do_brain_cfg:
+        for name, full, text in (("prompt_embeds", prompt_embeds, text_prompt_embeds),
+                                 ("pooled_prompt_embeds", pooled_prompt_embeds, text_pooled_prompt_embeds)):
+            if full.dim() != text.dim() or full.shape[1:] != text.shape[1:] or \
+                    (full.shape[0] != text.shape[0] and 1 not in (full.shape[0], text.shape[0])):
+                raise ValueError(f"brain_guidance_scale: the brain-conditioned `{name}` {tuple(full.shape)} and the text-only ones "
+                                 f"{tuple(text.shape)} must have one shape (or a batch of 1) to run as branches of one batch")
+        rows = max(prompt_embeds.shape[0], text_prompt_embeds.shape[0], pooled_prompt_embeds.shape[0], text_pooled_prompt_embeds.shape[0])
+        prompt_embeds, text_prompt_embeds = (t if t.shape[0] == rows else t.expand(rows, -1, -1) for t in (prompt_embeds, text_prompt_embeds))
+        pooled_prompt_embeds, text_pooled_prompt_embeds = (t if t.shape[0] == rows else t.expand(rows, -1)
+                                                           for t in (pooled_prompt_embeds, text_pooled_prompt_embeds))
+    # ---- true CFG: the negative branch is the last part of that ONE batch, built here once per image. Its embeddings are used as
+    # given -- the brain signals above act on the full branch only (under brain_replace both branches would otherwise carry the same
     # embedding and guidance would do nothing)
     if do_true_cfg:
         if negative_prompt_embeds.shape[0] != prompt_embeds.shape[0]:           # (one negative prompt for the whole batch)
@@ -345,8 +392,12 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             negative_pooled_prompt_embeds = negative_pooled_prompt_embeds[:1].expand(pooled_prompt_embeds.shape[0], -1)
         _fits_positive("negative_prompt_embeds", negative_prompt_embeds, prompt_embeds)
         _fits_positive("negative_pooled_prompt_embeds", negative_pooled_prompt_embeds, pooled_prompt_embeds)
-        prompt_embeds = torch.cat([prompt_embeds, negative_prompt_embeds.to(prompt_embeds.dtype)])
-        pooled_prompt_embeds = torch.cat([pooled_prompt_embeds, negative_pooled_prompt_embeds.to(pooled_prompt_embeds.dtype)])
+    n_branches = 1 + do_brain_cfg + do_true_cfg
+    if n_branches > 1:
+        others = ([(text_prompt_embeds, text_pooled_prompt_embeds)] if do_brain_cfg else []) + \
+                 ([(negative_prompt_embeds, negative_pooled_prompt_embeds)] if do_true_cfg else [])
+        prompt_embeds = torch.cat([prompt_embeds] + [e.to(prompt_embeds.dtype) for e, _ in others])
+        pooled_prompt_embeds = torch.cat([pooled_prompt_embeds] + [p.to(pooled_prompt_embeds.dtype) for _, p in others])
 
     # ---- latents + condition tokens ----------------------------------------------------------------------
     num_channels_latents = self.transformer.config.in_channels // 4
@@ -385,16 +436,20 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
     step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
     n_images = latents.shape[0]
-    if do_true_cfg:
-        # the start latents twice ([positive; negative]; the draw above stays [B·n, ...], so the generator is consumed as in the plain call),
-        # the condition tokens and a [B·n] attention mask for both halves; image_latents / noise / mask stay [B·n, ...] (lx_euler_step_cfg)
-        step_kwargs["true_cfg_scale"] = float(true_cfg_scale)
-        latents = torch.cat([latents, latents])
+    if n_branches > 1:
+        # the start latents once per branch ([full; text; negative] where all are on; the draw above stays [B·n, ...], so the generator is
+        # consumed as in the plain call), the condition tokens and a [B·n] attention mask for every part; image_latents / noise / mask stay
+        # [B·n, ...] (lx_euler_step_cfg, lx_euler_step_cfg3)
+        if do_true_cfg:
+            step_kwargs["true_cfg_scale"] = float(true_cfg_scale)
+        if do_brain_cfg:
+            step_kwargs["brain_guidance_scale"] = float(brain_guidance_scale)
+        latents = torch.cat([latents] * n_branches)
         if use_condition:
-            condition_latents = condition_latents.repeat(2 * n_images // condition_latents.shape[0], 1, 1)
+            condition_latents = condition_latents.repeat(n_branches * n_images // condition_latents.shape[0], 1, 1)
         user_mask = (self.joint_attention_kwargs or {}).get("attention_mask")
         if isinstance(user_mask, torch.Tensor) and user_mask.dim() == 4 and user_mask.shape[0] == n_images and n_images > 1:
-            self._joint_attention_kwargs = dict(self.joint_attention_kwargs, attention_mask=torch.cat([user_mask, user_mask]))
+            self._joint_attention_kwargs = dict(self.joint_attention_kwargs, attention_mask=torch.cat([user_mask] * n_branches))
     self._num_timesteps = len(timesteps)
     guidance = None
     if self.transformer.config.guidance_embeds:
@@ -419,7 +474,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
 
     def denoise(latents, prompt_embeds, model_config):
         nonlocal step_cache_report
-        with adapter_weight_tiles(engine, 2 if do_true_cfg else 1), self.progress_bar(total=num_inference_steps) as progress_bar:
+        with adapter_weight_tiles(engine, n_branches), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
                     continue
@@ -435,16 +490,16 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                 latents = self.scheduler.step(noise_pred, t, latents, return_dict=False, **step_kwargs)[0]
                 if callback_on_step_end is not None:
                     scope = dict(locals())                                  # (a comprehension has its own locals() before 3.12)
-                    if do_true_cfg:
-                        scope["latents"] = shown = latents[:n_images]       # (the halves are equal: a callback sees the images' own)
+                    if n_branches > 1:
+                        scope["latents"] = shown = latents[:n_images]       # (the parts are equal: a callback sees the images' own)
                     callback_kwargs = {}
                     for k in callback_on_step_end_tensor_inputs:
                         callback_kwargs[k] = scope[k]
                     callback_outputs = callback_on_step_end(self, i, t, callback_kwargs)
-                    if do_true_cfg:
+                    if n_branches > 1:
                         given = callback_outputs.pop("latents", shown)
-                        if given is not shown:                              # (its latents go to both halves: a copy, made only when it returns some)
-                            latents = torch.cat([given, given])
+                        if given is not shown:                              # (its latents go to every part: a copy, made only when it returns some)
+                            latents = torch.cat([given] * n_branches)
                     else:
                         latents = callback_outputs.pop("latents", latents)
                     prompt_embeds = callback_outputs.pop("prompt_embeds", prompt_embeds)
@@ -452,7 +507,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                     progress_bar.update()
         # what the step cache decided for this trajectory (None when off): read here, the conditioning it belongs to ends with the image
         step_cache_report = engine.step_cache_report() if hasattr(engine, "step_cache_report") else None
-        return latents[:n_images] if do_true_cfg else latents
+        return latents[:n_images] if n_branches > 1 else latents
 
     latents = denoise(start_latents, prompt_embeds, model_config)
     if engine is not None and engine.f16:

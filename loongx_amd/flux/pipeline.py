@@ -88,19 +88,37 @@ class FlowMatchEulerDiscreteScheduler:
         sigma = float(self._sig_host[self._sigma_index(sigma_index_or_timestep)])
         return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None):
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None,
+             brain_guidance_scale=None):
         """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
         inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
         level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend).
         true_cfg_scale = s: sample and model_output have a leading dimension 2B, [positive; negative]; both halves of prev are the step of
         the positive half along neg + s * (pos - neg) (diffusers' FluxPipeline true CFG), in one launch (lx_euler_step_cfg). inpaint then has
-        the shape of one half."""
+        the shape of one half.
+        brain_guidance_scale = s_b (> 1; generate's guidance along the brain signal): alone, the leading dimension is 2B, [full; text], and
+        the step is the same launch along text + s_b * (full - text). With true_cfg_scale = s_t as well the leading dimension is 3B,
+        [full; text; negative], and all three parts of prev are the step of the first along neg + s_t * (text + s_b * (full - text) - neg),
+        in one launch (lx_euler_step_cfg3). inpaint has the shape of one part."""
         i = self._step_index
         ds = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i]))
         x = sample.to(torch.float32).clone() if (sample.dtype != torch.float32 or not sample.is_contiguous()) else sample.clone()
         v = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
         half = tuple(x.shape)
-        if true_cfg_scale is not None:
+        if brain_guidance_scale is not None and not float(brain_guidance_scale) > 1:
+            raise ValueError(f"step(brain_guidance_scale={brain_guidance_scale}): must be > 1; without brain guidance pass None and the "
+                             "batch without its text-only part")
+        if brain_guidance_scale is not None and true_cfg_scale is not None:
+            if x.dim() < 1 or x.shape[0] % 3 or x.shape[0] == 0 or v.shape != x.shape:
+                raise ValueError(f"step(true_cfg_scale=..., brain_guidance_scale=...): sample {tuple(x.shape)} and model_output "
+                                 f"{tuple(v.shape)} must have one shape with a leading dimension that is a multiple of 3, [full; text; negative]")
+            half = (x.shape[0] // 3,) + tuple(x.shape[1:])
+        elif brain_guidance_scale is not None:
+            if x.dim() < 1 or x.shape[0] % 2 or x.shape[0] == 0 or v.shape != x.shape:
+                raise ValueError(f"step(brain_guidance_scale=...): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one "
+                                 "shape with an even leading dimension, [full; text]")
+            half = (x.shape[0] // 2,) + tuple(x.shape[1:])
+        elif true_cfg_scale is not None:
             if x.dim() < 1 or x.shape[0] % 2 or x.shape[0] == 0 or v.shape != x.shape:
                 raise ValueError(f"step(true_cfg_scale=...): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one shape "
                                  "with an even leading dimension, [positive; negative]")
@@ -110,7 +128,11 @@ class FlowMatchEulerDiscreteScheduler:
             if not (tuple(x0.shape) == tuple(z.shape) == tuple(m.shape) == half):
                 raise ValueError(f"step(inpaint=...): image_latents {tuple(x0.shape)}, noise {tuple(z.shape)} and mask {tuple(m.shape)} must "
                                  f"have the latents' shape {half}")
-        if true_cfg_scale is not None:
+        if brain_guidance_scale is not None and true_cfg_scale is not None:
+            ops.euler_step_cfg3(x, v.contiguous(), ds, float(brain_guidance_scale), float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
+        elif brain_guidance_scale is not None:
+            ops.euler_step_cfg(x, v.contiguous(), ds, float(brain_guidance_scale), inpaint, float(self._sig_host[i + 1]))
+        elif true_cfg_scale is not None:
             ops.euler_step_cfg(x, v.contiguous(), ds, float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
         elif inpaint is None:
             ops.euler_step(x, v.contiguous(), ds)

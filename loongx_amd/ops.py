@@ -650,6 +650,28 @@ def euler_step_cfg(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale: float
                                 float(sigma_next), n, _stream()), "lx_euler_step_cfg")
 
 
+def euler_step_cfg3(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale_brain: float, scale_text: float, inpaint=None,
+                    sigma_next: float = 0.0) -> None:
+    """The step under brain guidance nested in true classifier-free guidance, in place (lx_euler_step_cfg3): x fp32 and v fp32 or bf16 hold
+    [full; text; negative] parts of n elements each; all three parts of x become x[:n] + dsigma * (vN + scale_text * (gb - vN)) with
+    gb = vT + scale_brain * (vF - vT). inpaint = (x0, z, m), fp32 with n elements each: blended with the source at sigma_next as
+    euler_step_blend does, once, for all parts. All contiguous."""
+    _req(x, torch.float32, "x")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    n = x.numel() // 3
+    assert x.numel() == 3 * n and v.numel() == 3 * n, "euler_step_cfg3: x and v hold three parts of one element count"
+    x0 = z = m = None
+    if inpaint is not None:
+        x0, z, m = inpaint
+        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
+        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_cfg3: x0, z and m have the element count of one part"
+    assert all(t.is_contiguous() for t in (x, v, x0, z, m) if t is not None), "euler_step_cfg3: contiguous operands"
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    check(lib.lx_euler_step_cfg3(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), float(scale_brain), float(scale_text),
+                                 ptr(x0), ptr(z), ptr(m), float(sigma_next), n, _stream()), "lx_euler_step_cfg3")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
