@@ -589,6 +589,51 @@ int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float dsigma, floa
  * overlapping x[0, 3n); fp32 v overlapping x[0, 3n); a scale that is not finite. */
 int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
                        const float* z, const float* m, float sigma_next, size_t n, void* stream);
+/* One guided step under adaptive projected guidance (APG; generate's apg_eta / apg_norm_threshold / apg_momentum): the total guidance
+ * update of the call is clamped in norm, given a momentum, split along the denoised prediction of the first branch, and its parallel part
+ * is down-weighted. n_parts = 2: x and v are [2n] laid out as lx_euler_step_cfg's, scale_a is its scale, scale_b is ignored. n_parts = 3:
+ * [3n] laid out as lx_euler_step_cfg3's, (scale_a, scale_b) = (scale_brain, scale_text). n = n_images * elems: every part holds n_images
+ * images of elems elements, and the projection and the clamp are per image. sigma is the current sigma (> 0), dsigma and sigma_next as in
+ * the sibling steps. M is fp32 [n], the momentum state in the space of the denoised prediction; sums is double [n_images][3]; workspace is
+ * lx_apg_workspace_bytes(n_images, elems) bytes, 8-byte aligned, scratch. vc is part 0 of v. Per element i of image b, in this order:
+ * Pass 1
+ *   g0  = lx_euler_step_cfg's g (n_parts 2) or lx_euler_step_cfg3's g (n_parts 3), the same operations in the same order
+ *   dv  = g0 - vc                          -- rounded on its own
+ *   D   = (-sigma) * dv                    -- one rounded product: the update in the space of the denoised prediction
+ *   Db  = momentum == 0 ? D : fmaf(momentum, M[i], D);   M[i] = Db        -- M is NOT read when momentum == 0, and always written
+ *   w   = fmaf(-sigma, vc, x[i])           -- the denoised prediction of the first branch
+ *   sums[b] = (S_dd, S_dw, S_ww) = (sum Db^2, sum Db w, sum w^2) over the image: the products formed in double from the fp32 values (exact),
+ *             added in double in a fixed order (per chunk of 4096 elements, then the chunks in order): the same bits from run to run
+ * Pass 2 (reads sums on the device; nothing is synchronised with the host)
+ *   c   = (norm_threshold > 0 && S_dd > r^2) ? r / sqrt(S_dd) : 1,  r = norm_threshold        (double)
+ *   a   = S_ww > 0 ? S_dw / S_ww : 0                                                           (double)
+ *   c32 = (float)c;   k32 = (float)((c * (1 - eta)) * a)
+ *   p   = k32 * w                          -- rounded on its own; w recomputed, the same bits
+ *   u   = fmaf(c32, Db, -p)                -- the clamped update less (1 - eta) of its part along w
+ *   g   = fmaf(-inv_sigma, u, vc)          -- inv_sigma = 1.0f / sigma, formed on the host
+ *   e   = fmaf(dsigma, g, x[i])            -- lx_euler_step on g
+ *   r   = e, or lx_euler_step_blend's three operations on e where (x0, z, m) are given, bit-identical given e
+ *   x[i] = x[n + i] (= x[2n + i]) = r      -- only part 0 of x is read
+ * So branches equal bit for bit give dv = 0, S_dd = S_dw = 0, u = 0 and g = vc (momentum 0, or M all zero): the step is lx_euler_step's, or
+ * lx_euler_step_blend's, bit for bit up to the sign of a zero. m == 0 keeps the source as in lx_euler_step_blend's contract. eta == 1,
+ * no threshold and no momentum is g = vc + (g0 - vc) to rounding, which is NOT g0 bit for bit: a caller who wants the plain guided step
+ * calls lx_euler_step_cfg / lx_euler_step_cfg3. With E the exact result given the stored M and sums, every |d_i| <= u = 2^-24:
+ *   |u - U| <= u (|c Db| + 3 |k W| + |U|),  |g - G| <= (|u - U| + u |U|) / sigma + u |G|,  |e - E| <= |dsigma| |g - G| + u |E|
+ * to first order (c32 on c Db; w, k32 and the product on k W; the fma on U; inv_sigma on U / sigma; the two fmas on G and E), with
+ * k = c (1 - eta) a, W = x - sigma vc, U = c Db - k W, G = vc - U / sigma, E = x + dsigma G.
+ * 16-byte accesses (8 for bf16 v) only when every part and every image start is aligned -- elems % 4 == 0 and aligned x, v, M, x0, z, m;
+ * every other call goes element by element, same bits, sums included. Plain vector stores, no atomics.
+ * LX_ERR_INVALID before any launch: NULL x, v, M, sums or workspace; n_parts outside {2, 3}; n_images < 1 (or > 65535) or elems == 0;
+ * sigma not finite or <= 0; a scale (scale_b only where n_parts == 3), eta, norm_threshold or momentum that is not finite; eta outside
+ * [0, 1]; norm_threshold < 0; |momentum| >= 1; a partly NULL (x0, z, m); workspace_bytes < lx_apg_workspace_bytes(n_images, elems); a
+ * workspace or sums that is not 8-byte aligned; M, sums, the workspace, x0, z or m overlapping x[0, n_parts n); fp32 v overlapping x; M
+ * overlapping v. */
+int lx_euler_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float eta,
+                      float norm_threshold, float momentum, float* M, double* sums, void* workspace, size_t workspace_bytes, const float* x0,
+                      const float* z, const float* m, float sigma_next, int n_images, size_t elems, void* stream);
+/* bytes of lx_euler_step_apg's workspace (3 doubles per chunk of 4096 elements per image); 0 for n_images < 1 or > 65535, elems == 0, or
+ * sizes that do not fit an address */
+size_t lx_apg_workspace_bytes(int n_images, size_t elems);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

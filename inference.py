@@ -114,10 +114,15 @@ def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
     return kw
 
 
-def cfg_kwargs(true_cfg_scale=None, negative_prompt=None, brain_guidance_scale=None):
+def cfg_kwargs(true_cfg_scale=None, negative_prompt=None, brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None,
+               apg_momentum=None):
     """--true_cfg_scale / --negative_prompt -> generate()'s true-CFG keywords (an addition; diffusers' FluxPipeline), --brain_guidance_scale ->
-    its guidance along the brain signal, each only when given."""
+    its guidance along the brain signal, --apg_eta / --apg_norm_threshold / --apg_momentum -> its adaptive projected guidance, each only
+    when given."""
     kw = {}
+    for name, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
+        if value is not None:
+            kw[name] = value
     if brain_guidance_scale is not None:
         kw["brain_guidance_scale"] = brain_guidance_scale
     if true_cfg_scale is not None:
@@ -151,9 +156,9 @@ def load_captions(caption_path):
 
 def process_image_batch(rank, world_size, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta,
                         target_size, seed, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                        brain_guidance_scale=None):
+                        brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None):
     """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image; true_cfg_scale /
-    negative_prompt / brain_guidance_scale: cfg_kwargs, the same for every image."""
+    negative_prompt / brain_guidance_scale / apg_*: cfg_kwargs, the same for every image."""
     from PIL import Image
     from loongx_amd.dist import shard_range
     start_idx, end_idx = shard_range(len(image_files), rank, world_size)
@@ -164,7 +169,8 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
         result_img = inference_single_image(model, condition_img, prompt, condition_type=condition_type, position_delta=position_delta,
                                             target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device),
                                             **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None),
-                                            **cfg_kwargs(true_cfg_scale, negative_prompt, brain_guidance_scale))
+                                            **cfg_kwargs(true_cfg_scale, negative_prompt, brain_guidance_scale, apg_eta, apg_norm_threshold,
+                                                         apg_momentum))
         result_img.save(os.path.join(output_dir, img_file))
         if rank == 0 and (idx - start_idx) % 10 == 0:
             print(f"Process {rank}: Completed {idx - start_idx}/{end_idx - start_idx} images")
@@ -172,7 +178,7 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
 
 def batch_inference(model, input_dir, output_dir, caption_path=None, condition_type="SEED", target_size=512, position_delta=[0, -32],
                     seed=42, brain_data_path=None, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                    brain_guidance_scale=None):
+                    brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None):
     """inference.py:255-339: all captioned images of a directory on one GPU."""
     os.makedirs(output_dir, exist_ok=True)
     brain_data = load_brain_data(brain_data_path) if brain_data_path and os.path.exists(brain_data_path) else {}
@@ -180,7 +186,8 @@ def batch_inference(model, input_dir, output_dir, caption_path=None, condition_t
     image_files = [f for f in captions if f.endswith((".png", ".jpg", ".jpeg"))]
     process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed,
                         strength=strength, mask_dir=mask_dir, true_cfg_scale=true_cfg_scale, negative_prompt=negative_prompt,
-                        brain_guidance_scale=brain_guidance_scale)
+                        brain_guidance_scale=brain_guidance_scale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
+                        apg_momentum=apg_momentum)
     print(f"Processed {len(image_files)} images. Results saved to {output_dir}")
 
 
@@ -289,7 +296,8 @@ def distributed_inference_worker(rank, world_size, args, config, model_loaded_ev
         process_image_batch(rank, world_size, model, image_files, args.input_dir, args.output_dir, captions, brain_data, args.condition_type,
                             [args.position_delta_x, args.position_delta_y], args.target_size, args.seed, strength=args.strength,
                             mask_dir=args.mask_dir, true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
-                            brain_guidance_scale=args.brain_guidance_scale)
+                            brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
         n_total, n, dt = len(image_files), len(image_files) // world_size, time.time() - t0
     if world_size > 1:
         dist.barrier()
@@ -334,6 +342,14 @@ def main(argv=None):
     p.add_argument("--brain_guidance_scale", type=float, default=None,
                    help="guidance along the brain signal: extrapolate from the text-only prediction towards the brain-conditioned one by this "
                         "factor, > 1 (generate(brain_guidance_scale=)); each step then runs one forward with one more branch in its batch")
+    p.add_argument("--apg_eta", type=float, default=None,
+                   help="adaptive projected guidance, with --true_cfg_scale and/or --brain_guidance_scale: the weight in [0, 1] of the guidance "
+                        "update's part along the prediction (generate(apg_eta=); 1 keeps it, 0 removes it: less saturation at high scales)")
+    p.add_argument("--apg_norm_threshold", type=float, default=None,
+                   help="adaptive projected guidance: clamp the per-image norm of the guidance update to this, > 0 (generate(apg_norm_threshold=))")
+    p.add_argument("--apg_momentum", type=float, default=None,
+                   help="adaptive projected guidance: momentum of the guidance update over the steps, in (-1, 1), usually negative "
+                        "(generate(apg_momentum=))")
     p.add_argument("--step_cache_thresh", type=float, default=None,
                    help="step caching (TeaCache; model_config['step_cache_thresh']): skip the blocks of denoise steps whose accumulated input "
                         "distance stays under this threshold, > 0 (about 0.25 .. 0.8; larger skips more); prints the computed steps per image")
@@ -344,6 +360,8 @@ def main(argv=None):
         p.error("--true_cfg_scale / --negative_prompt need a text encoder for the negative prompt: not with --synthetic")
     if args.synthetic and args.brain_guidance_scale is not None:
         p.error("--brain_guidance_scale goes to the images of --input_dir / --single_image: not with --synthetic")
+    if args.synthetic and any(a is not None for a in (args.apg_eta, args.apg_norm_threshold, args.apg_momentum)):
+        p.error("--apg_eta / --apg_norm_threshold / --apg_momentum act on a guided call: not with --synthetic")
     config = get_config()
     config.setdefault("model", {})
     if args.operands:
@@ -362,7 +380,8 @@ def main(argv=None):
                                             position_delta=[args.position_delta_x, args.position_delta_y], target_size=args.target_size,
                                             seed=args.seed, **_signals(brain_data, name),
                                             **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path),
-                                            **cfg_kwargs(args.true_cfg_scale, args.negative_prompt, args.brain_guidance_scale))
+                                            **cfg_kwargs(args.true_cfg_scale, args.negative_prompt, args.brain_guidance_scale, args.apg_eta,
+                                                         args.apg_norm_threshold, args.apg_momentum))
         os.makedirs(args.output_dir, exist_ok=True)
         output_path = os.path.join(args.output_dir, name)
         result_img.save(output_path)
@@ -382,7 +401,8 @@ def main(argv=None):
                             target_size=args.target_size, position_delta=[args.position_delta_x, args.position_delta_y], seed=args.seed,
                             brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir,
                             true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
-                            brain_guidance_scale=args.brain_guidance_scale)
+                            brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
     else:
         print(f"Running distributed inference on {world} GPUs")
         mp.set_start_method("spawn", force=True)

@@ -790,6 +790,140 @@ __global__ __launch_bounds__(256) void euler_cfg3_kernel(float* __restrict__ x, 
   }
 }
 
+// ---- the guided step under adaptive projected guidance (lx_euler_step_apg) -----------------------------------------------------------
+// Three launches, the order of include/lx.h. An image is cut into chunks of APG_CHUNK elements; block (chunk, image) owns one chunk, so no
+// chunk straddles two images. Within a chunk thread t owns the 4 elements at 1024 r + 4 t, r = 0..3, on the 16-byte path and on the element
+// path alike, and adds their products in (r, element) order: the two paths give the same bits.
+//   apg_reduce_kernel  Db of every element to M, and the chunk's (sum Db^2, sum Db w, sum w^2) in double to the workspace: per thread in its
+//                      fixed order, across the lanes of a wave by the xor tree, across the four waves in wave order by thread 0.
+//   apg_total_kernel   per image, the chunk triples added in chunk order. No atomics anywhere: the same bits from run to run.
+//   apg_step_kernel    reads the image's sums, forms the two fp32 coefficients, projects, steps, blends and stores to every part.
+constexpr int APG_CHUNK = 4096;
+
+template <int PARTS>
+__device__ __forceinline__ float apg_g0(float v0, float v1, float v2, float scale_a, float scale_b) {
+  const float g = fmaf(scale_a, __fsub_rn(v0, v1), v1);                  // euler_cfg1's g; euler_cfg3_1's gb
+  return PARTS == 2 ? g : fmaf(scale_b, __fsub_rn(g, v2), v2);
+}
+
+template <int VEC, int PARTS>
+__global__ __launch_bounds__(256) void apg_reduce_kernel(const float* __restrict__ x, const void* __restrict__ v, int v_bf16, float scale_a,
+                                                         float scale_b, float neg_sigma, float momentum, float* __restrict__ M,
+                                                         double* __restrict__ partials, size_t elems, size_t n) {
+  const size_t base = (size_t)blockIdx.y * elems, c0 = (size_t)blockIdx.x * APG_CHUNK;
+  double sdd = 0.0, sdw = 0.0, sww = 0.0;
+  for (int r = 0; r < 4; ++r) {
+    const size_t e = c0 + (size_t)r * 1024 + (size_t)threadIdx.x * 4;
+    if (e >= elems) break;
+    const size_t i = base + e;
+    const int cnt = elems - e < 4 ? (int)(elems - e) : 4;               // (4 on the 16-byte path: elems % 4 == 0 there)
+    float xi[4], vc[4], db[4];
+    if (VEC == 4) {
+      const f32x4 xx = *(const f32x4*)(x + i), v0 = load_v4(v, v_bf16, i), v1 = load_v4(v, v_bf16, n + i);
+      const f32x4 v2 = PARTS == 3 ? load_v4(v, v_bf16, 2 * n + i) : v1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xi[j] = xx[j];
+        vc[j] = v0[j];
+        db[j] = __fmul_rn(neg_sigma, __fsub_rn(apg_g0<PARTS>(v0[j], v1[j], v2[j], scale_a, scale_b), v0[j]));
+      }
+      if (momentum != 0.f) {
+        const f32x4 mm = *(const f32x4*)(M + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) db[j] = fmaf(momentum, mm[j], db[j]);
+      }
+      *(f32x4*)(M + i) = f32x4{db[0], db[1], db[2], db[3]};
+    } else {
+      for (int j = 0; j < cnt; ++j) {
+        const float v0 = load_v1(v, v_bf16, i + j), v1 = load_v1(v, v_bf16, n + i + j);
+        const float v2 = PARTS == 3 ? load_v1(v, v_bf16, 2 * n + i + j) : v1;
+        xi[j] = x[i + j];
+        vc[j] = v0;
+        db[j] = __fmul_rn(neg_sigma, __fsub_rn(apg_g0<PARTS>(v0, v1, v2, scale_a, scale_b), v0));
+        if (momentum != 0.f) db[j] = fmaf(momentum, M[i + j], db[j]);
+        M[i + j] = db[j];
+      }
+    }
+    for (int j = 0; j < cnt; ++j) {
+      const double d = (double)db[j], w = (double)fmaf(neg_sigma, vc[j], xi[j]);      // (products of two fp32 values: exact in double)
+      sdd += d * d;
+      sdw += d * w;
+      sww += w * w;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sdd += __shfl_xor(sdd, o, 64);
+    sdw += __shfl_xor(sdw, o, 64);
+    sww += __shfl_xor(sww, o, 64);
+  }
+  __shared__ double wave_sums[4][3];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    wave_sums[wave][0] = sdd;
+    wave_sums[wave][1] = sdw;
+    wave_sums[wave][2] = sww;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+    out[threadIdx.x] = ((wave_sums[0][threadIdx.x] + wave_sums[1][threadIdx.x]) + wave_sums[2][threadIdx.x]) + wave_sums[3][threadIdx.x];
+  }
+}
+
+// one wave per image; lane k < 3 adds component k of the image's chunk triples in chunk order
+__global__ __launch_bounds__(64) void apg_total_kernel(const double* __restrict__ partials, int chunks, double* __restrict__ sums) {
+  if (threadIdx.x >= 3) return;
+  const double* p = partials + (size_t)blockIdx.x * chunks * 3 + threadIdx.x;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += p[(size_t)c * 3];
+  sums[(size_t)blockIdx.x * 3 + threadIdx.x] = s;
+}
+
+__device__ __forceinline__ float apg_step1(float x, float vc, float db, float neg_sigma, float c32, float k32, float neg_inv_sigma, float ds) {
+  const float w = fmaf(neg_sigma, vc, x);
+  const float u = fmaf(c32, db, -__fmul_rn(k32, w));
+  return fmaf(ds, fmaf(neg_inv_sigma, u, vc), x);
+}
+
+template <int VEC, bool BLEND>
+__global__ __launch_bounds__(256) void apg_step_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, int parts,
+                                                       float neg_sigma, float neg_inv_sigma, float ds, float eta, float norm_threshold,
+                                                       const float* __restrict__ M, const double* __restrict__ sums,
+                                                       const float* __restrict__ x0, const float* __restrict__ z, const float* __restrict__ m,
+                                                       float sigma_next, float one_minus_sigma, size_t elems, size_t n) {
+  const double sdd = sums[(size_t)blockIdx.y * 3], sdw = sums[(size_t)blockIdx.y * 3 + 1], sww = sums[(size_t)blockIdx.y * 3 + 2];
+  const double r = (double)norm_threshold;
+  const double c = (norm_threshold > 0.f && sdd > r * r) ? r / sqrt(sdd) : 1.0;
+  const double a = sww > 0.0 ? sdw / sww : 0.0;
+  const float c32 = (float)c, k32 = (float)((c * (1.0 - (double)eta)) * a);
+  const size_t base = (size_t)blockIdx.y * elems, c0 = (size_t)blockIdx.x * APG_CHUNK;
+  for (int rr = 0; rr < 4; ++rr) {
+    const size_t e = c0 + (size_t)rr * 1024 + (size_t)threadIdx.x * 4;
+    if (e >= elems) break;
+    const size_t i = base + e;
+    if (VEC == 4) {
+      const f32x4 vc = load_v4(v, v_bf16, i), db = *(const f32x4*)(M + i);
+      f32x4 o = *(const f32x4*)(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = apg_step1(o[j], vc[j], db[j], neg_sigma, c32, k32, neg_inv_sigma, ds);
+      if (BLEND) {
+        const f32x4 s = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], s[j], b[j], mm[j], sigma_next, one_minus_sigma);
+      }
+      for (int p = 0; p < parts; ++p) *(f32x4*)(x + (size_t)p * n + i) = o;
+    } else {
+      const int cnt = elems - e < 4 ? (int)(elems - e) : 4;
+      for (int j = 0; j < cnt; ++j) {
+        float o = apg_step1(x[i + j], load_v1(v, v_bf16, i + j), M[i + j], neg_sigma, c32, k32, neg_inv_sigma, ds);
+        if (BLEND) o = blend1(o, x0[i + j], z[i + j], m[i + j], sigma_next, one_minus_sigma);
+        for (int p = 0; p < parts; ++p) x[(size_t)p * n + i + j] = o;
+      }
+    }
+  }
+}
+
 __global__ void convert_kernel(void* __restrict__ dst, int dst_bf16,const void* __restrict__ src, int src_bf16, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -1302,6 +1436,71 @@ extern "C" int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float 
   if (vec) launch_euler_cfg3<4>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
   else launch_euler_cfg3<1>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
   LX_LAUNCH_CHECK("lx_euler_step_cfg3");
+  return LX_OK;
+}
+
+// chunks of one image; 0 where n_images x chunks x 3 doubles, or 3 parts of n_images x elems floats, do not fit an address
+static size_t apg_chunks(int n_images, size_t elems) {
+  if (n_images < 1 || n_images > 65535 || elems == 0) return 0;
+  if (elems > SIZE_MAX / (3 * sizeof(float)) / (size_t)n_images) return 0;
+  const size_t chunks = (elems + APG_CHUNK - 1) / APG_CHUNK;
+  return chunks <= 0x7fffffffu ? chunks : 0;
+}
+
+extern "C" size_t lx_apg_workspace_bytes(int n_images, size_t elems) {
+  return apg_chunks(n_images, elems) * (size_t)(n_images > 0 ? n_images : 0) * 3 * sizeof(double);
+}
+
+template <int VEC>
+static void launch_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float eta,
+                       float norm_threshold, float momentum, float* M, double* sums, double* partials, const float* x0, const float* z,
+                       const float* m, float sigma_next, int n_images, size_t elems, hipStream_t stream) {
+  const size_t n = (size_t)n_images * elems;
+  const int chunks = (int)apg_chunks(n_images, elems);
+  const dim3 grid(chunks, n_images);
+  const float neg_sigma = -sigma, neg_inv_sigma = -(1.0f / sigma), oms = 1.0f - sigma_next;
+  if (n_parts == 2) hipLaunchKernelGGL((apg_reduce_kernel<VEC, 2>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
+  else hipLaunchKernelGGL((apg_reduce_kernel<VEC, 3>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
+  hipLaunchKernelGGL(apg_total_kernel, dim3(n_images), dim3(64), 0, stream, (const double*)partials, chunks, sums);
+  if (m) hipLaunchKernelGGL((apg_step_kernel<VEC, true>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, x0, z, m, sigma_next, oms, elems, n);
+  else hipLaunchKernelGGL((apg_step_kernel<VEC, false>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, x0, z, m, sigma_next, oms, elems, n);
+}
+
+extern "C" int lx_euler_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
+                                 float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
+                                 size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images,
+                                 size_t elems, void* stream) {
+  LX_CHECK_ARG(x && v && M && sums && workspace, "lx_euler_step_apg: NULL x, v, M, sums or workspace");
+  LX_CHECK_ARG(n_parts == 2 || n_parts == 3, "lx_euler_step_apg: n_parts=%d must be 2 or 3", n_parts);
+  LX_CHECK_ARG(n_images >= 1 && elems > 0, "lx_euler_step_apg: n_images < 1 or elems == 0");
+  LX_CHECK_ARG(apg_chunks(n_images, elems) > 0, "lx_euler_step_apg: more than 65535 images, or the parts do not fit an address");
+  LX_CHECK_ARG(f32_is_finite(sigma) && sigma > 0.f, "lx_euler_step_apg: sigma must be finite and > 0");
+  LX_CHECK_ARG(f32_is_finite(scale_a) && (n_parts == 2 || f32_is_finite(scale_b)), "lx_euler_step_apg: a scale is not finite");
+  LX_CHECK_ARG(f32_is_finite(eta) && f32_is_finite(norm_threshold) && f32_is_finite(momentum),
+               "lx_euler_step_apg: eta, norm_threshold or momentum is not finite");
+  LX_CHECK_ARG(eta >= 0.f && eta <= 1.f, "lx_euler_step_apg: eta must lie in [0, 1]");
+  LX_CHECK_ARG(norm_threshold >= 0.f, "lx_euler_step_apg: norm_threshold must be >= 0");
+  LX_CHECK_ARG(momentum > -1.f && momentum < 1.f, "lx_euler_step_apg: |momentum| must be < 1");
+  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_apg: x0, z and m go together (all NULL: no blend)");
+  LX_CHECK_ARG(workspace_bytes >= lx_apg_workspace_bytes(n_images, elems), "lx_euler_step_apg: the workspace is smaller than lx_apg_workspace_bytes");
+  LX_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)sums) & 7) == 0, "lx_euler_step_apg: the workspace and sums must be 8-byte aligned");
+  const size_t n = (size_t)n_images * elems, xbytes = (size_t)n_parts * n * sizeof(float), pbytes = n * sizeof(float);
+  const size_t vbytes = (size_t)n_parts * n * (v_is_bf16 ? 2 : 4);
+  LX_CHECK_ARG(!byte_ranges_overlap(x, xbytes, M, pbytes) && !byte_ranges_overlap(x, xbytes, sums, (size_t)n_images * 3 * sizeof(double)) &&
+               !byte_ranges_overlap(x, xbytes, workspace, workspace_bytes),
+               "lx_euler_step_apg: M, sums and the workspace may not overlap x[0, n_parts n)");
+  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, pbytes) && !byte_ranges_overlap(x, xbytes, z, pbytes) &&
+                      !byte_ranges_overlap(x, xbytes, m, pbytes)),
+               "lx_euler_step_apg: x0, z and m may not alias x[0, n_parts n) (it is updated in place)");
+  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_apg: v may not alias x[0, n_parts n)");
+  LX_CHECK_ARG(!byte_ranges_overlap(v, vbytes, M, pbytes), "lx_euler_step_apg: M may not overlap v (it is written while v is read)");
+  // every part and every image start: x + p n + b elems and the like are aligned only where elems % 4 == 0
+  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
+  const bool vec = elems % 4 == 0 && (((uintptr_t)x | (uintptr_t)M | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 &&
+                   ((uintptr_t)v & v_align) == 0;
+  if (vec) launch_apg<4>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, x0, z, m, sigma_next, n_images, elems, (hipStream_t)stream);
+  else launch_apg<1>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, x0, z, m, sigma_next, n_images, elems, (hipStream_t)stream);
+  LX_LAUNCH_CHECK("lx_euler_step_apg");
   return LX_OK;
 }
 

@@ -24,6 +24,12 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       v_b = v_T + s_b (v_F - v_T), then g = v_N + s_t (v_b - v_N) under true CFG. On only where the signals changed an embedding (decided by
       tensor identity); otherwise one RuntimeWarning and the call without it. One forward per step at batch k·B·n, [F; T], [F; N] or
       [F; T; N]; lx_euler_step_cfg steps two branches, lx_euler_step_cfg3 three.
+  Q10 adaptive projected guidance (apg_eta, apg_norm_threshold, apg_momentum; Sadat, Hilliges and Weber -- PAPERS.md; neither the
+      reference nor diffusers' FluxPipeline has it): against the oversaturation of high guidance scales, the TOTAL guidance update of a
+      guided call (Q7 and/or Q9) is taken to the space of the denoised prediction, given a momentum, clamped in norm and split along the
+      first branch's prediction, whose part is weighted by eta. On only where the call is guided and one of the three differs from its
+      default (1, 0, 0); otherwise the call is what it was, bit for bit (unguided: one RuntimeWarning). lx_euler_step_apg then steps in
+      place of lx_euler_step_cfg / lx_euler_step_cfg3; the per-step sums stay on the device as the output's `lx_apg`.
 """
 from __future__ import annotations
 
@@ -37,7 +43,7 @@ import torch
 import yaml
 
 from .condition import Condition
-from .pipeline import FluxPipelineOutput, calculate_shift, retrieve_timesteps
+from .pipeline import ApgState, FluxPipelineOutput, calculate_shift, retrieve_timesteps
 from .pipeline_tools import encode_images
 from .step_cache import step_cache_config
 from .transformer import tranformer_forward
@@ -101,10 +107,11 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    latent_mask: Optional[torch.Tensor] = None, strength: float = 1.0,
                    negative_prompt: Union[str, List[str]] = None, negative_prompt_2=None,
                    negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
-                   true_cfg_scale: float = 1.0, brain_guidance_scale: float = 1.0, **kwargs):
+                   true_cfg_scale: float = 1.0, brain_guidance_scale: float = 1.0, apg_eta: float = 1.0,
+                   apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, **kwargs):
     """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline, the true-CFG
-    keywords of its FluxPipeline and this project's brain_guidance_scale are named here (so they are not among the swallowed **kwargs) and
-    returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params."""
+    keywords of its FluxPipeline and this project's brain_guidance_scale and apg_* are named here (so they are not among the swallowed
+    **kwargs) and returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params / prepare_apg_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
@@ -134,6 +141,31 @@ def _brain_cfg(brain_guidance_scale) -> bool:
     if float(s) < 1:
         warnings.warn(f"brain_guidance_scale={s} (< 1): guidance is off, running the plain call", RuntimeWarning, stacklevel=3)
     return float(s) > 1
+
+
+def prepare_apg_params(apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, **kwargs):
+    return apg_eta, apg_norm_threshold, apg_momentum
+
+
+_APG_UNGUIDED = ("apg_eta / apg_norm_threshold / apg_momentum were given but the call is not guided (neither true_cfg_scale nor "
+                 "brain_guidance_scale is on): there is no guidance update to project, running the plain call")
+
+
+def _apg(apg_eta, apg_norm_threshold, apg_momentum):
+    """generate()'s apg_eta / apg_norm_threshold / apg_momentum -> (eta, norm_threshold, momentum) as floats where adaptive projected
+    guidance is asked for (one of them differs from its default), else None; whether it is ON is known only once the branches are (it needs
+    a guided call). A refusal is a ValueError on the host, before anything of the pipeline is touched."""
+    for name, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
+            raise ValueError(f"{name} must be a finite number, got {value!r}")
+    eta, norm_threshold, momentum = float(apg_eta), float(apg_norm_threshold), float(apg_momentum)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"apg_eta must lie in [0, 1] (the weight of the update's part along the prediction), got {apg_eta!r}")
+    if norm_threshold < 0.0:
+        raise ValueError(f"apg_norm_threshold must be >= 0 (0: no clamp), got {apg_norm_threshold!r}")
+    if not abs(momentum) < 1.0:
+        raise ValueError(f"apg_momentum must lie in (-1, 1), got {apg_momentum!r}")
+    return None if (eta, norm_threshold, momentum) == (1.0, 0.0, 0.0) else (eta, norm_threshold, momentum)
 
 
 def _fits_positive(name, neg, pos):
@@ -291,6 +323,10 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     # ---- guidance along the brain signal (Q9): the scale is checked here; whether it is on is known after the brain section
     brain_guidance_scale = prepare_brain_cfg_params(**params)
     want_brain_cfg = _brain_cfg(brain_guidance_scale)
+    # ---- adaptive projected guidance (Q10): the three values are checked here; it is on only if the call ends up guided
+    want_apg = _apg(*prepare_apg_params(**params))
+    if want_apg is not None and not do_true_cfg and not want_brain_cfg:
+        warnings.warn(_APG_UNGUIDED, RuntimeWarning, stacklevel=2)
     step_cache_config(model_config)          # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
@@ -436,6 +472,9 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
     step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
     n_images = latents.shape[0]
+    apg_state = None
+    if want_apg is not None and n_branches == 1 and (do_true_cfg or want_brain_cfg):      # (brain guidance was asked for and is off)
+        warnings.warn(_APG_UNGUIDED, RuntimeWarning, stacklevel=2)
     if n_branches > 1:
         # the start latents once per branch ([full; text; negative] where all are on; the draw above stays [B·n, ...], so the generator is
         # consumed as in the plain call), the condition tokens and a [B·n] attention mask for every part; image_latents / noise / mask stay
@@ -444,6 +483,11 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             step_kwargs["true_cfg_scale"] = float(true_cfg_scale)
         if do_brain_cfg:
             step_kwargs["brain_guidance_scale"] = float(brain_guidance_scale)
+        if want_apg is not None:
+            # (Q10) one state for the steps of this call: M and the sums have one part's shape, [B·n, ...]; lx_euler_step_apg then steps in
+            # place of lx_euler_step_cfg / lx_euler_step_cfg3. With all three keywords at their defaults the call is not routed here.
+            apg_state = ApgState(*want_apg, tuple(latents.shape), len(timesteps), device)
+            step_kwargs["apg"] = apg_state
         latents = torch.cat([latents] * n_branches)
         if use_condition:
             condition_latents = condition_latents.repeat(n_branches * n_images // condition_latents.shape[0], 1, 1)
@@ -474,6 +518,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
 
     def denoise(latents, prompt_embeds, model_config):
         nonlocal step_cache_report
+        if apg_state is not None:
+            apg_state.zero()                  # (empty momentum: the fp16 fallback's second pass starts as a fresh call does)
         with adapter_weight_tiles(engine, n_branches), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
@@ -560,4 +606,5 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             pipeline.transformer.engine.check_status(sync=False)
     if not return_dict:
         return (image,)
-    return FluxPipelineOutput(images=image, lx_operands=operands_used, lx_step_cache=step_cache_report)
+    return FluxPipelineOutput(images=image, lx_operands=operands_used, lx_step_cache=step_cache_report,
+                              lx_apg=None if apg_state is None else apg_state.sums)

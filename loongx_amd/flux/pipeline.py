@@ -30,6 +30,26 @@ def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4
     return image_seq_len * m + (base_shift - m * base_seq_len)
 
 
+class ApgState:
+    """What adaptive projected guidance carries through the steps of one guided call (FlowMatchEulerDiscreteScheduler.step(apg=)): the three
+    parameters, the momentum buffer M (fp32, one part's shape, in the space of the denoised prediction), the sums every step leaves
+    ([steps, images, 3] float64: sum Db^2, sum Db w, sum w^2 per image; on the device, never synchronised), lx_euler_step_apg's workspace and
+    the number of steps taken. zero() is the state before the first step."""
+
+    def __init__(self, eta: float, norm_threshold: float, momentum: float, part_shape, steps: int, device):
+        images, elems = int(part_shape[0]), int(np.prod(part_shape[1:], dtype=np.int64))
+        self.eta, self.norm_threshold, self.momentum = float(eta), float(norm_threshold), float(momentum)
+        self.M = torch.zeros(tuple(part_shape), dtype=torch.float32, device=device)
+        self.sums = torch.zeros(int(steps), images, 3, dtype=torch.float64, device=device)
+        self.workspace = torch.empty(max(ops.apg_workspace_bytes(images, elems), 8) // 8, dtype=torch.float64, device=device)
+        self.step = 0
+
+    def zero(self):
+        self.M.zero_()
+        self.sums.zero_()
+        self.step = 0
+
+
 class FlowMatchEulerDiscreteScheduler:
     """FLUX.1-dev scheduler config; sigma schedule on the host in fp64 -> fp32 like diffusers, step on the GPU."""
     order = 1
@@ -89,7 +109,7 @@ class FlowMatchEulerDiscreteScheduler:
         return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None,
-             brain_guidance_scale=None):
+             brain_guidance_scale=None, apg=None):
         """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
         inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
         level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend).
@@ -99,7 +119,14 @@ class FlowMatchEulerDiscreteScheduler:
         brain_guidance_scale = s_b (> 1; generate's guidance along the brain signal): alone, the leading dimension is 2B, [full; text], and
         the step is the same launch along text + s_b * (full - text). With true_cfg_scale = s_t as well the leading dimension is 3B,
         [full; text; negative], and all three parts of prev are the step of the first along neg + s_t * (text + s_b * (full - text) - neg),
-        in one launch (lx_euler_step_cfg3). inpaint has the shape of one part."""
+        in one launch (lx_euler_step_cfg3). inpaint has the shape of one part.
+        apg = an ApgState made for one part's shape (generate's apg_eta / apg_norm_threshold / apg_momentum): only together with
+        true_cfg_scale and/or brain_guidance_scale. The same batch, stepped by lx_euler_step_apg instead: the total guidance update is
+        clamped, given momentum and projected on the first branch's denoised prediction, per image; the state's next row of sums is written
+        on the device. Without apg the method launches what it launched before."""
+        if apg is not None and brain_guidance_scale is None and true_cfg_scale is None:
+            raise ValueError("step(apg=...): adaptive projected guidance acts on a guidance update; pass true_cfg_scale and/or "
+                             "brain_guidance_scale with it")
         i = self._step_index
         ds = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i]))
         x = sample.to(torch.float32).clone() if (sample.dtype != torch.float32 or not sample.is_contiguous()) else sample.clone()
@@ -128,7 +155,15 @@ class FlowMatchEulerDiscreteScheduler:
             if not (tuple(x0.shape) == tuple(z.shape) == tuple(m.shape) == half):
                 raise ValueError(f"step(inpaint=...): image_latents {tuple(x0.shape)}, noise {tuple(z.shape)} and mask {tuple(m.shape)} must "
                                  f"have the latents' shape {half}")
-        if brain_guidance_scale is not None and true_cfg_scale is not None:
+        if apg is not None:
+            if tuple(apg.M.shape) != half or apg.M.dtype != torch.float32 or apg.sums.shape[1] != half[0] or not apg.step < apg.sums.shape[0]:
+                raise ValueError(f"step(apg=...): the state (M {tuple(apg.M.shape)}, sums {tuple(apg.sums.shape)}, step {apg.step}) was not "
+                                 f"made for parts of shape {half} or has run out of steps")
+            scales = tuple(float(s) for s in (brain_guidance_scale, true_cfg_scale) if s is not None)
+            ops.euler_step_apg(x, v.contiguous(), float(self._sig_host[i]), ds, scales, apg.eta, apg.norm_threshold, apg.momentum, apg.M,
+                               apg.sums[apg.step], apg.workspace, inpaint, float(self._sig_host[i + 1]))
+            apg.step += 1
+        elif brain_guidance_scale is not None and true_cfg_scale is not None:
             ops.euler_step_cfg3(x, v.contiguous(), ds, float(brain_guidance_scale), float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
         elif brain_guidance_scale is not None:
             ops.euler_step_cfg(x, v.contiguous(), ds, float(brain_guidance_scale), inpaint, float(self._sig_host[i + 1]))

@@ -672,6 +672,46 @@ def euler_step_cfg3(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale_brain
                                  ptr(x0), ptr(z), ptr(m), float(sigma_next), n, _stream()), "lx_euler_step_cfg3")
 
 
+def apg_workspace_bytes(n_images: int, elems: int) -> int:
+    """bytes of euler_step_apg's workspace for parts of n_images images of elems elements (lx_apg_workspace_bytes)"""
+    return int(lib.lx_apg_workspace_bytes(int(n_images), int(elems)))
+
+
+def euler_step_apg(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: float, scales, eta: float, norm_threshold: float, momentum: float,
+                   M: torch.Tensor, sums: torch.Tensor, workspace: torch.Tensor, inpaint=None, sigma_next: float = 0.0) -> None:
+    """The guided step under adaptive projected guidance, in place (lx_euler_step_apg). scales = (s,): x fp32 and v fp32 or bf16 hold two
+    parts laid out as euler_step_cfg's; scales = (scale_brain, scale_text): three parts as euler_step_cfg3's. M is fp32 with one part's
+    element count (the momentum state: read unless momentum == 0, always written), sums float64 [n_images, 3] (written: sum Db^2, sum Db w,
+    sum w^2 per image; its first dimension says how many images a part holds), workspace a contiguous buffer of at least
+    apg_workspace_bytes(n_images, elems) bytes. inpaint = (x0, z, m), fp32 with one part's element count. All contiguous; nothing is
+    synchronised."""
+    _req(x, torch.float32, "x")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    scales = tuple(float(s) for s in scales)
+    assert len(scales) in (1, 2), "euler_step_apg: scales is (scale,) for two parts or (scale_brain, scale_text) for three"
+    parts = len(scales) + 1
+    n = x.numel() // parts
+    assert x.numel() == parts * n and v.numel() == parts * n, f"euler_step_apg: x and v hold {parts} parts of one element count"
+    _req(M, torch.float32, "M")
+    _req(sums, torch.float64, "sums")
+    assert M.numel() == n, "euler_step_apg: M has the element count of one part"
+    assert sums.dim() == 2 and sums.shape[1] == 3 and sums.shape[0] >= 1, "euler_step_apg: sums is [n_images, 3]"
+    n_images = sums.shape[0]
+    assert n % n_images == 0, "euler_step_apg: a part holds n_images images of one element count"
+    x0 = z = m = None
+    if inpaint is not None:
+        x0, z, m = inpaint
+        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
+        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_apg: x0, z and m have the element count of one part"
+    assert all(t.is_contiguous() for t in (x, v, M, sums, workspace, x0, z, m) if t is not None), "euler_step_apg: contiguous operands"
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    check(lib.lx_euler_step_apg(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), parts, scales[0], scales[-1], float(sigma),
+                                float(dsigma), float(eta), float(norm_threshold), float(momentum), M.data_ptr(), sums.data_ptr(),
+                                workspace.data_ptr(), workspace.numel() * workspace.element_size(), ptr(x0), ptr(z), ptr(m),
+                                float(sigma_next), n_images, n // n_images, _stream()), "lx_euler_step_apg")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
