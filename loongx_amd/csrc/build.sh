@@ -8,7 +8,7 @@ OBJ="$HERE/../lib/obj"
 mkdir -p "$OUT" "$OBJ"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result "$@")
-SRCS=(api gemm gemm_f16 gemm_modes gemm4 gemm4_f16 gemm4_split attn attn4 attn_mask rowops precise fp8 vae cs3 dgf)
+SRCS=(api gemm gemm_f16 gemm_modes gemm4 gemm4_f16 gemm4_split attn attn4 attn_mask rowops step precise fp8 vae cs3 dgf)
 # per-file flags. attn: the online softmax takes row maxima of MFMA results; with NaNs honoured hipcc quiets every such operand first
 # (v_max_f32 x, x, x: 10-14 extra vector instructions per key tile in kernels whose vector pipe is the bottleneck). The kernels mask with
 # -1e30, never with NaN / inf.

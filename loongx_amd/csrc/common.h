@@ -32,6 +32,12 @@ void lx_set_error(const char* fmt, ...);
     }                                                                           \
   } while (0)
 
+// [a, a + na) and [b, b + nb) bytes share an address
+inline bool byte_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+
 __device__ __forceinline__ float bf16_to_f32(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // fp32 -> bf16, round-to-nearest-even, through the native __bf16 cast: hipcc lowers it to the gfx950 hardware
 // converts (v_cvt_pk_bf16_f32) -- branch-free, NaN-safe. (A hand-rolled bit trick with a NaN branch compiles to

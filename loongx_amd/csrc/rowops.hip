@@ -1,5 +1,5 @@
 // rowops.hip -- HBM-bound row kernels of the DiT step (gfx950): AdaLN LayerNorm+modulate, per-head
-// RMSNorm+RoPE(+V^T image), LoRA down-projection, skinny (M<=16) linears, timestep embedding, Euler step.
+// RMSNorm+RoPE(+V^T image), LoRA down-projection, skinny (M<=16) linears, timestep embedding. (The scheduler step: step.hip.)
 // All loads/stores are 8-16 B per lane and coalesced; reductions are wave64 shuffles (no LDS, no atomics).
 #include "row_common.h"
 #include <type_traits>
@@ -626,304 +626,6 @@ __global__ void timestep_embed_kernel(const float* __restrict__ t, float* __rest
   out[(size_t)b * dim + half + j] = sinf(a);
 }
 
-__global__ void euler_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, size_t n) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float vv = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[i]) : ((const float*)v)[i];
-    x[i] = fmaf(ds, vv, x[i]);
-  }
-}
-
-// ---- img2img start and the inpaint step (lx_scale_noise, lx_euler_step_blend) ----------------------------------------------------------
-// The operation order is the contract of include/lx.h: three fused multiply-adds, two separately rounded products, written out so that
-// no contraction setting can move a rounding. A work item is VEC consecutive elements (VEC = 4: 16-byte accesses, 8-byte for bf16 v;
-// taken when every pointer is 16-byte aligned; the last n % 4 elements go one by one), grid-stride loop under euler_kernel's grid cap.
-__device__ __forceinline__ float scale_noise1(float x0, float z, float sigma, float one_minus_sigma) {
-  return fmaf(sigma, z, __fmul_rn(one_minus_sigma, x0));
-}
-// the stepped value e blended with the source noised to the next level
-__device__ __forceinline__ float blend1(float e, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
-  const float r = scale_noise1(x0, z, sigma_next, one_minus_sigma);
-  return fmaf(m, e, __fmul_rn(__fsub_rn(1.f, m), r));
-}
-__device__ __forceinline__ float euler_blend1(float x, float v, float ds, float x0, float z, float m, float sigma_next, float one_minus_sigma) {
-  return blend1(fmaf(ds, v, x), x0, z, m, sigma_next, one_minus_sigma);
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void scale_noise_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ z,
-                                                          float sigma, float one_minus_sigma, size_t n) {
-  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t i = it * VEC;
-    if (VEC == 4 && i + 4 <= n) {
-      const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i);
-      f32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = scale_noise1(a[j], b[j], sigma, one_minus_sigma);
-      *(f32x4*)(out + i) = o;
-    } else {
-      for (size_t k = i; k < n && k < i + VEC; ++k) out[k] = scale_noise1(x0[k], z[k], sigma, one_minus_sigma);
-    }
-  }
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void euler_blend_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds,
-                                                          const float* __restrict__ x0, const float* __restrict__ z,
-                                                          const float* __restrict__ m, float sigma_next, float one_minus_sigma, size_t n) {
-  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t i = it * VEC;
-    if (VEC == 4 && i + 4 <= n) {
-      f32x4 vv;
-      if (v_bf16) {
-        const u32x2 p = *(const u32x2*)((const uint16_t*)v + i);
-        vv = f32x4{bf16_to_f32((uint16_t)(p[0] & 0xffffu)), bf16_to_f32((uint16_t)(p[0] >> 16)),
-                   bf16_to_f32((uint16_t)(p[1] & 0xffffu)), bf16_to_f32((uint16_t)(p[1] >> 16))};
-      } else {
-        vv = *(const f32x4*)((const float*)v + i);
-      }
-      const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
-      f32x4 o = *(const f32x4*)(x + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = euler_blend1(o[j], vv[j], ds, a[j], b[j], mm[j], sigma_next, one_minus_sigma);
-      *(f32x4*)(x + i) = o;
-    } else {
-      for (size_t k = i; k < n && k < i + VEC; ++k) {
-        const float vk = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[k]) : ((const float*)v)[k];
-        x[k] = euler_blend1(x[k], vk, ds, x0[k], z[k], m[k], sigma_next, one_minus_sigma);
-      }
-    }
-  }
-}
-
-// ---- the guided step (lx_euler_step_cfg) --------------------------------------------------------------------------------------------
-// x and v hold two halves of n elements, [positive; negative]. g = vn + scale (vp - vn), the Euler step on g from the positive half of x,
-// the inpaint blend where BLEND, and the result stored to both halves: the order of include/lx.h, one rounding per named operation.
-// VEC = 4 reads and writes both halves 16 bytes at a time (8 for bf16 v). The host takes it only when the second halves x + n and v + n
-// are aligned as well as the first, which needs n % 4 == 0: there is no element tail on that path.
-__device__ __forceinline__ float euler_cfg1(float x, float vp, float vn, float ds, float scale) {
-  return fmaf(ds, fmaf(scale, __fsub_rn(vp, vn), vn), x);
-}
-__device__ __forceinline__ f32x4 load_v4(const void* __restrict__ v, int v_bf16, size_t i) {
-  if (v_bf16) {
-    const u32x2 p = *(const u32x2*)((const uint16_t*)v + i);
-    return f32x4{bf16_to_f32((uint16_t)(p[0] & 0xffffu)), bf16_to_f32((uint16_t)(p[0] >> 16)),
-                 bf16_to_f32((uint16_t)(p[1] & 0xffffu)), bf16_to_f32((uint16_t)(p[1] >> 16))};
-  }
-  return *(const f32x4*)((const float*)v + i);
-}
-
-template <int VEC, bool BLEND>
-__global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, float scale,
-                                                        const float* __restrict__ x0, const float* __restrict__ z,
-                                                        const float* __restrict__ m, float sigma_next, float one_minus_sigma, size_t n) {
-  const size_t items = n / VEC, stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t i = it * VEC;
-    if (VEC == 4) {
-      const f32x4 vp = load_v4(v, v_bf16, i), vn = load_v4(v, v_bf16, n + i);
-      f32x4 o = *(const f32x4*)(x + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = euler_cfg1(o[j], vp[j], vn[j], ds, scale);
-      if (BLEND) {
-        const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], a[j], b[j], mm[j], sigma_next, one_minus_sigma);
-      }
-      *(f32x4*)(x + i) = o;
-      *(f32x4*)(x + n + i) = o;
-    } else {
-      const float vp = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[i]) : ((const float*)v)[i];
-      const float vn = v_bf16 ? bf16_to_f32(((const uint16_t*)v)[n + i]) : ((const float*)v)[n + i];
-      float o = euler_cfg1(x[i], vp, vn, ds, scale);
-      if (BLEND) o = blend1(o, x0[i], z[i], m[i], sigma_next, one_minus_sigma);
-      x[i] = o;
-      x[n + i] = o;
-    }
-  }
-}
-
-// ---- the twice-guided step (lx_euler_step_cfg3) ---------------------------------------------------------------------------------------
-// x and v hold three parts of n elements, [full; text; negative]. gb = vt + scale_brain (vf - vt), g = vn + scale_text (gb - vn), the Euler
-// step on g from the first part of x, the inpaint blend where BLEND, and the result stored to all three parts: the order of include/lx.h,
-// one rounding per named operation. VEC = 4 as in euler_cfg_kernel: the host takes it only when all three parts of x and of v are aligned
-// (n % 4 == 0), so that path has no element tail. vf == vt bit for bit makes gb == vt exactly (0 * scale_brain + vt; the scale is finite),
-// and what is left is euler_cfg1 on (vt, vn).
-__device__ __forceinline__ float euler_cfg3_1(float x, float vf, float vt, float vn, float ds, float scale_brain, float scale_text) {
-  const float gb = fmaf(scale_brain, __fsub_rn(vf, vt), vt);
-  return fmaf(ds, fmaf(scale_text, __fsub_rn(gb, vn), vn), x);
-}
-__device__ __forceinline__ float load_v1(const void* __restrict__ v, int v_bf16, size_t i) {
-  return v_bf16 ? bf16_to_f32(((const uint16_t*)v)[i]) : ((const float*)v)[i];
-}
-
-template <int VEC, bool BLEND>
-__global__ __launch_bounds__(256) void euler_cfg3_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds,
-                                                         float scale_brain, float scale_text, const float* __restrict__ x0,
-                                                         const float* __restrict__ z, const float* __restrict__ m, float sigma_next,
-                                                         float one_minus_sigma, size_t n) {
-  const size_t items = n / VEC, stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t i = it * VEC;
-    if (VEC == 4) {
-      const f32x4 vf = load_v4(v, v_bf16, i), vt = load_v4(v, v_bf16, n + i), vn = load_v4(v, v_bf16, 2 * n + i);
-      f32x4 o = *(const f32x4*)(x + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = euler_cfg3_1(o[j], vf[j], vt[j], vn[j], ds, scale_brain, scale_text);
-      if (BLEND) {
-        const f32x4 a = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], a[j], b[j], mm[j], sigma_next, one_minus_sigma);
-      }
-      *(f32x4*)(x + i) = o;
-      *(f32x4*)(x + n + i) = o;
-      *(f32x4*)(x + 2 * n + i) = o;
-    } else {
-      float o = euler_cfg3_1(x[i], load_v1(v, v_bf16, i), load_v1(v, v_bf16, n + i), load_v1(v, v_bf16, 2 * n + i), ds, scale_brain, scale_text);
-      if (BLEND) o = blend1(o, x0[i], z[i], m[i], sigma_next, one_minus_sigma);
-      x[i] = o;
-      x[n + i] = o;
-      x[2 * n + i] = o;
-    }
-  }
-}
-
-// ---- the guided step under adaptive projected guidance (lx_euler_step_apg) -----------------------------------------------------------
-// Three launches, the order of include/lx.h. An image is cut into chunks of APG_CHUNK elements; block (chunk, image) owns one chunk, so no
-// chunk straddles two images. Within a chunk thread t owns the 4 elements at 1024 r + 4 t, r = 0..3, on the 16-byte path and on the element
-// path alike, and adds their products in (r, element) order: the two paths give the same bits.
-//   apg_reduce_kernel  Db of every element to M, and the chunk's (sum Db^2, sum Db w, sum w^2) in double to the workspace: per thread in its
-//                      fixed order, across the lanes of a wave by the xor tree, across the four waves in wave order by thread 0.
-//   apg_total_kernel   per image, the chunk triples added in chunk order. No atomics anywhere: the same bits from run to run.
-//   apg_step_kernel    reads the image's sums, forms the two fp32 coefficients, projects, steps, blends and stores to every part.
-constexpr int APG_CHUNK = 4096;
-
-template <int PARTS>
-__device__ __forceinline__ float apg_g0(float v0, float v1, float v2, float scale_a, float scale_b) {
-  const float g = fmaf(scale_a, __fsub_rn(v0, v1), v1);                  // euler_cfg1's g; euler_cfg3_1's gb
-  return PARTS == 2 ? g : fmaf(scale_b, __fsub_rn(g, v2), v2);
-}
-
-template <int VEC, int PARTS>
-__global__ __launch_bounds__(256) void apg_reduce_kernel(const float* __restrict__ x, const void* __restrict__ v, int v_bf16, float scale_a,
-                                                         float scale_b, float neg_sigma, float momentum, float* __restrict__ M,
-                                                         double* __restrict__ partials, size_t elems, size_t n) {
-  const size_t base = (size_t)blockIdx.y * elems, c0 = (size_t)blockIdx.x * APG_CHUNK;
-  double sdd = 0.0, sdw = 0.0, sww = 0.0;
-  for (int r = 0; r < 4; ++r) {
-    const size_t e = c0 + (size_t)r * 1024 + (size_t)threadIdx.x * 4;
-    if (e >= elems) break;
-    const size_t i = base + e;
-    const int cnt = elems - e < 4 ? (int)(elems - e) : 4;               // (4 on the 16-byte path: elems % 4 == 0 there)
-    float xi[4], vc[4], db[4];
-    if (VEC == 4) {
-      const f32x4 xx = *(const f32x4*)(x + i), v0 = load_v4(v, v_bf16, i), v1 = load_v4(v, v_bf16, n + i);
-      const f32x4 v2 = PARTS == 3 ? load_v4(v, v_bf16, 2 * n + i) : v1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xi[j] = xx[j];
-        vc[j] = v0[j];
-        db[j] = __fmul_rn(neg_sigma, __fsub_rn(apg_g0<PARTS>(v0[j], v1[j], v2[j], scale_a, scale_b), v0[j]));
-      }
-      if (momentum != 0.f) {
-        const f32x4 mm = *(const f32x4*)(M + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) db[j] = fmaf(momentum, mm[j], db[j]);
-      }
-      *(f32x4*)(M + i) = f32x4{db[0], db[1], db[2], db[3]};
-    } else {
-      for (int j = 0; j < cnt; ++j) {
-        const float v0 = load_v1(v, v_bf16, i + j), v1 = load_v1(v, v_bf16, n + i + j);
-        const float v2 = PARTS == 3 ? load_v1(v, v_bf16, 2 * n + i + j) : v1;
-        xi[j] = x[i + j];
-        vc[j] = v0;
-        db[j] = __fmul_rn(neg_sigma, __fsub_rn(apg_g0<PARTS>(v0, v1, v2, scale_a, scale_b), v0));
-        if (momentum != 0.f) db[j] = fmaf(momentum, M[i + j], db[j]);
-        M[i + j] = db[j];
-      }
-    }
-    for (int j = 0; j < cnt; ++j) {
-      const double d = (double)db[j], w = (double)fmaf(neg_sigma, vc[j], xi[j]);      // (products of two fp32 values: exact in double)
-      sdd += d * d;
-      sdw += d * w;
-      sww += w * w;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sdd += __shfl_xor(sdd, o, 64);
-    sdw += __shfl_xor(sdw, o, 64);
-    sww += __shfl_xor(sww, o, 64);
-  }
-  __shared__ double wave_sums[4][3];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    wave_sums[wave][0] = sdd;
-    wave_sums[wave][1] = sdw;
-    wave_sums[wave][2] = sww;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-    out[threadIdx.x] = ((wave_sums[0][threadIdx.x] + wave_sums[1][threadIdx.x]) + wave_sums[2][threadIdx.x]) + wave_sums[3][threadIdx.x];
-  }
-}
-
-// one wave per image; lane k < 3 adds component k of the image's chunk triples in chunk order
-__global__ __launch_bounds__(64) void apg_total_kernel(const double* __restrict__ partials, int chunks, double* __restrict__ sums) {
-  if (threadIdx.x >= 3) return;
-  const double* p = partials + (size_t)blockIdx.x * chunks * 3 + threadIdx.x;
-  double s = 0.0;
-  for (int c = 0; c < chunks; ++c) s += p[(size_t)c * 3];
-  sums[(size_t)blockIdx.x * 3 + threadIdx.x] = s;
-}
-
-__device__ __forceinline__ float apg_step1(float x, float vc, float db, float neg_sigma, float c32, float k32, float neg_inv_sigma, float ds) {
-  const float w = fmaf(neg_sigma, vc, x);
-  const float u = fmaf(c32, db, -__fmul_rn(k32, w));
-  return fmaf(ds, fmaf(neg_inv_sigma, u, vc), x);
-}
-
-template <int VEC, bool BLEND>
-__global__ __launch_bounds__(256) void apg_step_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, int parts,
-                                                       float neg_sigma, float neg_inv_sigma, float ds, float eta, float norm_threshold,
-                                                       const float* __restrict__ M, const double* __restrict__ sums,
-                                                       const float* __restrict__ x0, const float* __restrict__ z, const float* __restrict__ m,
-                                                       float sigma_next, float one_minus_sigma, size_t elems, size_t n) {
-  const double sdd = sums[(size_t)blockIdx.y * 3], sdw = sums[(size_t)blockIdx.y * 3 + 1], sww = sums[(size_t)blockIdx.y * 3 + 2];
-  const double r = (double)norm_threshold;
-  const double c = (norm_threshold > 0.f && sdd > r * r) ? r / sqrt(sdd) : 1.0;
-  const double a = sww > 0.0 ? sdw / sww : 0.0;
-  const float c32 = (float)c, k32 = (float)((c * (1.0 - (double)eta)) * a);
-  const size_t base = (size_t)blockIdx.y * elems, c0 = (size_t)blockIdx.x * APG_CHUNK;
-  for (int rr = 0; rr < 4; ++rr) {
-    const size_t e = c0 + (size_t)rr * 1024 + (size_t)threadIdx.x * 4;
-    if (e >= elems) break;
-    const size_t i = base + e;
-    if (VEC == 4) {
-      const f32x4 vc = load_v4(v, v_bf16, i), db = *(const f32x4*)(M + i);
-      f32x4 o = *(const f32x4*)(x + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = apg_step1(o[j], vc[j], db[j], neg_sigma, c32, k32, neg_inv_sigma, ds);
-      if (BLEND) {
-        const f32x4 s = *(const f32x4*)(x0 + i), b = *(const f32x4*)(z + i), mm = *(const f32x4*)(m + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = blend1(o[j], s[j], b[j], mm[j], sigma_next, one_minus_sigma);
-      }
-      for (int p = 0; p < parts; ++p) *(f32x4*)(x + (size_t)p * n + i) = o;
-    } else {
-      const int cnt = elems - e < 4 ? (int)(elems - e) : 4;
-      for (int j = 0; j < cnt; ++j) {
-        float o = apg_step1(x[i + j], load_v1(v, v_bf16, i + j), M[i + j], neg_sigma, c32, k32, neg_inv_sigma, ds);
-        if (BLEND) o = blend1(o, x0[i + j], z[i + j], m[i + j], sigma_next, one_minus_sigma);
-        for (int p = 0; p < parts; ++p) x[(size_t)p * n + i + j] = o;
-      }
-    }
-  }
-}
-
 __global__ void convert_kernel(void* __restrict__ dst, int dst_bf16,const void* __restrict__ src, int src_bf16, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -1316,191 +1018,6 @@ extern "C" int lx_timestep_embed(const float* t, float* out, int B, int dim, voi
   const int n = B * dim / 2;
   hipLaunchKernelGGL(timestep_embed_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, out, B, dim);
   LX_LAUNCH_CHECK("lx_timestep_embed");
-  return LX_OK;
-}
-
-extern "C" int lx_euler_step(float* x, const void* v, int v_is_bf16, float dsigma, size_t n, void* stream) {
-  LX_CHECK_ARG(x && v, "lx_euler_step: NULL operand");
-  if (n == 0) return LX_OK;
-  const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-  hipLaunchKernelGGL(euler_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, n);
-  LX_LAUNCH_CHECK("lx_euler_step");
-  return LX_OK;
-}
-
-// [a, a + n) and [b, b + n) fp32 elements share an address
-static bool f32_ranges_overlap(const void* a, const void* b, size_t n) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = n * sizeof(float);
-  return pa < pb + bytes && pb < pa + bytes;
-}
-
-extern "C" int lx_scale_noise(float* out, const float* x0, const float* z, float sigma, size_t n, void* stream) {
-  LX_CHECK_ARG(out && x0 && z, "lx_scale_noise: NULL operand");
-  LX_CHECK_ARG(!f32_ranges_overlap(out, x0, n) && !f32_ranges_overlap(out, z, n), "lx_scale_noise: x0 and z may not alias out");
-  if (n == 0) return LX_OK;
-  const bool vec = (((uintptr_t)out | (uintptr_t)x0 | (uintptr_t)z) & 15) == 0;
-  const size_t items = vec ? (n + 3) / 4 : n;
-  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
-  const float oms = 1.0f - sigma;
-  if (vec) hipLaunchKernelGGL(scale_noise_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, x0, z, sigma, oms, n);
-  else hipLaunchKernelGGL(scale_noise_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, x0, z, sigma, oms, n);
-  LX_LAUNCH_CHECK("lx_scale_noise");
-  return LX_OK;
-}
-
-extern "C" int lx_euler_step_blend(float* x, const void* v, int v_is_bf16, float dsigma, const float* x0, const float* z, const float* m,
-                                   float sigma_next, size_t n, void* stream) {
-  LX_CHECK_ARG(x && v && x0 && z && m, "lx_euler_step_blend: NULL operand");
-  LX_CHECK_ARG(!f32_ranges_overlap(x, x0, n) && !f32_ranges_overlap(x, z, n) && !f32_ranges_overlap(x, m, n),
-               "lx_euler_step_blend: x0, z and m may not alias x (it is updated in place)");
-  if (n == 0) return LX_OK;
-  const bool vec = (((uintptr_t)x | (uintptr_t)v | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0;
-  const size_t items = vec ? (n + 3) / 4 : n;
-  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
-  const float oms = 1.0f - sigma_next;
-  if (vec) hipLaunchKernelGGL(euler_blend_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
-  else hipLaunchKernelGGL(euler_blend_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, v, v_is_bf16, dsigma, x0, z, m, sigma_next, oms, n);
-  LX_LAUNCH_CHECK("lx_euler_step_blend");
-  return LX_OK;
-}
-
-// [a, a + na) and [b, b + nb) bytes share an address
-static bool byte_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
-template <int VEC>
-static void launch_euler_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z, const float* m,
-                             float sigma_next, size_t n, hipStream_t stream) {
-  const size_t items = n / VEC;
-  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
-  const float oms = 1.0f - sigma_next;
-  if (m) hipLaunchKernelGGL((euler_cfg_kernel<VEC, true>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, oms, n);
-  else hipLaunchKernelGGL((euler_cfg_kernel<VEC, false>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, oms, n);
-}
-
-extern "C" int lx_euler_step_cfg(float* x, const void* v, int v_is_bf16, float dsigma, float scale, const float* x0, const float* z,
-                                 const float* m, float sigma_next, size_t n, void* stream) {
-  LX_CHECK_ARG(x && v, "lx_euler_step_cfg: NULL x or v");
-  LX_CHECK_ARG(n > 0, "lx_euler_step_cfg: n == 0");
-  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_cfg: x0, z and m go together (all NULL: no blend)");
-  uint32_t scale_bits;
-  __builtin_memcpy(&scale_bits, &scale, sizeof scale_bits);
-  LX_CHECK_ARG((scale_bits & 0x7f800000u) != 0x7f800000u, "lx_euler_step_cfg: scale is not finite");
-  const size_t xbytes = 2 * n * sizeof(float), hbytes = n * sizeof(float);
-  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, hbytes) && !byte_ranges_overlap(x, xbytes, z, hbytes) &&
-                      !byte_ranges_overlap(x, xbytes, m, hbytes)),
-               "lx_euler_step_cfg: x0, z and m may not alias x[0, 2n) (it is updated in place)");
-  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_cfg: v may not alias x[0, 2n)");
-  // both halves of every operand: x + n and v + n are aligned only where n % 4 == 0
-  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
-  const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 && ((uintptr_t)v & v_align) == 0;
-  if (vec) launch_euler_cfg<4>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
-  else launch_euler_cfg<1>(x, v, v_is_bf16, dsigma, scale, x0, z, m, sigma_next, n, (hipStream_t)stream);
-  LX_LAUNCH_CHECK("lx_euler_step_cfg");
-  return LX_OK;
-}
-
-template <int VEC>
-static void launch_euler_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
-                              const float* z, const float* m, float sigma_next, size_t n, hipStream_t stream) {
-  const size_t items = n / VEC;
-  const int grid = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
-  const float oms = 1.0f - sigma_next;
-  if (m) hipLaunchKernelGGL((euler_cfg3_kernel<VEC, true>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, oms, n);
-  else hipLaunchKernelGGL((euler_cfg3_kernel<VEC, false>), dim3(grid), dim3(256), 0, stream, x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, oms, n);
-}
-
-static bool f32_is_finite(float f) {
-  uint32_t bits;
-  __builtin_memcpy(&bits, &f, sizeof bits);
-  return (bits & 0x7f800000u) != 0x7f800000u;
-}
-
-extern "C" int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float dsigma, float scale_brain, float scale_text, const float* x0,
-                                  const float* z, const float* m, float sigma_next, size_t n, void* stream) {
-  LX_CHECK_ARG(x && v, "lx_euler_step_cfg3: NULL x or v");
-  LX_CHECK_ARG(n > 0, "lx_euler_step_cfg3: n == 0");
-  LX_CHECK_ARG(n <= SIZE_MAX / (3 * sizeof(float)), "lx_euler_step_cfg3: 3n elements do not fit an address");
-  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_cfg3: x0, z and m go together (all NULL: no blend)");
-  LX_CHECK_ARG(f32_is_finite(scale_brain) && f32_is_finite(scale_text), "lx_euler_step_cfg3: scale_brain or scale_text is not finite");
-  const size_t xbytes = 3 * n * sizeof(float), pbytes = n * sizeof(float);
-  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, pbytes) && !byte_ranges_overlap(x, xbytes, z, pbytes) &&
-                      !byte_ranges_overlap(x, xbytes, m, pbytes)),
-               "lx_euler_step_cfg3: x0, z and m may not alias x[0, 3n) (it is updated in place)");
-  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_cfg3: v may not alias x[0, 3n)");
-  // all three parts of every operand: x + n, x + 2n, v + n and v + 2n are aligned only where n % 4 == 0
-  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
-  const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 && ((uintptr_t)v & v_align) == 0;
-  if (vec) launch_euler_cfg3<4>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
-  else launch_euler_cfg3<1>(x, v, v_is_bf16, dsigma, scale_brain, scale_text, x0, z, m, sigma_next, n, (hipStream_t)stream);
-  LX_LAUNCH_CHECK("lx_euler_step_cfg3");
-  return LX_OK;
-}
-
-// chunks of one image; 0 where n_images x chunks x 3 doubles, or 3 parts of n_images x elems floats, do not fit an address
-static size_t apg_chunks(int n_images, size_t elems) {
-  if (n_images < 1 || n_images > 65535 || elems == 0) return 0;
-  if (elems > SIZE_MAX / (3 * sizeof(float)) / (size_t)n_images) return 0;
-  const size_t chunks = (elems + APG_CHUNK - 1) / APG_CHUNK;
-  return chunks <= 0x7fffffffu ? chunks : 0;
-}
-
-extern "C" size_t lx_apg_workspace_bytes(int n_images, size_t elems) {
-  return apg_chunks(n_images, elems) * (size_t)(n_images > 0 ? n_images : 0) * 3 * sizeof(double);
-}
-
-template <int VEC>
-static void launch_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float eta,
-                       float norm_threshold, float momentum, float* M, double* sums, double* partials, const float* x0, const float* z,
-                       const float* m, float sigma_next, int n_images, size_t elems, hipStream_t stream) {
-  const size_t n = (size_t)n_images * elems;
-  const int chunks = (int)apg_chunks(n_images, elems);
-  const dim3 grid(chunks, n_images);
-  const float neg_sigma = -sigma, neg_inv_sigma = -(1.0f / sigma), oms = 1.0f - sigma_next;
-  if (n_parts == 2) hipLaunchKernelGGL((apg_reduce_kernel<VEC, 2>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
-  else hipLaunchKernelGGL((apg_reduce_kernel<VEC, 3>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
-  hipLaunchKernelGGL(apg_total_kernel, dim3(n_images), dim3(64), 0, stream, (const double*)partials, chunks, sums);
-  if (m) hipLaunchKernelGGL((apg_step_kernel<VEC, true>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, x0, z, m, sigma_next, oms, elems, n);
-  else hipLaunchKernelGGL((apg_step_kernel<VEC, false>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, x0, z, m, sigma_next, oms, elems, n);
-}
-
-extern "C" int lx_euler_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
-                                 float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
-                                 size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images,
-                                 size_t elems, void* stream) {
-  LX_CHECK_ARG(x && v && M && sums && workspace, "lx_euler_step_apg: NULL x, v, M, sums or workspace");
-  LX_CHECK_ARG(n_parts == 2 || n_parts == 3, "lx_euler_step_apg: n_parts=%d must be 2 or 3", n_parts);
-  LX_CHECK_ARG(n_images >= 1 && elems > 0, "lx_euler_step_apg: n_images < 1 or elems == 0");
-  LX_CHECK_ARG(apg_chunks(n_images, elems) > 0, "lx_euler_step_apg: more than 65535 images, or the parts do not fit an address");
-  LX_CHECK_ARG(f32_is_finite(sigma) && sigma > 0.f, "lx_euler_step_apg: sigma must be finite and > 0");
-  LX_CHECK_ARG(f32_is_finite(scale_a) && (n_parts == 2 || f32_is_finite(scale_b)), "lx_euler_step_apg: a scale is not finite");
-  LX_CHECK_ARG(f32_is_finite(eta) && f32_is_finite(norm_threshold) && f32_is_finite(momentum),
-               "lx_euler_step_apg: eta, norm_threshold or momentum is not finite");
-  LX_CHECK_ARG(eta >= 0.f && eta <= 1.f, "lx_euler_step_apg: eta must lie in [0, 1]");
-  LX_CHECK_ARG(norm_threshold >= 0.f, "lx_euler_step_apg: norm_threshold must be >= 0");
-  LX_CHECK_ARG(momentum > -1.f && momentum < 1.f, "lx_euler_step_apg: |momentum| must be < 1");
-  LX_CHECK_ARG((x0 && z && m) || (!x0 && !z && !m), "lx_euler_step_apg: x0, z and m go together (all NULL: no blend)");
-  LX_CHECK_ARG(workspace_bytes >= lx_apg_workspace_bytes(n_images, elems), "lx_euler_step_apg: the workspace is smaller than lx_apg_workspace_bytes");
-  LX_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)sums) & 7) == 0, "lx_euler_step_apg: the workspace and sums must be 8-byte aligned");
-  const size_t n = (size_t)n_images * elems, xbytes = (size_t)n_parts * n * sizeof(float), pbytes = n * sizeof(float);
-  const size_t vbytes = (size_t)n_parts * n * (v_is_bf16 ? 2 : 4);
-  LX_CHECK_ARG(!byte_ranges_overlap(x, xbytes, M, pbytes) && !byte_ranges_overlap(x, xbytes, sums, (size_t)n_images * 3 * sizeof(double)) &&
-               !byte_ranges_overlap(x, xbytes, workspace, workspace_bytes),
-               "lx_euler_step_apg: M, sums and the workspace may not overlap x[0, n_parts n)");
-  LX_CHECK_ARG(!m || (!byte_ranges_overlap(x, xbytes, x0, pbytes) && !byte_ranges_overlap(x, xbytes, z, pbytes) &&
-                      !byte_ranges_overlap(x, xbytes, m, pbytes)),
-               "lx_euler_step_apg: x0, z and m may not alias x[0, n_parts n) (it is updated in place)");
-  LX_CHECK_ARG(v_is_bf16 || !byte_ranges_overlap(x, xbytes, v, xbytes), "lx_euler_step_apg: v may not alias x[0, n_parts n)");
-  LX_CHECK_ARG(!byte_ranges_overlap(v, vbytes, M, pbytes), "lx_euler_step_apg: M may not overlap v (it is written while v is read)");
-  // every part and every image start: x + p n + b elems and the like are aligned only where elems % 4 == 0
-  const uintptr_t v_align = v_is_bf16 ? 7 : 15;
-  const bool vec = elems % 4 == 0 && (((uintptr_t)x | (uintptr_t)M | (uintptr_t)x0 | (uintptr_t)z | (uintptr_t)m) & 15) == 0 &&
-                   ((uintptr_t)v & v_align) == 0;
-  if (vec) launch_apg<4>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, x0, z, m, sigma_next, n_images, elems, (hipStream_t)stream);
-  else launch_apg<1>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, x0, z, m, sigma_next, n_images, elems, (hipStream_t)stream);
-  LX_LAUNCH_CHECK("lx_euler_step_apg");
   return LX_OK;
 }
 

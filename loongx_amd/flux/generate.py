@@ -131,13 +131,25 @@ def prepare_brain_cfg_params(brain_guidance_scale: float = 1.0, **kwargs):
     return brain_guidance_scale
 
 
+def _finite_number(name, value, at_least=None) -> None:
+    """a keyword that takes a number: anything but a finite int or float (a bool is neither), or one below `at_least`, is a ValueError"""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value) or \
+            (at_least is not None and float(value) < at_least):
+        raise ValueError(f"{name} must be a finite number{'' if at_least is None else f' >= {at_least}'}, got {value!r}")
+
+
+def _n_prompts(prompt, prompt_embeds):
+    """how many prompts the call has: from `prompt`, else from the embeddings' batch; None where neither says"""
+    return 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
+        prompt_embeds.shape[0] if prompt_embeds is not None else None
+
+
 def _brain_cfg(brain_guidance_scale) -> bool:
     """generate()'s brain_guidance_scale -> whether guidance along the brain signal is asked for (s_b > 1; whether it is ON is known only
     after the brain section: the signals have to change an embedding). A refusal is a ValueError on the host, before anything of the
     pipeline is touched; a scale in [0, 1) is one RuntimeWarning and the plain call, as true_cfg_scale <= 1 is."""
     s = brain_guidance_scale
-    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s) or float(s) < 0:
-        raise ValueError(f"brain_guidance_scale must be a finite number >= 0, got {s!r}")
+    _finite_number("brain_guidance_scale", s, at_least=0)
     if float(s) < 1:
         warnings.warn(f"brain_guidance_scale={s} (< 1): guidance is off, running the plain call", RuntimeWarning, stacklevel=3)
     return float(s) > 1
@@ -156,8 +168,7 @@ def _apg(apg_eta, apg_norm_threshold, apg_momentum):
     guidance is asked for (one of them differs from its default), else None; whether it is ON is known only once the branches are (it needs
     a guided call). A refusal is a ValueError on the host, before anything of the pipeline is touched."""
     for name, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
-            raise ValueError(f"{name} must be a finite number, got {value!r}")
+        _finite_number(name, value)
     eta, norm_threshold, momentum = float(apg_eta), float(apg_norm_threshold), float(apg_momentum)
     if not 0.0 <= eta <= 1.0:
         raise ValueError(f"apg_eta must lie in [0, 1] (the weight of the update's part along the prediction), got {apg_eta!r}")
@@ -180,14 +191,12 @@ def _true_cfg(negative_prompt, negative_prompt_embeds, negative_pooled_prompt_em
     """generate()'s true-CFG arguments -> whether the call is guided (diffusers' rule: true_cfg_scale > 1 and a negative prompt given). Every
     refusal is a ValueError on the host, before anything of the pipeline is touched; half a request is one RuntimeWarning and the plain call."""
     s = true_cfg_scale
-    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s):
-        raise ValueError(f"true_cfg_scale must be a finite number, got {s!r}")
+    _finite_number("true_cfg_scale", s)
     if negative_prompt is not None and negative_prompt_embeds is not None:
         raise ValueError("Cannot forward both `negative_prompt` and `negative_prompt_embeds`.")
     if (negative_prompt_embeds is None) != (negative_pooled_prompt_embeds is None):
         raise ValueError("`negative_prompt_embeds` and `negative_pooled_prompt_embeds` have to be passed together.")
-    n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
-        prompt_embeds.shape[0] if prompt_embeds is not None else None
+    n_prompts = _n_prompts(prompt, prompt_embeds)
     if negative_prompt is not None:
         if not isinstance(negative_prompt, (str, list)):
             raise ValueError(f"`negative_prompt` has to be of type `str` or `list` but is {type(negative_prompt)}")
@@ -329,8 +338,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         warnings.warn(_APG_UNGUIDED, RuntimeWarning, stacklevel=2)
     step_cache_config(model_config)          # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
-        n_prompts = 1 if isinstance(prompt, str) else len(prompt) if isinstance(prompt, list) else \
-            prompt_embeds.shape[0] if prompt_embeds is not None else None
+        n_prompts = _n_prompts(prompt, prompt_embeds)
         image_latents, inpaint_mask = _inpaint_source(
             pipeline, image, image_latents, mask_image, latent_mask, strength, num_inference_steps,
             latents.shape[0] if latents is not None else None if n_prompts is None else n_prompts * num_images_per_prompt,
@@ -347,12 +355,7 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
                       callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
     self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
-    if prompt is not None and isinstance(prompt, str):
-        batch_size = 1
-    elif prompt is not None and isinstance(prompt, list):
-        batch_size = len(prompt)
-    else:
-        batch_size = prompt_embeds.shape[0]
+    batch_size = _n_prompts(prompt, prompt_embeds)
     device = self._execution_device
     lora_scale = self.joint_attention_kwargs.get("scale", None) if self.joint_attention_kwargs is not None else None
     prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(

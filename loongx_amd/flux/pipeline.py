@@ -128,28 +128,24 @@ class FlowMatchEulerDiscreteScheduler:
             raise ValueError("step(apg=...): adaptive projected guidance acts on a guidance update; pass true_cfg_scale and/or "
                              "brain_guidance_scale with it")
         i = self._step_index
-        ds = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i]))
+        ds, sigma_next = float(np.float32(self._sig_host[i + 1]) - np.float32(self._sig_host[i])), float(self._sig_host[i + 1])
         x = sample.to(torch.float32).clone() if (sample.dtype != torch.float32 or not sample.is_contiguous()) else sample.clone()
         v = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
         half = tuple(x.shape)
         if brain_guidance_scale is not None and not float(brain_guidance_scale) > 1:
             raise ValueError(f"step(brain_guidance_scale={brain_guidance_scale}): must be > 1; without brain guidance pass None and the "
                              "batch without its text-only part")
-        if brain_guidance_scale is not None and true_cfg_scale is not None:
-            if x.dim() < 1 or x.shape[0] % 3 or x.shape[0] == 0 or v.shape != x.shape:
-                raise ValueError(f"step(true_cfg_scale=..., brain_guidance_scale=...): sample {tuple(x.shape)} and model_output "
-                                 f"{tuple(v.shape)} must have one shape with a leading dimension that is a multiple of 3, [full; text; negative]")
-            half = (x.shape[0] // 3,) + tuple(x.shape[1:])
-        elif brain_guidance_scale is not None:
-            if x.dim() < 1 or x.shape[0] % 2 or x.shape[0] == 0 or v.shape != x.shape:
-                raise ValueError(f"step(brain_guidance_scale=...): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one "
-                                 "shape with an even leading dimension, [full; text]")
-            half = (x.shape[0] // 2,) + tuple(x.shape[1:])
-        elif true_cfg_scale is not None:
-            if x.dim() < 1 or x.shape[0] % 2 or x.shape[0] == 0 or v.shape != x.shape:
-                raise ValueError(f"step(true_cfg_scale=...): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one shape "
-                                 "with an even leading dimension, [positive; negative]")
-            half = (x.shape[0] // 2,) + tuple(x.shape[1:])
+        # the scales in the order the kernels take them; with them the batch has one more part, laid out as `layout` says
+        scales = tuple(float(s) for s in (brain_guidance_scale, true_cfg_scale) if s is not None)
+        parts = len(scales) + 1
+        if parts > 1:
+            keywords = ", ".join(k for k, s in (("true_cfg_scale=...", true_cfg_scale), ("brain_guidance_scale=...", brain_guidance_scale))
+                                 if s is not None)
+            layout = "[full; text; negative]" if parts == 3 else "[full; text]" if brain_guidance_scale is not None else "[positive; negative]"
+            if x.dim() < 1 or x.shape[0] % parts or x.shape[0] == 0 or v.shape != x.shape:
+                raise ValueError(f"step({keywords}): sample {tuple(x.shape)} and model_output {tuple(v.shape)} must have one shape with "
+                                 f"{'a leading dimension that is a multiple of 3' if parts == 3 else 'an even leading dimension'}, {layout}")
+            half = (x.shape[0] // parts,) + tuple(x.shape[1:])
         if inpaint is not None:
             x0, z, m = inpaint
             if not (tuple(x0.shape) == tuple(z.shape) == tuple(m.shape) == half):
@@ -159,20 +155,17 @@ class FlowMatchEulerDiscreteScheduler:
             if tuple(apg.M.shape) != half or apg.M.dtype != torch.float32 or apg.sums.shape[1] != half[0] or not apg.step < apg.sums.shape[0]:
                 raise ValueError(f"step(apg=...): the state (M {tuple(apg.M.shape)}, sums {tuple(apg.sums.shape)}, step {apg.step}) was not "
                                  f"made for parts of shape {half} or has run out of steps")
-            scales = tuple(float(s) for s in (brain_guidance_scale, true_cfg_scale) if s is not None)
             ops.euler_step_apg(x, v.contiguous(), float(self._sig_host[i]), ds, scales, apg.eta, apg.norm_threshold, apg.momentum, apg.M,
-                               apg.sums[apg.step], apg.workspace, inpaint, float(self._sig_host[i + 1]))
+                               apg.sums[apg.step], apg.workspace, inpaint, sigma_next)
             apg.step += 1
-        elif brain_guidance_scale is not None and true_cfg_scale is not None:
-            ops.euler_step_cfg3(x, v.contiguous(), ds, float(brain_guidance_scale), float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
-        elif brain_guidance_scale is not None:
-            ops.euler_step_cfg(x, v.contiguous(), ds, float(brain_guidance_scale), inpaint, float(self._sig_host[i + 1]))
-        elif true_cfg_scale is not None:
-            ops.euler_step_cfg(x, v.contiguous(), ds, float(true_cfg_scale), inpaint, float(self._sig_host[i + 1]))
+        elif parts == 3:
+            ops.euler_step_cfg3(x, v.contiguous(), ds, *scales, inpaint, sigma_next)
+        elif parts == 2:
+            ops.euler_step_cfg(x, v.contiguous(), ds, *scales, inpaint, sigma_next)
         elif inpaint is None:
             ops.euler_step(x, v.contiguous(), ds)
         else:
-            ops.euler_step_blend(x, v.contiguous(), ds, x0, z, m, float(self._sig_host[i + 1]))
+            ops.euler_step_blend(x, v.contiguous(), ds, x0, z, m, sigma_next)
         self._step_index += 1
         return (x.to(model_output.dtype),)
 

@@ -617,37 +617,38 @@ def scale_noise(x0: torch.Tensor, z: torch.Tensor, sigma: float, out: Optional[t
     return out
 
 
+def _step_operands(name: str, x, v, parts: int, inpaint, held: str, piece: str, also=()):
+    """What the guided and blended steps check and marshal alike: x fp32 and v fp32 or bf16 hold `parts` parts of n elements (`held`: the
+    refusal's wording), inpaint = (x0, z, m) or None is fp32 with n elements each (`piece`: the same), and everything, the entry's
+    further tensors `also` included, is contiguous. -> (n, whether v is bf16, the addresses of x0, z and m: None, C's NULL, without inpaint)"""
+    _req(x, torch.float32, "x")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    n = x.numel() // parts
+    assert x.numel() == parts * n and v.numel() == parts * n, f"{name}: {held}"
+    x0, z, m = (None, None, None) if inpaint is None else inpaint
+    if inpaint is not None:
+        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
+        assert x0.numel() == n and z.numel() == n and m.numel() == n, f"{name}: {piece}"
+    assert all(t.is_contiguous() for t in (x, v, x0, z, m) + tuple(also) if t is not None), f"{name}: contiguous operands"
+    return n, int(v.dtype == torch.bfloat16), (_p(x0), _p(z), _p(m))
+
+
 def euler_step_blend(x: torch.Tensor, v: torch.Tensor, dsigma: float, x0: torch.Tensor, z: torch.Tensor, m: torch.Tensor, sigma_next: float) -> None:
     """x <- m*(x + dsigma*v) + (1 - m)*(sigma_next*z + (1 - sigma_next)*x0) in place (lx_euler_step_blend): x, x0, z, m fp32, v fp32 or
     bf16, all contiguous with x's element count."""
-    _req(x, torch.float32, "x"); _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
-    if v.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
-    n = x.numel()
-    assert v.numel() == n and x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_blend: one element count for all operands"
-    assert all(t.is_contiguous() for t in (x, v, x0, z, m)), "euler_step_blend: contiguous operands"
-    check(lib.lx_euler_step_blend(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), x0.data_ptr(), z.data_ptr(), m.data_ptr(),
-                                  float(sigma_next), n, _stream()), "lx_euler_step_blend")
+    n, bf16, blend = _step_operands("euler_step_blend", x, v, 1, (x0, z, m), *("one element count for all operands",) * 2)
+    check(lib.lx_euler_step_blend(x.data_ptr(), v.data_ptr(), bf16, float(dsigma), *blend, float(sigma_next), n, _stream()), "lx_euler_step_blend")
 
 
 def euler_step_cfg(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale: float, inpaint=None, sigma_next: float = 0.0) -> None:
     """The step under true classifier-free guidance, in place (lx_euler_step_cfg): x fp32 and v fp32 or bf16 hold [positive; negative]
     halves of n elements each; both halves of x become x[:n] + dsigma * (vn + scale * (vp - vn)). inpaint = (x0, z, m), fp32 with n
     elements each: blended with the source at sigma_next as euler_step_blend does, once, for both halves. All contiguous."""
-    _req(x, torch.float32, "x")
-    if v.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
-    n = x.numel() // 2
-    assert x.numel() == 2 * n and v.numel() == 2 * n, "euler_step_cfg: x and v hold two halves of one element count"
-    x0 = z = m = None
-    if inpaint is not None:
-        x0, z, m = inpaint
-        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
-        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_cfg: x0, z and m have the element count of one half"
-    assert all(t.is_contiguous() for t in (x, v, x0, z, m) if t is not None), "euler_step_cfg: contiguous operands"
-    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-    check(lib.lx_euler_step_cfg(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), float(scale), ptr(x0), ptr(z), ptr(m),
-                                float(sigma_next), n, _stream()), "lx_euler_step_cfg")
+    n, bf16, blend = _step_operands("euler_step_cfg", x, v, 2, inpaint, "x and v hold two halves of one element count",
+                                    "x0, z and m have the element count of one half")
+    check(lib.lx_euler_step_cfg(x.data_ptr(), v.data_ptr(), bf16, float(dsigma), float(scale), *blend, float(sigma_next), n, _stream()),
+          "lx_euler_step_cfg")
 
 
 def euler_step_cfg3(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale_brain: float, scale_text: float, inpaint=None,
@@ -656,20 +657,10 @@ def euler_step_cfg3(x: torch.Tensor, v: torch.Tensor, dsigma: float, scale_brain
     [full; text; negative] parts of n elements each; all three parts of x become x[:n] + dsigma * (vN + scale_text * (gb - vN)) with
     gb = vT + scale_brain * (vF - vT). inpaint = (x0, z, m), fp32 with n elements each: blended with the source at sigma_next as
     euler_step_blend does, once, for all parts. All contiguous."""
-    _req(x, torch.float32, "x")
-    if v.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
-    n = x.numel() // 3
-    assert x.numel() == 3 * n and v.numel() == 3 * n, "euler_step_cfg3: x and v hold three parts of one element count"
-    x0 = z = m = None
-    if inpaint is not None:
-        x0, z, m = inpaint
-        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
-        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_cfg3: x0, z and m have the element count of one part"
-    assert all(t.is_contiguous() for t in (x, v, x0, z, m) if t is not None), "euler_step_cfg3: contiguous operands"
-    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-    check(lib.lx_euler_step_cfg3(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(dsigma), float(scale_brain), float(scale_text),
-                                 ptr(x0), ptr(z), ptr(m), float(sigma_next), n, _stream()), "lx_euler_step_cfg3")
+    n, bf16, blend = _step_operands("euler_step_cfg3", x, v, 3, inpaint, "x and v hold three parts of one element count",
+                                    "x0, z and m have the element count of one part")
+    check(lib.lx_euler_step_cfg3(x.data_ptr(), v.data_ptr(), bf16, float(dsigma), float(scale_brain), float(scale_text), *blend,
+                                 float(sigma_next), n, _stream()), "lx_euler_step_cfg3")
 
 
 def apg_workspace_bytes(n_images: int, elems: int) -> int:
@@ -685,31 +676,21 @@ def euler_step_apg(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: float
     sum w^2 per image; its first dimension says how many images a part holds), workspace a contiguous buffer of at least
     apg_workspace_bytes(n_images, elems) bytes. inpaint = (x0, z, m), fp32 with one part's element count. All contiguous; nothing is
     synchronised."""
-    _req(x, torch.float32, "x")
-    if v.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
     scales = tuple(float(s) for s in scales)
     assert len(scales) in (1, 2), "euler_step_apg: scales is (scale,) for two parts or (scale_brain, scale_text) for three"
     parts = len(scales) + 1
-    n = x.numel() // parts
-    assert x.numel() == parts * n and v.numel() == parts * n, f"euler_step_apg: x and v hold {parts} parts of one element count"
+    n, bf16, blend = _step_operands("euler_step_apg", x, v, parts, inpaint, f"x and v hold {parts} parts of one element count",
+                                    "x0, z and m have the element count of one part", also=(M, sums, workspace))
     _req(M, torch.float32, "M")
     _req(sums, torch.float64, "sums")
     assert M.numel() == n, "euler_step_apg: M has the element count of one part"
     assert sums.dim() == 2 and sums.shape[1] == 3 and sums.shape[0] >= 1, "euler_step_apg: sums is [n_images, 3]"
     n_images = sums.shape[0]
     assert n % n_images == 0, "euler_step_apg: a part holds n_images images of one element count"
-    x0 = z = m = None
-    if inpaint is not None:
-        x0, z, m = inpaint
-        _req(x0, torch.float32, "x0"); _req(z, torch.float32, "z"); _req(m, torch.float32, "m")
-        assert x0.numel() == n and z.numel() == n and m.numel() == n, "euler_step_apg: x0, z and m have the element count of one part"
-    assert all(t.is_contiguous() for t in (x, v, M, sums, workspace, x0, z, m) if t is not None), "euler_step_apg: contiguous operands"
-    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-    check(lib.lx_euler_step_apg(x.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), parts, scales[0], scales[-1], float(sigma),
-                                float(dsigma), float(eta), float(norm_threshold), float(momentum), M.data_ptr(), sums.data_ptr(),
-                                workspace.data_ptr(), workspace.numel() * workspace.element_size(), ptr(x0), ptr(z), ptr(m),
-                                float(sigma_next), n_images, n // n_images, _stream()), "lx_euler_step_apg")
+    check(lib.lx_euler_step_apg(x.data_ptr(), v.data_ptr(), bf16, parts, scales[0], scales[-1], float(sigma), float(dsigma), float(eta),
+                                float(norm_threshold), float(momentum), M.data_ptr(), sums.data_ptr(), workspace.data_ptr(),
+                                workspace.numel() * workspace.element_size(), *blend, float(sigma_next), n_images, n // n_images, _stream()),
+          "lx_euler_step_apg")
 
 
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:

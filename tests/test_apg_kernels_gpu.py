@@ -1,4 +1,4 @@
-"""lx_euler_step_apg (csrc/rowops.hip) against a float64 numpy restatement of the rule in include/lx.h: the guided step under adaptive
+"""lx_euler_step_apg (csrc/step.hip) against a float64 numpy restatement of the rule in include/lx.h: the guided step under adaptive
 projected guidance, a per-image reduction over the branch velocities and a fused project, clamp, Euler-step and blend.
 
 x and v hold 2 or 3 parts of n = n_images * elems elements. Pass 1 leaves Db = (-sigma)(g0 - vc) [+ momentum M] in M and, per image, the

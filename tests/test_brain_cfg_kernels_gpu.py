@@ -1,4 +1,4 @@
-"""lx_euler_step_cfg3 (csrc/rowops.hip) against float64: the step of an image under brain guidance nested in true CFG, three branches in one
+"""lx_euler_step_cfg3 (csrc/step.hip) against float64: the step of an image under brain guidance nested in true CFG, three branches in one
 launch.
 
 x and v hold [full; text; negative] parts of n elements. The contract of include/lx.h is an operation order -- db = vF - vT rounded on its

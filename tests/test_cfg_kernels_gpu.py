@@ -1,4 +1,4 @@
-"""lx_euler_step_cfg (csrc/rowops.hip) against float64: the step of a true-CFG image, both branches in one launch.
+"""lx_euler_step_cfg (csrc/step.hip) against float64: the step of a true-CFG image, both branches in one launch.
 
 x and v hold [positive; negative] halves of n elements. The contract of include/lx.h is an operation order -- d = vp - vn rounded on its own;
 g = fmaf(scale, d, vn); e = fmaf(dsigma, g, x[i]); then lx_euler_step_blend's blend of e where (x0, z, m) are given; x[i] = x[n + i] = the

@@ -1,4 +1,4 @@
-"""lx_scale_noise and lx_euler_step_blend (csrc/rowops.hip) against float64: the start of an img2img trajectory and the inpaint step.
+"""lx_scale_noise and lx_euler_step_blend (csrc/step.hip) against float64: the start of an img2img trajectory and the inpaint step.
 
 The contract of include/lx.h is an operation order -- e = fmaf(ds, v, x); r = fmaf(s, z, (1 - s) * x0); x = fmaf(m, e, (1 - m) * r), the two
 products and the two differences rounded on their own -- and the tests hold the kernels to it three ways:

@@ -20,7 +20,8 @@ def kernels(path):
         start = next(i for i, ln in enumerate(lines) if ln.split(";")[0].strip() == name + ":")
         body = []
         for ln in lines[start + 1:]:
-            ln = ln.split(";")[0].strip()
+            # (local labels carry the kernel's ordinal in its file, .LBB12_3: dropped, so that kernels moving out of a file do not rename them)
+            ln = re.sub(r"\.L([A-Za-z]+)\d+_", r".L\1_", ln.split(";")[0].strip())
             if ln:
                 body.append(ln)
             if ln == "s_endpgm":

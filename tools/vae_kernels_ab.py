@@ -13,13 +13,14 @@ full FLUX.1 VAE shape, batch 1, on bf16, fp16 and precise operands -- taken from
 and replayed on seeded inputs of the traced sizes. Then the whole decode and encode per format, digest and times alike.
 
 compare: exits non-zero unless (a) every digest is the same in all files and (b) for every row this tree's median is at most the parent's
-median plus the parent's own (max - min), both over the counted launches of all of an arm's runs."""
-import hashlib
+median plus the parent's own (max - min), both over the counted launches of all of an arm's runs (tools/kernels_ab.py)."""
 import os
-import statistics
 import sys
 
-ROUNDS = 9
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernels_ab  # noqa: E402
+from kernels_ab import counted, row  # noqa: E402
+
 NAN16 = 0x7FC0
 VAE_ENTRIES = ("lx_groupnorm_silu", "lx_groupnorm_silu_f16", "lx_groupnorm_silu_split", "lx_im2col3x3", "lx_im2col3x3_split", "lx_softmax_rows",
                "lx_softmax_rows_valid", "lx_softmax_rows_f16", "lx_softmax_rows_split", "lx_convert_f16")
@@ -136,23 +137,6 @@ def run():
         fn = getattr(lib, name)
         return (lambda: ops.check(fn(*args, ops._stream()), name)), y, keep
 
-    def counted(call):
-        call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(ROUNDS):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            out = call()
-            e.record()
-            torch.cuda.synchronize()
-            ms.append(s.elapsed_time(e))
-        return out, ms
-
-    def row(key, t, ms):
-        digest = hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
-        print("\t".join(("case", key, digest, " ".join(f"{v:.4f}" for v in ms))), flush=True)
-
     print(f"# tools/vae_kernels_ab.py run on {torch.cuda.get_device_name(0)}, library {_lib.LIB_PATH}")
     cases, seen, whole = [], set(), []
     with torch.no_grad():
@@ -177,45 +161,5 @@ def run():
             row(what, out, ms)
 
 
-def read(paths):
-    """{case: (set of digests, pooled times)} over an arm's files, in the first file's order"""
-    rows = {}
-    for p in paths:
-        for line in open(p):
-            if line.startswith("case\t"):
-                _, key, digest, ms = line.rstrip("\n").split("\t")
-                d, t = rows.setdefault(key, (set(), []))
-                d.add(digest)
-                t += [float(v) for v in ms.split()]
-    return rows
-
-
-def compare(argv):
-    parent, here = read(argv[argv.index("--parent") + 1:argv.index("--here")]), read(argv[argv.index("--here") + 1:])
-    n_runs = len(argv) - argv.index("--here") - 1
-    print(f"# {len(here)} rows; per arm {n_runs} runs of {ROUNDS} counted launches after one warm-up each, processes alternating; ms: median (min .. max)")
-    differ = missed = 0
-    if set(parent) != set(here):
-        differ += 1
-        print(f"DIFFERENT case lists: only in the parent {sorted(set(parent) - set(here))}, only here {sorted(set(here) - set(parent))}")
-    for key, (dh, th) in here.items():
-        dp, tp = parent.get(key, (set(), [0.0]))
-        same = len(dh) == 1 and dh == dp
-        bound = statistics.median(tp) + (max(tp) - min(tp))
-        ok = statistics.median(th) <= bound
-        differ += not same
-        missed += not ok
-        print(f"{'same bits' if same else 'DIFFERENT'} {'within' if ok else 'MISSED'} {sorted(dh)[0][:12]}  here {statistics.median(th):8.4f} ({min(th):8.4f} .. {max(th):8.4f})  "
-              f"parent {statistics.median(tp):8.4f} ({min(tp):8.4f} .. {max(tp):8.4f})  bound {bound:8.4f}  {key}")
-    print(f"# (a) bits: {len(here) - differ} of {len(here)} rows equal in every file; (b) time: {len(here) - missed} of {len(here)} rows within their bound")
-    if differ or missed:
-        sys.exit(f"{differ} row(s) with different bits, {missed} timing row(s) beyond their bound")
-
-
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "run":
-        run()
-    elif len(sys.argv) >= 6 and sys.argv[1] == "compare" and "--parent" in sys.argv and "--here" in sys.argv:
-        compare(sys.argv)
-    else:
-        sys.exit(__doc__)
+    kernels_ab.main(run, __doc__)
