@@ -634,6 +634,45 @@ int lx_euler_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float
 /* bytes of lx_euler_step_apg's workspace (3 doubles per chunk of 4096 elements per image); 0 for n_images < 1 or > 65535, elems == 0, or
  * sizes that do not fit an address */
 size_t lx_apg_workspace_bytes(int n_images, size_t elems);
+/* One step of the second-order multistep solver DPM-Solver++(2M) on the flow's sigmas (generate's solver="dpmpp_2m"; diffusers'
+ * DPMSolverMultistepScheduler(use_flow_sigmas=True)), written as the Euler step plus one correction: with the flow x = (1 - sigma) x0 +
+ * sigma eps, the velocity g = eps - x0, the denoised prediction d = x - sigma g and lambda = ln((1 - sigma) / sigma), diffusers' update is
+ *   x' = x + dsigma g + c (d - d_prev),   c = (1 - sigma_next / sigma) (lambda_next - lambda) / (2 (lambda - lambda_prev))
+ * exactly. c is formed by the caller (float64, rounded once to fp32) and is 0 where the step is first order: no d_prev yet, sigma_next == 0,
+ * or sigma_prev >= 1. n_parts = 1: x and v are [n] as lx_euler_step's (scale_a, scale_b ignored). n_parts = 2: [2n] laid out as
+ * lx_euler_step_cfg's, scale_a is its scale. n_parts = 3: [3n] as lx_euler_step_cfg3's, (scale_a, scale_b) = (scale_brain, scale_text).
+ * sigma is the current sigma (> 0); dsigma, x0, z, m and sigma_next as in the sibling steps. D is fp32 [n], the previous step's denoised
+ * prediction, updated in place. Per element i < n, in this order:
+ *   g = v (n_parts 1), lx_euler_step_cfg's g (2) or lx_euler_step_cfg3's g (3), the same operations in the same order
+ *   e = fmaf(dsigma, g, x[i])          -- lx_euler_step on g
+ *   d = fmaf(-sigma, g, x[i])          -- the denoised prediction
+ *   o = c == 0 ? e : fmaf(c, d - D[i], e)          -- the difference rounded on its own; D is NOT read when c == 0
+ *   D[i] = d                           -- always written
+ *   r = o, or lx_euler_step_blend's three operations on o where (x0, z, m) are given, bit-identical given o
+ *   x[i] = x[n + i] (= x[2n + i]) = r  -- only part 0 of x is read
+ * So c == 0 is lx_euler_step / lx_euler_step_blend / lx_euler_step_cfg / lx_euler_step_cfg3 of that part count in every bit of x, whatever
+ * D held (a NaN included), and D leaves finite for finite inputs. m == 0 keeps the source as in lx_euler_step_blend's contract. With
+ * G, E = x + dsigma G, Dx = x - sigma G and O = E + c (Dx - D_prev) exact, dg a bound on |g - G| (0 for one fp32 part) and u = 2^-24:
+ *   |d - Dx| <= sigma dg + u |Dx|,   |o - O| <= |dsigma| dg + u |E| + |c| (sigma dg + u |Dx| + u |Dx - D_prev|) + u |O|
+ * to first order (the two fmas on E and Dx, the rounded difference, the fma on O), then the blend's own roundings. 16-byte accesses (8 for
+ * bf16 v) only when every part is aligned -- aligned x, v, D, x0, z, m, and n % 4 == 0 where n_parts > 1; every other call goes element by
+ * element, same bits. Each work item reads, then writes, only its own elements of D. Plain vector stores, no atomics.
+ * LX_ERR_INVALID before any launch: NULL x, v or D; n_parts outside 1..3; n == 0 (or 3n floats past the address space); sigma not finite
+ * or <= 0; c, or a scale the part count uses, not finite; a partly NULL (x0, z, m); x0, z or m overlapping x[0, n_parts n); fp32 v
+ * overlapping x; D overlapping x[0, n_parts n), v (fp32 or bf16), x0, z or m. */
+int lx_dpmpp2m_step(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float c,
+                    float* D, const float* x0, const float* z, const float* m, float sigma_next, size_t n, void* stream);
+/* lx_dpmpp2m_step under adaptive projected guidance: lx_euler_step_apg, its passes, operands and refusals unchanged, with the correction
+ * applied around the PROJECTED velocity g = fmaf(-inv_sigma, u, vc) of its pass 2:
+ *   e = fmaf(dsigma, g, x[i]);  d = fmaf(-sigma, g, x[i]);  o = c == 0 ? e : fmaf(c, d - D[i], e);  D[i] = d;  then the blend on o.
+ * D is fp32 [n] (one part: n_images * elems). c == 0 does not read D and is lx_euler_step_apg in every bit of x, M and sums. The error of o
+ * is lx_dpmpp2m_step's with dg = lx_euler_step_apg's |g - G|. D joins the operands that must be 16-byte aligned for the 16-byte path.
+ * LX_ERR_INVALID before any launch: lx_euler_step_apg's refusals; NULL D; c not finite; D overlapping x[0, n_parts n), v, x0, z, m, M, sums
+ * or the workspace. */
+int lx_dpmpp2m_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float c,
+                        float* D, float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
+                        size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images, size_t elems,
+                        void* stream);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

@@ -115,11 +115,13 @@ def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
 
 
 def cfg_kwargs(true_cfg_scale=None, negative_prompt=None, brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None,
-               apg_momentum=None):
+               apg_momentum=None, solver=None):
     """--true_cfg_scale / --negative_prompt -> generate()'s true-CFG keywords (an addition; diffusers' FluxPipeline), --brain_guidance_scale ->
-    its guidance along the brain signal, --apg_eta / --apg_norm_threshold / --apg_momentum -> its adaptive projected guidance, each only
-    when given."""
+    its guidance along the brain signal, --apg_eta / --apg_norm_threshold / --apg_momentum -> its adaptive projected guidance, --solver ->
+    its sampler, each only when given."""
     kw = {}
+    if solver is not None:
+        kw["solver"] = solver
     for name, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
         if value is not None:
             kw[name] = value
@@ -156,9 +158,9 @@ def load_captions(caption_path):
 
 def process_image_batch(rank, world_size, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta,
                         target_size, seed, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                        brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None):
+                        brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None):
     """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image; true_cfg_scale /
-    negative_prompt / brain_guidance_scale / apg_*: cfg_kwargs, the same for every image."""
+    negative_prompt / brain_guidance_scale / apg_* / solver: cfg_kwargs, the same for every image."""
     from PIL import Image
     from loongx_amd.dist import shard_range
     start_idx, end_idx = shard_range(len(image_files), rank, world_size)
@@ -170,7 +172,7 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
                                             target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device),
                                             **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None),
                                             **cfg_kwargs(true_cfg_scale, negative_prompt, brain_guidance_scale, apg_eta, apg_norm_threshold,
-                                                         apg_momentum))
+                                                         apg_momentum, solver))
         result_img.save(os.path.join(output_dir, img_file))
         if rank == 0 and (idx - start_idx) % 10 == 0:
             print(f"Process {rank}: Completed {idx - start_idx}/{end_idx - start_idx} images")
@@ -178,7 +180,7 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
 
 def batch_inference(model, input_dir, output_dir, caption_path=None, condition_type="SEED", target_size=512, position_delta=[0, -32],
                     seed=42, brain_data_path=None, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                    brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None):
+                    brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None):
     """inference.py:255-339: all captioned images of a directory on one GPU."""
     os.makedirs(output_dir, exist_ok=True)
     brain_data = load_brain_data(brain_data_path) if brain_data_path and os.path.exists(brain_data_path) else {}
@@ -187,7 +189,7 @@ def batch_inference(model, input_dir, output_dir, caption_path=None, condition_t
     process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed,
                         strength=strength, mask_dir=mask_dir, true_cfg_scale=true_cfg_scale, negative_prompt=negative_prompt,
                         brain_guidance_scale=brain_guidance_scale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
-                        apg_momentum=apg_momentum)
+                        apg_momentum=apg_momentum, solver=solver)
     print(f"Processed {len(image_files)} images. Results saved to {output_dir}")
 
 
@@ -204,7 +206,7 @@ def synthetic_item(idx, target_size, device, seed):
                 ppg=torch.randn(4, 256, device=device, generator=g), motion=torch.randn(6, 128, device=device, generator=g))
 
 
-def inference_single(model, item, condition_type, position_delta, target_size, use_signals=("eeg", "fnirs", "ppg", "motion")):
+def inference_single(model, item, condition_type, position_delta, target_size, use_signals=("eeg", "fnirs", "ppg", "motion"), solver=None):
     from src.flux.condition import Condition
     from src.flux.generate import generate
     cond = Condition(condition_type=condition_type, latents=item["cond"], latent_hw=(item["hw"], item["hw"]), position_delta=position_delta)
@@ -213,7 +215,8 @@ def inference_single(model, item, condition_type, position_delta, target_size, u
                    prompt_embeds=item["prompt_embeds"], pooled_prompt_embeds=item["pooled"], output_type="latent",
                    model_config=model.model_config, default_lora=True, additional_condition1=sig["eeg"],
                    additional_condition2=sig["fnirs"], additional_condition3=sig["ppg"], additional_condition4=sig["motion"],
-                   use_brain_condition=sig["eeg"] is not None or sig["fnirs"] is not None, fuse_flag=False)      # inference.py:99-117
+                   use_brain_condition=sig["eeg"] is not None or sig["fnirs"] is not None, fuse_flag=False,      # inference.py:99-117
+                   **cfg_kwargs(solver=solver))
     _print_step_cache(out)
     return out.images[0]
 
@@ -225,7 +228,8 @@ def process_shard(rank, world_size, model, n_items, args, device):
     t0 = time.time()
     for idx in range(start, end):
         item = synthetic_item(idx, args.target_size, device, args.seed)
-        lat = inference_single(model, item, args.condition_type, [args.position_delta_x, args.position_delta_y], args.target_size)
+        lat = inference_single(model, item, args.condition_type, [args.position_delta_x, args.position_delta_y], args.target_size,
+                               **cfg_kwargs(solver=getattr(args, "solver", None)))
         host = lat.cpu()                                             # drains the stream
         eng = getattr(getattr(model, "transformer", None), "engine", None)
         if eng is not None:
@@ -297,7 +301,7 @@ def distributed_inference_worker(rank, world_size, args, config, model_loaded_ev
                             [args.position_delta_x, args.position_delta_y], args.target_size, args.seed, strength=args.strength,
                             mask_dir=args.mask_dir, true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
                             brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
-                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver)
         n_total, n, dt = len(image_files), len(image_files) // world_size, time.time() - t0
     if world_size > 1:
         dist.barrier()
@@ -350,6 +354,9 @@ def main(argv=None):
     p.add_argument("--apg_momentum", type=float, default=None,
                    help="adaptive projected guidance: momentum of the guidance update over the steps, in (-1, 1), usually negative "
                         "(generate(apg_momentum=))")
+    p.add_argument("--solver", type=str, default=None, choices=("euler", "dpmpp_2m"),
+                   help="the sampler (generate(solver=)): euler, the first-order flow-match step (the default), or dpmpp_2m, the second-order "
+                        "multistep DPM-Solver++(2M) on the same schedule at the same one forward per step")
     p.add_argument("--step_cache_thresh", type=float, default=None,
                    help="step caching (TeaCache; model_config['step_cache_thresh']): skip the blocks of denoise steps whose accumulated input "
                         "distance stays under this threshold, > 0 (about 0.25 .. 0.8; larger skips more); prints the computed steps per image")
@@ -381,7 +388,7 @@ def main(argv=None):
                                             seed=args.seed, **_signals(brain_data, name),
                                             **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path),
                                             **cfg_kwargs(args.true_cfg_scale, args.negative_prompt, args.brain_guidance_scale, args.apg_eta,
-                                                         args.apg_norm_threshold, args.apg_momentum))
+                                                         args.apg_norm_threshold, args.apg_momentum, args.solver))
         os.makedirs(args.output_dir, exist_ok=True)
         output_path = os.path.join(args.output_dir, name)
         result_img.save(output_path)
@@ -402,7 +409,7 @@ def main(argv=None):
                             brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir,
                             true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
                             brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
-                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver)
     else:
         print(f"Running distributed inference on {world} GPUs")
         mp.set_start_method("spawn", force=True)

@@ -1,7 +1,7 @@
 // step.hip -- the scheduler step (gfx950): the Euler step on one, two or three branches of the velocity, the inpaint blend, the img2img
-// start (lx_scale_noise) and adaptive projected guidance. One operation written once: a further guidance variant is a PARTS value or a term
-// in guided_v, and a thin entry point. The operation order is the contract of include/lx.h: every rounding below is spelled out
-// (__fsub_rn / __fmul_rn / fmaf), so that no contraction setting can move one.
+// start (lx_scale_noise), adaptive projected guidance and the second-order multistep term (DPM-Solver++(2M)). One operation written once:
+// a further guidance variant is a PARTS value or a term in guided_v, and a thin entry point. The operation order is the contract of
+// include/lx.h: every rounding below is spelled out (__fsub_rn / __fmul_rn / fmaf), so that no contraction setting can move one.
 #include "common.h"
 
 namespace {
@@ -88,32 +88,56 @@ __device__ __forceinline__ void blend_item(Item<W>& o, const Blend& bl, size_t i
   for (int j = 0; j < W; ++j) o.e[j] = blend1(o.e[j], a.e[j], b.e[j], mm.e[j], bl.sigma_next, bl.one_minus_sigma);
 }
 
-// ---- the step (lx_euler_step, lx_euler_step_blend, lx_euler_step_cfg, lx_euler_step_cfg3) ------------------------------------------------
-// x and v hold PARTS parts of n elements. e = x[0, n) + ds guided_v, the inpaint blend where BLEND, and the result stored to every part of
-// x. A work item is VEC consecutive elements of one part, grid-stride loop under a capped grid. VEC = 4: the last n % 4 elements go one by
-// one; with PARTS > 1 the host takes it only where n % 4 == 0 (the later parts are aligned only there), so that tail is dead.
-template <int W, int PARTS, bool BLEND>
-__device__ __forceinline__ void step_item(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, float scale_a, float scale_b,
-                                          const Blend& bl, size_t n, size_t i) {
-  Item<W> v0;
-  const Item<W> g = guided_item<W, PARTS>(v, v_bf16, n, i, scale_a, scale_b, v0);
-  Item<W> o = load_f32<W>(x, i);
+// the second-order operands of a step (lx_dpmpp2m_step, lx_dpmpp2m_step_apg): the previous step's denoised prediction D (fp32, one part's
+// element count, updated in place) and the coefficient c of its difference. All unused where the kernel is not a MULTI one.
+struct Multi {
+  float* D;
+  float c, neg_sigma;
+};
+// o, the Euler value of x along g, receives c (d - D[i]) with d = x - sigma g the denoised prediction, which replaces D[i]. A work item reads
+// and then writes only its own elements of D. c == 0 (uniform over the launch) does not read D: the Euler value leaves as it came, and
+// whatever D held, a NaN included, is overwritten.
+template <int W>
+__device__ __forceinline__ void multi_item(Item<W>& o, const Item<W>& x, const Item<W>& g, const Multi& ms, size_t i) {
+  Item<W> d;
 #pragma unroll
-  for (int j = 0; j < W; ++j) o.e[j] = fmaf(ds, g.e[j], o.e[j]);
+  for (int j = 0; j < W; ++j) d.e[j] = fmaf(ms.neg_sigma, g.e[j], x.e[j]);
+  if (ms.c != 0.f) {
+    const Item<W> prev = load_f32<W>(ms.D, i);
+#pragma unroll
+    for (int j = 0; j < W; ++j) o.e[j] = fmaf(ms.c, __fsub_rn(d.e[j], prev.e[j]), o.e[j]);
+  }
+  store_f32<W>(ms.D, i, d);
+}
+
+// ---- the step (lx_euler_step, lx_euler_step_blend, lx_euler_step_cfg, lx_euler_step_cfg3, lx_dpmpp2m_step) ---------------------------------
+// x and v hold PARTS parts of n elements. e = x[0, n) + ds guided_v, the second-order term where MULTI, the inpaint blend where BLEND, and
+// the result stored to every part of x. A work item is VEC consecutive elements of one part, grid-stride loop under a capped grid. VEC = 4:
+// the last n % 4 elements go one by one; with PARTS > 1 the host takes it only where n % 4 == 0 (the later parts are aligned only there),
+// so that tail is dead.
+template <int W, int PARTS, bool BLEND, bool MULTI>
+__device__ __forceinline__ void step_item(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, float scale_a, float scale_b,
+                                          const Blend& bl, const Multi& ms, size_t n, size_t i) {
+  Item<W> v0;
+  const Item<W> g = guided_item<W, PARTS>(v, v_bf16, n, i, scale_a, scale_b, v0), xx = load_f32<W>(x, i);
+  Item<W> o;
+#pragma unroll
+  for (int j = 0; j < W; ++j) o.e[j] = fmaf(ds, g.e[j], xx.e[j]);
+  if constexpr (MULTI) multi_item<W>(o, xx, g, ms, i);
   if constexpr (BLEND) blend_item<W>(o, bl, i);
   store_parts<W>(x, PARTS, n, i, o);
 }
 
-template <int VEC, int PARTS, bool BLEND>
+template <int VEC, int PARTS, bool BLEND, bool MULTI>
 __global__ __launch_bounds__(256) void euler_parts_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, float ds, float scale_a,
-                                                          float scale_b, const Blend bl, size_t n) {
+                                                          float scale_b, const Blend bl, size_t n, const Multi ms) {
   const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
     const size_t i = it * VEC;
     if (VEC == 4 && i + 4 <= n) {
-      step_item<4, PARTS, BLEND>(x, v, v_bf16, ds, scale_a, scale_b, bl, n, i);
+      step_item<4, PARTS, BLEND, MULTI>(x, v, v_bf16, ds, scale_a, scale_b, bl, ms, n, i);
     } else {
-      for (size_t k = i; k < n && k < i + VEC; ++k) step_item<1, PARTS, BLEND>(x, v, v_bf16, ds, scale_a, scale_b, bl, n, k);
+      for (size_t k = i; k < n && k < i + VEC; ++k) step_item<1, PARTS, BLEND, MULTI>(x, v, v_bf16, ds, scale_a, scale_b, bl, ms, n, k);
     }
   }
 }
@@ -144,7 +168,8 @@ __global__ __launch_bounds__(256) void scale_noise_kernel(float* __restrict__ ou
 //   apg_reduce_kernel  Db of every element to M, and the chunk's (sum Db^2, sum Db w, sum w^2) in double to the workspace: per thread in its
 //                      fixed order, across the lanes of a wave by the xor tree, across the four waves in wave order by thread 0.
 //   apg_total_kernel   per image, the chunk triples added in chunk order. No atomics anywhere: the same bits from run to run.
-//   apg_step_kernel    reads the image's sums, forms the two fp32 coefficients, projects, steps, blends and stores to every part.
+//   apg_step_kernel    reads the image's sums, forms the two fp32 coefficients, projects, steps (with the second-order term around the
+//                      projected velocity where MULTI: lx_dpmpp2m_step_apg), blends and stores to every part.
 constexpr int APG_CHUNK = 4096;
 
 // Db = -sigma (guided_v - v0) (+ momentum M) of the W elements at i, stored to M; xi, vc and db receive x, v0 and Db for the sums
@@ -228,27 +253,32 @@ __global__ __launch_bounds__(64) void apg_total_kernel(const double* __restrict_
 // the fp32 values of a projected step that are the same for every element of an image
 struct ApgCoef { float neg_sigma, c32, k32, neg_inv_sigma, ds; };
 
-__device__ __forceinline__ float apg_step1(float x, float vc, float db, const ApgCoef& a) {
+// the projected velocity the step runs along
+__device__ __forceinline__ float apg_velocity1(float x, float vc, float db, const ApgCoef& a) {
   const float w = fmaf(a.neg_sigma, vc, x);
   const float u = fmaf(a.c32, db, -__fmul_rn(a.k32, w));
-  return fmaf(a.ds, fmaf(a.neg_inv_sigma, u, vc), x);
+  return fmaf(a.neg_inv_sigma, u, vc);
 }
-template <int W, bool BLEND>
+template <int W, bool BLEND, bool MULTI>
 __device__ __forceinline__ void apg_step_item(float* __restrict__ x, const void* __restrict__ v, int v_bf16, int parts, const ApgCoef& a,
-                                              const float* __restrict__ M, const Blend& bl, size_t n, size_t i) {
-  const Item<W> vc = load_v<W>(v, v_bf16, i), db = load_f32<W>(M, i);
-  Item<W> o = load_f32<W>(x, i);
+                                              const float* __restrict__ M, const Blend& bl, const Multi& ms, size_t n, size_t i) {
+  const Item<W> vc = load_v<W>(v, v_bf16, i), db = load_f32<W>(M, i), xx = load_f32<W>(x, i);
+  Item<W> g, o;
 #pragma unroll
-  for (int j = 0; j < W; ++j) o.e[j] = apg_step1(o.e[j], vc.e[j], db.e[j], a);
+  for (int j = 0; j < W; ++j) {
+    g.e[j] = apg_velocity1(xx.e[j], vc.e[j], db.e[j], a);
+    o.e[j] = fmaf(a.ds, g.e[j], xx.e[j]);
+  }
+  if constexpr (MULTI) multi_item<W>(o, xx, g, ms, i);
   if constexpr (BLEND) blend_item<W>(o, bl, i);
   store_parts<W>(x, parts, n, i, o);
 }
 
-template <int VEC, bool BLEND>
+template <int VEC, bool BLEND, bool MULTI>
 __global__ __launch_bounds__(256) void apg_step_kernel(float* __restrict__ x, const void* __restrict__ v, int v_bf16, int parts,
                                                        float neg_sigma, float neg_inv_sigma, float ds, float eta, float norm_threshold,
                                                        const float* __restrict__ M, const double* __restrict__ sums, const Blend bl,
-                                                       size_t elems, size_t n) {
+                                                       size_t elems, size_t n, const Multi ms) {
   const double sdd = sums[(size_t)blockIdx.y * 3], sdw = sums[(size_t)blockIdx.y * 3 + 1], sww = sums[(size_t)blockIdx.y * 3 + 2];
   const double r = (double)norm_threshold;
   const double c = (norm_threshold > 0.f && sdd > r * r) ? r / sqrt(sdd) : 1.0;
@@ -260,10 +290,10 @@ __global__ __launch_bounds__(256) void apg_step_kernel(float* __restrict__ x, co
     if (e >= elems) break;
     const size_t i = base + e;
     if (VEC == 4) {
-      apg_step_item<4, BLEND>(x, v, v_bf16, parts, coef, M, bl, n, i);
+      apg_step_item<4, BLEND, MULTI>(x, v, v_bf16, parts, coef, M, bl, ms, n, i);
     } else {
       const int cnt = elems - e < 4 ? (int)(elems - e) : 4;
-      for (int j = 0; j < cnt; ++j) apg_step_item<1, BLEND>(x, v, v_bf16, parts, coef, M, bl, n, i + j);
+      for (int j = 0; j < cnt; ++j) apg_step_item<1, BLEND, MULTI>(x, v, v_bf16, parts, coef, M, bl, ms, n, i + j);
     }
   }
 }
@@ -286,6 +316,18 @@ int check_step_aliases(const char* name, const char* xrange, const float* x, siz
   return LX_OK;
 }
 
+// The aliasing rules of the second-order history D (pbytes: one part, read and written in place): not x, not v (fp32 or bf16: v is read
+// by other work items while D is written), not the blend's operands.
+int check_multi_aliases(const char* name, const char* xrange, const float* D, const float* x, size_t xbytes, const void* v, size_t vbytes,
+                        const float* x0, const float* z, const float* m, size_t pbytes) {
+  LX_CHECK_ARG(!byte_ranges_overlap(D, pbytes, x, xbytes), "%s: D may not overlap %s", name, xrange);
+  LX_CHECK_ARG(!byte_ranges_overlap(D, pbytes, v, vbytes), "%s: D may not overlap v (it is written while v is read)", name);
+  LX_CHECK_ARG(!m || (!byte_ranges_overlap(D, pbytes, x0, pbytes) && !byte_ranges_overlap(D, pbytes, z, pbytes) &&
+                      !byte_ranges_overlap(D, pbytes, m, pbytes)),
+               "%s: D may not overlap x0, z or m", name);
+  return LX_OK;
+}
+
 // x0, z and m are given together or not at all
 bool blend_triple_ok(const float* x0, const float* z, const float* m) { return (x0 && z && m) || (!x0 && !z && !m); }
 
@@ -294,27 +336,28 @@ bool blend_triple_ok(const float* x0, const float* z, const float* m) { return (
 bool step_vec16(size_t part_stride, uintptr_t f32_ptrs, const void* v, int v_is_bf16) {
   return part_stride % 4 == 0 && (f32_ptrs & 15) == 0 && ((uintptr_t)v & (v_is_bf16 ? 7 : 15)) == 0;
 }
-uintptr_t addr_bits(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
-  return (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e;
+uintptr_t addr_bits(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr,
+                    const void* f = nullptr) {
+  return (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f;
 }
 
 int step_grid(size_t items) { return (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048); }
 
-template <int VEC, int PARTS, bool BLEND>
+template <int VEC, int PARTS, bool BLEND, bool MULTI = false>
 void launch_parts(float* x, const void* v, int v_is_bf16, float dsigma, float scale_a, float scale_b, const Blend& bl, size_t n,
-                  hipStream_t stream) {
-  hipLaunchKernelGGL((euler_parts_kernel<VEC, PARTS, BLEND>), dim3(step_grid((n + VEC - 1) / VEC)), dim3(256), 0, stream, x, v, v_is_bf16,
-                     dsigma, scale_a, scale_b, bl, n);
+                  hipStream_t stream, const Multi& ms = Multi{}) {
+  hipLaunchKernelGGL((euler_parts_kernel<VEC, PARTS, BLEND, MULTI>), dim3(step_grid((n + VEC - 1) / VEC)), dim3(256), 0, stream, x, v,
+                     v_is_bf16, dsigma, scale_a, scale_b, bl, n, ms);
 }
-// the guided step on PARTS parts of n elements: the blend where m is given, 16 bytes at a time where vec
-template <int PARTS>
+// the guided step on PARTS parts of n elements: the blend where m is given, 16 bytes at a time where vec, the second-order term where MULTI
+template <int PARTS, bool MULTI = false>
 void launch_step(float* x, const void* v, int v_is_bf16, float dsigma, float scale_a, float scale_b, const float* x0, const float* z,
-                 const float* m, float sigma_next, size_t n, bool vec, hipStream_t stream) {
+                 const float* m, float sigma_next, size_t n, bool vec, hipStream_t stream, const Multi& ms = Multi{}) {
   const Blend bl{x0, z, m, sigma_next, 1.0f - sigma_next};
-  if (vec && m) launch_parts<4, PARTS, true>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream);
-  else if (vec) launch_parts<4, PARTS, false>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream);
-  else if (m) launch_parts<1, PARTS, true>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream);
-  else launch_parts<1, PARTS, false>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream);
+  if (vec && m) launch_parts<4, PARTS, true, MULTI>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream, ms);
+  else if (vec) launch_parts<4, PARTS, false, MULTI>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream, ms);
+  else if (m) launch_parts<1, PARTS, true, MULTI>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream, ms);
+  else launch_parts<1, PARTS, false, MULTI>(x, v, v_is_bf16, dsigma, scale_a, scale_b, bl, n, stream, ms);
 }
 
 // chunks of one image; 0 where n_images x chunks x 3 doubles, or 3 parts of n_images x elems floats, do not fit an address
@@ -325,10 +368,14 @@ size_t apg_chunks(int n_images, size_t elems) {
   return chunks <= 0x7fffffffu ? chunks : 0;
 }
 
+size_t apg_workspace(int n_images, size_t elems) {
+  return apg_chunks(n_images, elems) * (size_t)(n_images > 0 ? n_images : 0) * 3 * sizeof(double);
+}
+
 template <int VEC>
 void launch_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma, float eta,
                 float norm_threshold, float momentum, float* M, double* sums, double* partials, const Blend& bl, int n_images, size_t elems,
-                hipStream_t stream) {
+                hipStream_t stream, const Multi* ms) {
   const size_t n = (size_t)n_images * elems;
   const int chunks = (int)apg_chunks(n_images, elems);
   const dim3 grid(chunks, n_images);
@@ -336,8 +383,53 @@ void launch_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale
   if (n_parts == 2) hipLaunchKernelGGL((apg_reduce_kernel<VEC, 2>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
   else hipLaunchKernelGGL((apg_reduce_kernel<VEC, 3>), grid, dim3(256), 0, stream, x, v, v_is_bf16, scale_a, scale_b, neg_sigma, momentum, M, partials, elems, n);
   hipLaunchKernelGGL(apg_total_kernel, dim3(n_images), dim3(64), 0, stream, (const double*)partials, chunks, sums);
-  if (bl.m) hipLaunchKernelGGL((apg_step_kernel<VEC, true>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n);
-  else hipLaunchKernelGGL((apg_step_kernel<VEC, false>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n);
+  const Multi none{};
+  if (ms && bl.m) hipLaunchKernelGGL((apg_step_kernel<VEC, true, true>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n, *ms);
+  else if (ms) hipLaunchKernelGGL((apg_step_kernel<VEC, false, true>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n, *ms);
+  else if (bl.m) hipLaunchKernelGGL((apg_step_kernel<VEC, true, false>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n, none);
+  else hipLaunchKernelGGL((apg_step_kernel<VEC, false, false>), grid, dim3(256), 0, stream, x, v, v_is_bf16, n_parts, neg_sigma, neg_inv_sigma, dsigma, eta, norm_threshold, M, sums, bl, elems, n, none);
+}
+
+// lx_euler_step_apg (D == NULL: no second-order term) and lx_dpmpp2m_step_apg under their own names: the checks, the 16-byte decision and
+// the three launches
+int apg_entry(const char* name, float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
+              const Multi* ms, float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace, size_t workspace_bytes,
+              const float* x0, const float* z, const float* m, float sigma_next, int n_images, size_t elems, void* stream) {
+  if (ms) LX_CHECK_ARG(x && v && M && sums && workspace && ms->D, "%s: NULL x, v, D, M, sums or workspace", name);
+  else LX_CHECK_ARG(x && v && M && sums && workspace, "%s: NULL x, v, M, sums or workspace", name);
+  LX_CHECK_ARG(n_parts == 2 || n_parts == 3, "%s: n_parts=%d must be 2 or 3", name, n_parts);
+  LX_CHECK_ARG(n_images >= 1 && elems > 0, "%s: n_images < 1 or elems == 0", name);
+  LX_CHECK_ARG(apg_chunks(n_images, elems) > 0, "%s: more than 65535 images, or the parts do not fit an address", name);
+  LX_CHECK_ARG(f32_is_finite(sigma) && sigma > 0.f, "%s: sigma must be finite and > 0", name);
+  LX_CHECK_ARG(f32_is_finite(scale_a) && (n_parts == 2 || f32_is_finite(scale_b)), "%s: a scale is not finite", name);
+  LX_CHECK_ARG(!ms || f32_is_finite(ms->c), "%s: c is not finite", name);
+  LX_CHECK_ARG(f32_is_finite(eta) && f32_is_finite(norm_threshold) && f32_is_finite(momentum),
+               "%s: eta, norm_threshold or momentum is not finite", name);
+  LX_CHECK_ARG(eta >= 0.f && eta <= 1.f, "%s: eta must lie in [0, 1]", name);
+  LX_CHECK_ARG(norm_threshold >= 0.f, "%s: norm_threshold must be >= 0", name);
+  LX_CHECK_ARG(momentum > -1.f && momentum < 1.f, "%s: |momentum| must be < 1", name);
+  LX_CHECK_ARG(blend_triple_ok(x0, z, m), "%s: x0, z and m go together (all NULL: no blend)", name);
+  LX_CHECK_ARG(workspace_bytes >= apg_workspace(n_images, elems), "%s: the workspace is smaller than lx_apg_workspace_bytes", name);
+  LX_CHECK_ARG((addr_bits(workspace, sums) & 7) == 0, "%s: the workspace and sums must be 8-byte aligned", name);
+  const size_t n = (size_t)n_images * elems, xbytes = (size_t)n_parts * n * sizeof(float), pbytes = n * sizeof(float);
+  const size_t vbytes = (size_t)n_parts * n * (v_is_bf16 ? 2 : 4), sbytes = (size_t)n_images * 3 * sizeof(double);
+  LX_CHECK_ARG(!byte_ranges_overlap(x, xbytes, M, pbytes) && !byte_ranges_overlap(x, xbytes, sums, sbytes) &&
+               !byte_ranges_overlap(x, xbytes, workspace, workspace_bytes),
+               "%s: M, sums and the workspace may not overlap x[0, n_parts n)", name);
+  if (int s = check_step_aliases(name, "x[0, n_parts n)", x, xbytes, v, !v_is_bf16, x0, z, m, pbytes)) return s;
+  LX_CHECK_ARG(!byte_ranges_overlap(v, vbytes, M, pbytes), "%s: M may not overlap v (it is written while v is read)", name);
+  if (ms)
+    if (int s = check_multi_aliases(name, "x[0, n_parts n)", ms->D, x, xbytes, v, vbytes, x0, z, m, pbytes)) return s;
+  LX_CHECK_ARG(!ms || (!byte_ranges_overlap(ms->D, pbytes, M, pbytes) && !byte_ranges_overlap(ms->D, pbytes, sums, sbytes) &&
+                       !byte_ranges_overlap(ms->D, pbytes, workspace, workspace_bytes)),
+               "%s: D may not overlap M, sums or the workspace", name);
+  // every part and every image start: elems is the stride between them
+  const Blend bl{x0, z, m, sigma_next, 1.0f - sigma_next};
+  if (step_vec16(elems, addr_bits(x, M, x0, z, m, ms ? ms->D : nullptr), v, v_is_bf16))
+    launch_apg<4>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, bl, n_images, elems, (hipStream_t)stream, ms);
+  else launch_apg<1>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, bl, n_images, elems, (hipStream_t)stream, ms);
+  LX_LAUNCH_CHECK(name);
+  return LX_OK;
 }
 
 }  // namespace
@@ -405,40 +497,44 @@ extern "C" int lx_euler_step_cfg3(float* x, const void* v, int v_is_bf16, float 
   return LX_OK;
 }
 
-extern "C" size_t lx_apg_workspace_bytes(int n_images, size_t elems) {
-  return apg_chunks(n_images, elems) * (size_t)(n_images > 0 ? n_images : 0) * 3 * sizeof(double);
-}
+extern "C" size_t lx_apg_workspace_bytes(int n_images, size_t elems) { return apg_workspace(n_images, elems); }
 
 extern "C" int lx_euler_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
                                  float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
                                  size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images,
                                  size_t elems, void* stream) {
-  LX_CHECK_ARG(x && v && M && sums && workspace, "lx_euler_step_apg: NULL x, v, M, sums or workspace");
-  LX_CHECK_ARG(n_parts == 2 || n_parts == 3, "lx_euler_step_apg: n_parts=%d must be 2 or 3", n_parts);
-  LX_CHECK_ARG(n_images >= 1 && elems > 0, "lx_euler_step_apg: n_images < 1 or elems == 0");
-  LX_CHECK_ARG(apg_chunks(n_images, elems) > 0, "lx_euler_step_apg: more than 65535 images, or the parts do not fit an address");
-  LX_CHECK_ARG(f32_is_finite(sigma) && sigma > 0.f, "lx_euler_step_apg: sigma must be finite and > 0");
-  LX_CHECK_ARG(f32_is_finite(scale_a) && (n_parts == 2 || f32_is_finite(scale_b)), "lx_euler_step_apg: a scale is not finite");
-  LX_CHECK_ARG(f32_is_finite(eta) && f32_is_finite(norm_threshold) && f32_is_finite(momentum),
-               "lx_euler_step_apg: eta, norm_threshold or momentum is not finite");
-  LX_CHECK_ARG(eta >= 0.f && eta <= 1.f, "lx_euler_step_apg: eta must lie in [0, 1]");
-  LX_CHECK_ARG(norm_threshold >= 0.f, "lx_euler_step_apg: norm_threshold must be >= 0");
-  LX_CHECK_ARG(momentum > -1.f && momentum < 1.f, "lx_euler_step_apg: |momentum| must be < 1");
-  LX_CHECK_ARG(blend_triple_ok(x0, z, m), "lx_euler_step_apg: x0, z and m go together (all NULL: no blend)");
-  LX_CHECK_ARG(workspace_bytes >= lx_apg_workspace_bytes(n_images, elems), "lx_euler_step_apg: the workspace is smaller than lx_apg_workspace_bytes");
-  LX_CHECK_ARG((addr_bits(workspace, sums) & 7) == 0, "lx_euler_step_apg: the workspace and sums must be 8-byte aligned");
-  const size_t n = (size_t)n_images * elems, xbytes = (size_t)n_parts * n * sizeof(float), pbytes = n * sizeof(float);
-  const size_t vbytes = (size_t)n_parts * n * (v_is_bf16 ? 2 : 4);
-  LX_CHECK_ARG(!byte_ranges_overlap(x, xbytes, M, pbytes) && !byte_ranges_overlap(x, xbytes, sums, (size_t)n_images * 3 * sizeof(double)) &&
-               !byte_ranges_overlap(x, xbytes, workspace, workspace_bytes),
-               "lx_euler_step_apg: M, sums and the workspace may not overlap x[0, n_parts n)");
-  if (int s = check_step_aliases("lx_euler_step_apg", "x[0, n_parts n)", x, xbytes, v, !v_is_bf16, x0, z, m, pbytes)) return s;
-  LX_CHECK_ARG(!byte_ranges_overlap(v, vbytes, M, pbytes), "lx_euler_step_apg: M may not overlap v (it is written while v is read)");
-  // every part and every image start: elems is the stride between them
-  const Blend bl{x0, z, m, sigma_next, 1.0f - sigma_next};
-  if (step_vec16(elems, addr_bits(x, M, x0, z, m), v, v_is_bf16))
-    launch_apg<4>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, bl, n_images, elems, (hipStream_t)stream);
-  else launch_apg<1>(x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, eta, norm_threshold, momentum, M, sums, (double*)workspace, bl, n_images, elems, (hipStream_t)stream);
-  LX_LAUNCH_CHECK("lx_euler_step_apg");
+  return apg_entry("lx_euler_step_apg", x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, nullptr, eta, norm_threshold, momentum, M,
+                   sums, workspace, workspace_bytes, x0, z, m, sigma_next, n_images, elems, stream);
+}
+
+// ---- the second-order multistep step (DPM-Solver++(2M) on the flow's sigmas): the Euler entries above with one more term ------------------
+extern "C" int lx_dpmpp2m_step(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
+                               float c, float* D, const float* x0, const float* z, const float* m, float sigma_next, size_t n, void* stream) {
+  LX_CHECK_ARG(x && v && D, "lx_dpmpp2m_step: NULL x, v or D");
+  LX_CHECK_ARG(n_parts >= 1 && n_parts <= 3, "lx_dpmpp2m_step: n_parts=%d must be 1, 2 or 3", n_parts);
+  LX_CHECK_ARG(n > 0, "lx_dpmpp2m_step: n == 0");
+  LX_CHECK_ARG(n <= SIZE_MAX / (3 * sizeof(float)), "lx_dpmpp2m_step: 3n elements do not fit an address");
+  LX_CHECK_ARG(f32_is_finite(sigma) && sigma > 0.f, "lx_dpmpp2m_step: sigma must be finite and > 0");
+  LX_CHECK_ARG(f32_is_finite(c), "lx_dpmpp2m_step: c is not finite");
+  LX_CHECK_ARG((n_parts < 2 || f32_is_finite(scale_a)) && (n_parts < 3 || f32_is_finite(scale_b)), "lx_dpmpp2m_step: a scale is not finite");
+  LX_CHECK_ARG(blend_triple_ok(x0, z, m), "lx_dpmpp2m_step: x0, z and m go together (all NULL: no blend)");
+  const size_t xbytes = (size_t)n_parts * n * sizeof(float), pbytes = n * sizeof(float), vbytes = (size_t)n_parts * n * (v_is_bf16 ? 2 : 4);
+  if (int s = check_step_aliases("lx_dpmpp2m_step", "x[0, n_parts n)", x, xbytes, v, !v_is_bf16, x0, z, m, pbytes)) return s;
+  if (int s = check_multi_aliases("lx_dpmpp2m_step", "x[0, n_parts n)", D, x, xbytes, v, vbytes, x0, z, m, pbytes)) return s;
+  const Multi ms{D, c, -sigma};
+  const bool vec = step_vec16(n_parts > 1 ? n : 0, addr_bits(x, x0, z, m, D), v, v_is_bf16);
+  if (n_parts == 1) launch_step<1, true>(x, v, v_is_bf16, dsigma, 0.f, 0.f, x0, z, m, sigma_next, n, vec, (hipStream_t)stream, ms);
+  else if (n_parts == 2) launch_step<2, true>(x, v, v_is_bf16, dsigma, scale_a, 0.f, x0, z, m, sigma_next, n, vec, (hipStream_t)stream, ms);
+  else launch_step<3, true>(x, v, v_is_bf16, dsigma, scale_a, scale_b, x0, z, m, sigma_next, n, vec, (hipStream_t)stream, ms);
+  LX_LAUNCH_CHECK("lx_dpmpp2m_step");
   return LX_OK;
+}
+
+extern "C" int lx_dpmpp2m_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, float scale_a, float scale_b, float sigma, float dsigma,
+                                   float c, float* D, float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
+                                   size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images,
+                                   size_t elems, void* stream) {
+  const Multi ms{D, c, -sigma};
+  return apg_entry("lx_dpmpp2m_step_apg", x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, &ms, eta, norm_threshold, momentum, M,
+                   sums, workspace, workspace_bytes, x0, z, m, sigma_next, n_images, elems, stream);
 }

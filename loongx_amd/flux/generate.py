@@ -30,6 +30,14 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       first branch's prediction, whose part is weighted by eta. On only where the call is guided and one of the three differs from its
       default (1, 0, 0); otherwise the call is what it was, bit for bit (unguided: one RuntimeWarning). lx_euler_step_apg then steps in
       place of lx_euler_step_cfg / lx_euler_step_cfg3; the per-step sums stay on the device as the output's `lx_apg`.
+  Q11 a second-order multistep sampler (solver="dpmpp_2m"; Lu et al., DPM-Solver++ -- PAPERS.md; diffusers has it as
+      DPMSolverMultistepScheduler(use_flow_sigmas=True), the reference steps with Euler only): the same schedule and the same one forward
+      per step, and each step is the Euler step plus c_i (D_i - D_{i-1}) on the denoised prediction D = x - sigma g along whatever velocity g
+      the step runs (plain, guided by Q7 / Q9, projected by Q10). c_i is formed on the host (pipeline.multistep_coefficient) and is 0 -- the
+      Euler step bit for bit -- on the first step of a trajectory, on the step onto sigma 0 and after sigma 1. One fp32 history buffer of one
+      part's shape lives for the call; lx_dpmpp2m_step / lx_dpmpp2m_step_apg step in place of the Euler entries. A callback that returns
+      latents keeps the history: the next step's difference is then taken against the prediction of the latents it replaced. The default,
+      solver="euler", launches what it launched before; the coefficients used are the output's `lx_solver`.
 """
 from __future__ import annotations
 
@@ -43,7 +51,7 @@ import torch
 import yaml
 
 from .condition import Condition
-from .pipeline import ApgState, FluxPipelineOutput, calculate_shift, retrieve_timesteps
+from .pipeline import ApgState, FluxPipelineOutput, MultistepState, calculate_shift, retrieve_timesteps
 from .pipeline_tools import encode_images
 from .step_cache import step_cache_config
 from .transformer import tranformer_forward
@@ -108,10 +116,11 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    negative_prompt: Union[str, List[str]] = None, negative_prompt_2=None,
                    negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
                    true_cfg_scale: float = 1.0, brain_guidance_scale: float = 1.0, apg_eta: float = 1.0,
-                   apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, **kwargs):
+                   apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, solver: str = "euler", **kwargs):
     """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline, the true-CFG
-    keywords of its FluxPipeline and this project's brain_guidance_scale and apg_* are named here (so they are not among the swallowed
-    **kwargs) and returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params / prepare_apg_params."""
+    keywords of its FluxPipeline and this project's brain_guidance_scale, apg_* and solver are named here (so they are not among the
+    swallowed **kwargs) and returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params / prepare_apg_params /
+    prepare_solver_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
@@ -177,6 +186,21 @@ def _apg(apg_eta, apg_norm_threshold, apg_momentum):
     if not abs(momentum) < 1.0:
         raise ValueError(f"apg_momentum must lie in (-1, 1), got {apg_momentum!r}")
     return None if (eta, norm_threshold, momentum) == (1.0, 0.0, 0.0) else (eta, norm_threshold, momentum)
+
+
+SOLVERS = ("euler", "dpmpp_2m")
+
+
+def prepare_solver_params(solver: str = "euler", **kwargs):
+    return solver
+
+
+def _solver(solver) -> bool:
+    """generate()'s solver -> whether the second-order multistep solver is on (Q11). Anything but one of SOLVERS is a ValueError on the
+    host, before anything of the pipeline is touched."""
+    if not isinstance(solver, str) or solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    return solver == "dpmpp_2m"
 
 
 def _fits_positive(name, neg, pos):
@@ -336,7 +360,9 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     want_apg = _apg(*prepare_apg_params(**params))
     if want_apg is not None and not do_true_cfg and not want_brain_cfg:
         warnings.warn(_APG_UNGUIDED, RuntimeWarning, stacklevel=2)
-    step_cache_config(model_config)          # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
+    # ---- the sampler (Q11): the name is checked here
+    multistep = _solver(prepare_solver_params(**params))
+    step_cache_config(model_config)         # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = _n_prompts(prompt, prompt_embeds)
         image_latents, inpaint_mask = _inpaint_source(
@@ -475,7 +501,11 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
     step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
     n_images = latents.shape[0]
-    apg_state = None
+    apg_state = multistep_state = None
+    if multistep:
+        # (Q11) one history buffer for the steps of this call, of one part's shape [B·n, ...]: made before the latents are repeated per branch
+        multistep_state = MultistepState(tuple(latents.shape), device)
+        step_kwargs["multistep"] = multistep_state
     if want_apg is not None and n_branches == 1 and (do_true_cfg or want_brain_cfg):      # (brain guidance was asked for and is off)
         warnings.warn(_APG_UNGUIDED, RuntimeWarning, stacklevel=2)
     if n_branches > 1:
@@ -523,6 +553,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         nonlocal step_cache_report
         if apg_state is not None:
             apg_state.zero()                  # (empty momentum: the fp16 fallback's second pass starts as a fresh call does)
+        if multistep_state is not None:
+            multistep_state.zero()            # (no history: the same)
         with adapter_weight_tiles(engine, n_branches), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
@@ -610,4 +642,6 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     if not return_dict:
         return (image,)
     return FluxPipelineOutput(images=image, lx_operands=operands_used, lx_step_cache=step_cache_report,
-                              lx_apg=None if apg_state is None else apg_state.sums)
+                              lx_apg=None if apg_state is None else apg_state.sums,
+                              lx_solver=None if multistep_state is None else {"solver": "dpmpp_2m",
+                                                                              "coefficients": list(multistep_state.coefficients)})

@@ -50,8 +50,44 @@ class ApgState:
         self.step = 0
 
 
+class MultistepState:
+    """What the second-order multistep solver carries through the steps of one call (FlowMatchEulerDiscreteScheduler.step(multistep=);
+    generate's solver="dpmpp_2m"): the previous step's denoised prediction D (fp32, one part's shape, on the device), whether one is
+    stored (`have`), and the coefficient of every step taken so far (host floats holding fp32 values; the first-order steps' are 0).
+    zero() is the state before the first step. The analogue of ApgState."""
+
+    def __init__(self, part_shape, device):
+        self.D = torch.zeros(tuple(part_shape), dtype=torch.float32, device=device)
+        self.have = False
+        self.coefficients: List[float] = []
+
+    def zero(self):
+        self.D.zero_()
+        self.have = False
+        self.coefficients = []
+
+
+def multistep_coefficient(sig_host, i: int, begin: int = 0) -> float:
+    """The coefficient c_i of DPM-Solver++(2M) written as the Euler step plus c_i (D_i - D_{i-1}) (include/lx.h, lx_dpmpp2m_step), for step i
+    of the schedule `sig_host` (its fp32 sigmas, the final 0 included) on a trajectory that began at step `begin`:
+        c_i = (1 - s_{i+1} / s_i) (lam_{i+1} - lam_i) / (2 (lam_i - lam_{i-1})),   lam(s) = ln((1 - s) / s)
+    in float64, rounded once to fp32 and returned as a Python float. 0 where the step is first order: the first step of the trajectory (no
+    history), a step onto sigma 0 (diffusers' final_sigmas_type "zero"), and a step whose previous sigma is >= 1 (lam_{i-1} = -inf: the
+    history carries no weight). Host only."""
+    if i <= begin:
+        return 0.0
+    s_prev, s, s_next = (float(sig_host[k]) for k in (i - 1, i, i + 1))
+    if s_next <= 0.0 or s_prev >= 1.0:
+        return 0.0
+    lam_prev, lam, lam_next = (math.log((1.0 - t) / t) for t in (s_prev, s, s_next))
+    if lam == lam_prev:                       # (a repeated sigma: no step was taken between the two predictions)
+        return 0.0
+    return float(np.float32((1.0 - s_next / s) * (lam_next - lam) / (2.0 * (lam - lam_prev))))
+
+
 class FlowMatchEulerDiscreteScheduler:
-    """FLUX.1-dev scheduler config; sigma schedule on the host in fp64 -> fp32 like diffusers, step on the GPU."""
+    """FLUX.1-dev scheduler config; sigma schedule on the host in fp64 -> fp32 like diffusers, step on the GPU. The step is the first-order
+    Euler step, or with step(multistep=) the second-order multistep one at the same one model call per step: `order` stays 1."""
     order = 1
 
     def __init__(self, num_train_timesteps=1000, shift=3.0, use_dynamic_shifting=True, base_shift=0.5, max_shift=1.15,
@@ -109,7 +145,7 @@ class FlowMatchEulerDiscreteScheduler:
         return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None,
-             brain_guidance_scale=None, apg=None):
+             brain_guidance_scale=None, apg=None, multistep=None):
         """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
         inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
         level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend).
@@ -123,7 +159,11 @@ class FlowMatchEulerDiscreteScheduler:
         apg = an ApgState made for one part's shape (generate's apg_eta / apg_norm_threshold / apg_momentum): only together with
         true_cfg_scale and/or brain_guidance_scale. The same batch, stepped by lx_euler_step_apg instead: the total guidance update is
         clamped, given momentum and projected on the first branch's denoised prediction, per image; the state's next row of sums is written
-        on the device. Without apg the method launches what it launched before."""
+        on the device. Without apg the method launches what it launched before.
+        multistep = a MultistepState made for one part's shape (generate's solver="dpmpp_2m"): the step is DPM-Solver++(2M), the same step
+        plus c * (D - D_prev) with D = sample - sigma * velocity the denoised prediction along whatever velocity the step runs (guided,
+        projected under apg) and c = multistep_coefficient(...), 0 on the state's first step; one launch of lx_dpmpp2m_step, or of
+        lx_dpmpp2m_step_apg with apg, in place of the Euler entries. The state keeps D and records c. Without it nothing changes."""
         if apg is not None and brain_guidance_scale is None and true_cfg_scale is None:
             raise ValueError("step(apg=...): adaptive projected guidance acts on a guidance update; pass true_cfg_scale and/or "
                              "brain_guidance_scale with it")
@@ -155,6 +195,20 @@ class FlowMatchEulerDiscreteScheduler:
             if tuple(apg.M.shape) != half or apg.M.dtype != torch.float32 or apg.sums.shape[1] != half[0] or not apg.step < apg.sums.shape[0]:
                 raise ValueError(f"step(apg=...): the state (M {tuple(apg.M.shape)}, sums {tuple(apg.sums.shape)}, step {apg.step}) was not "
                                  f"made for parts of shape {half} or has run out of steps")
+        if multistep is not None:
+            if tuple(multistep.D.shape) != half or multistep.D.dtype != torch.float32:
+                raise ValueError(f"step(multistep=...): the state (D {tuple(multistep.D.shape)}, {multistep.D.dtype}) was not made for parts "
+                                 f"of shape {half} in float32")
+            c = multistep_coefficient(self._sig_host, i, self._begin_index) if multistep.have else 0.0
+            if apg is None:
+                ops.dpmpp2m_step(x, v.contiguous(), float(self._sig_host[i]), ds, c, multistep.D, scales, inpaint, sigma_next)
+            else:
+                ops.dpmpp2m_step_apg(x, v.contiguous(), float(self._sig_host[i]), ds, c, multistep.D, scales, apg.eta, apg.norm_threshold,
+                                     apg.momentum, apg.M, apg.sums[apg.step], apg.workspace, inpaint, sigma_next)
+                apg.step += 1
+            multistep.have = True
+            multistep.coefficients.append(c)
+        elif apg is not None:
             ops.euler_step_apg(x, v.contiguous(), float(self._sig_host[i]), ds, scales, apg.eta, apg.norm_threshold, apg.momentum, apg.M,
                                apg.sums[apg.step], apg.workspace, inpaint, sigma_next)
             apg.step += 1

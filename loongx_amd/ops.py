@@ -693,6 +693,51 @@ def euler_step_apg(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: float
           "lx_euler_step_apg")
 
 
+def _multi_scales(name: str, scales):
+    scales = tuple(float(s) for s in scales)
+    assert len(scales) <= 2, f"{name}: scales is (), (scale,) for two parts or (scale_brain, scale_text) for three"
+    return scales, len(scales) + 1
+
+
+def dpmpp2m_step(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: float, c: float, D: torch.Tensor, scales=(), inpaint=None,
+                 sigma_next: float = 0.0) -> None:
+    """One step of DPM-Solver++(2M) on the flow's sigmas, in place (lx_dpmpp2m_step): the Euler step of euler_step (scales = ()),
+    euler_step_cfg (scales = (s,)) or euler_step_cfg3 (scales = (scale_brain, scale_text)) along its guided velocity g, plus
+    c * (d - D) with d = x - sigma * g the denoised prediction; D (fp32, one part's element count: the previous step's d) becomes d. c == 0
+    does not read D and is that Euler step bit for bit. inpaint = (x0, z, m) blends the result as euler_step_blend does. All contiguous;
+    nothing is synchronised."""
+    scales, parts = _multi_scales("dpmpp2m_step", scales)
+    n, bf16, blend = _step_operands("dpmpp2m_step", x, v, parts, inpaint, f"x and v hold {parts} part(s) of one element count",
+                                    "x0, z and m have the element count of one part", also=(D,))
+    _req(D, torch.float32, "D")
+    assert D.numel() == n, "dpmpp2m_step: D has the element count of one part"
+    check(lib.lx_dpmpp2m_step(x.data_ptr(), v.data_ptr(), bf16, parts, scales[0] if scales else 0.0, scales[-1] if scales else 0.0,
+                              float(sigma), float(dsigma), float(c), D.data_ptr(), *blend, float(sigma_next), n, _stream()), "lx_dpmpp2m_step")
+
+
+def dpmpp2m_step_apg(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: float, c: float, D: torch.Tensor, scales, eta: float,
+                     norm_threshold: float, momentum: float, M: torch.Tensor, sums: torch.Tensor, workspace: torch.Tensor, inpaint=None,
+                     sigma_next: float = 0.0) -> None:
+    """dpmpp2m_step under adaptive projected guidance, in place (lx_dpmpp2m_step_apg): euler_step_apg's operands and passes, with
+    c * (d - D) added around the projected velocity. D is fp32 with one part's element count; c == 0 does not read it and is
+    euler_step_apg bit for bit."""
+    scales, parts = _multi_scales("dpmpp2m_step_apg", scales)
+    assert parts > 1, "dpmpp2m_step_apg: scales is (scale,) for two parts or (scale_brain, scale_text) for three"
+    n, bf16, blend = _step_operands("dpmpp2m_step_apg", x, v, parts, inpaint, f"x and v hold {parts} parts of one element count",
+                                    "x0, z and m have the element count of one part", also=(D, M, sums, workspace))
+    _req(D, torch.float32, "D")
+    _req(M, torch.float32, "M")
+    _req(sums, torch.float64, "sums")
+    assert D.numel() == n and M.numel() == n, "dpmpp2m_step_apg: D and M have the element count of one part"
+    assert sums.dim() == 2 and sums.shape[1] == 3 and sums.shape[0] >= 1, "dpmpp2m_step_apg: sums is [n_images, 3]"
+    n_images = sums.shape[0]
+    assert n % n_images == 0, "dpmpp2m_step_apg: a part holds n_images images of one element count"
+    check(lib.lx_dpmpp2m_step_apg(x.data_ptr(), v.data_ptr(), bf16, parts, scales[0], scales[-1], float(sigma), float(dsigma), float(c),
+                                  D.data_ptr(), float(eta), float(norm_threshold), float(momentum), M.data_ptr(), sums.data_ptr(),
+                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), *blend, float(sigma_next), n_images,
+                                  n // n_images, _stream()), "lx_dpmpp2m_step_apg")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
