@@ -673,6 +673,33 @@ int lx_dpmpp2m_step_apg(float* x, const void* v, int v_is_bf16, int n_parts, flo
                         float* D, float eta, float norm_threshold, float momentum, float* M, double* sums, void* workspace,
                         size_t workspace_bytes, const float* x0, const float* z, const float* m, float sigma_next, int n_images, size_t elems,
                         void* stream);
+/* FlowEdit (Kulikov, Kleiner, Huberman-Spiegelglas and Michaeli, "FlowEdit: Inversion-Free Text-Based Editing Using Pre-Trained Flow
+ * Models"; generate's source_prompt): the inputs of one forward on the batch [target; source]. x_src is the source latents X, z_fe the edit
+ * state Z, noise a fresh draw, all fp32 [n]; out is fp32 [2n]. Per element i < n, in this order:
+ *   s          = fmaf(sigma, noise, (1 - sigma) * x_src)   -- lx_scale_noise(x_src, noise, sigma), the same bits: the source noised to sigma
+ *   out[n + i] = s                                         -- the source branch's input
+ *   out[i]     = z_fe + (s - x_src)                        -- the difference rounded on its own, then one add: the target branch's input
+ * So z_fe == x_src bit for bit gives out[i] within one rounding of s, sigma == 0 gives out[n + i] == x_src and out[i] == z_fe exactly
+ * (finite inputs; up to the sign of a zero). With S, R exact and u = 2^-24: |s - S| <= u (|(1 - sigma) x_src| + |S|) (lx_scale_noise's two
+ * roundings; 1 - sigma is formed once in fp32 and is part of the rule), |out[i] - R| <= |s - S| + u (|s - x_src| + |R|) to first order.
+ * 16-byte accesses only when out, x_src, z_fe and noise are aligned and n % 4 == 0 (out + n is aligned only there); every other call goes
+ * element by element, same bits. Plain vector stores, no atomics.
+ * LX_ERR_INVALID before any launch: a NULL pointer; n == 0 (or 2n floats past the address space); sigma not finite or outside [0, 1];
+ * out[0, 2n) overlapping x_src, z_fe or noise. */
+int lx_flowedit_inputs(float* out, const float* x_src, const float* z_fe, const float* noise, float sigma, size_t n, void* stream);
+/* FlowEdit's update after one forward: v is [2n] = [target; source], the two branches' velocities, fp32 or bf16; z_fe is fp32 [n], updated
+ * in place; m is NULL or an fp32 [n] mask (1: edit, 0: keep); coef = (sigma_next - sigma) / n_avg, formed by the caller. Per element i < n:
+ *   d       = vt - vs                                      -- rounded on its own
+ *   d       = m * d                                        -- only where m is given; one rounded product
+ *   z_fe[i] = (m given and m[i] == 0) ? z_fe[i] : fmaf(coef, d, z_fe[i])
+ * A kept element (m[i] == 0) is stored as it was read, whatever v holds there, a NaN included. vt == vs bit for bit (finite) leaves z_fe
+ * unchanged, up to the sign of a zero. With D = vt - vs exact (fp32 or bf16 values: both exact in fp32) and u = 2^-24:
+ *   |z_fe' - (z_fe + coef m D)| <= u (2 |coef m D| + |z_fe + coef m D|) to first order (one rounding less without m).
+ * 16-byte accesses (8 for bf16 v) only when z_fe, v and m are aligned and n % 4 == 0; every other call goes element by element, same bits.
+ * Each work item reads, then writes, only its own elements of z_fe. Plain vector stores, no atomics.
+ * LX_ERR_INVALID before any launch: NULL z_fe or v; n == 0 (or 2n floats past the address space); coef not finite; v (fp32 or bf16: it is
+ * read by other work items while z_fe is written) or m overlapping z_fe[0, n). */
+int lx_flowedit_step(float* z_fe, const void* v, int v_is_bf16, float coef, const float* m, size_t n, void* stream);
 /* dst(fp32)[i] = src(fp32|bf16)[i] ; dst(bf16) = src(fp32) : layout plumbing between streams. dst_bf16: 0 fp32 | 1 bf16 | 2 IEEE fp16
  * (saturated to +-65504: the operand image of an LX_OPERANDS_F16 GEMM) */
 int lx_convert(void* dst, int dst_bf16, const void* src, int src_bf16, size_t n, void* stream);

@@ -97,12 +97,14 @@ def _print_step_cache(result):
         print(f"step cache: computed {len(rep['computed'])} of {rep['steps']} steps (threshold {rep['thresh']:g})")
 
 
-def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
+def edit_kwargs(source_img, target_size, strength=None, mask_path=None, flowedit=None):
     """--strength / --mask_dir / --mask_path -> generate()'s img2img / inpaint keywords (an addition; diffusers' FluxImg2ImgPipeline /
     FluxInpaintPipeline): the input image, resized to the target size, is the source that `strength` starts from and that the black part
-    of the mask keeps. Nothing given: no keywords, and generate() is called as before."""
-    if strength is None and mask_path is None:
-        return {}
+    of the mask keeps. flowedit = flowedit_kwargs(...) with a --source_prompt: the input image is the source that prompt describes, and
+    the keywords go along. Nothing given: no keywords, and generate() is called as before."""
+    flowedit = flowedit or {}
+    if strength is None and mask_path is None and "source_prompt" not in flowedit:
+        return dict(flowedit)
     from PIL import Image
     kw = {"image": source_img.convert("RGB").resize((target_size, target_size), resample=Image.LANCZOS)}
     if strength is not None:
@@ -111,7 +113,16 @@ def edit_kwargs(source_img, target_size, strength=None, mask_path=None):
         if not os.path.isfile(mask_path):
             raise FileNotFoundError(f"no mask at {mask_path} (--mask_dir holds one mask per input file name; --mask_path is the one of --single_image)")
         kw["mask_image"] = Image.open(mask_path).convert("L")
+    kw.update(flowedit)
     return kw
+
+
+def flowedit_kwargs(source_prompt=None, source_guidance_scale=None, flowedit_n_max=None, flowedit_n_avg=None):
+    """--source_prompt / --source_guidance_scale / --flowedit_n_max / --flowedit_n_avg -> generate()'s FlowEdit keywords (an addition:
+    the input image is edited from what --source_prompt says it shows towards the prompt), each only when given"""
+    given = (("source_prompt", source_prompt), ("source_guidance_scale", source_guidance_scale), ("flowedit_n_max", flowedit_n_max),
+             ("flowedit_n_avg", flowedit_n_avg))
+    return {name: value for name, value in given if value is not None}
 
 
 def cfg_kwargs(true_cfg_scale=None, negative_prompt=None, brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None,
@@ -158,9 +169,11 @@ def load_captions(caption_path):
 
 def process_image_batch(rank, world_size, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta,
                         target_size, seed, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                        brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None):
+                        brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None,
+                        flowedit=None):
     """inference.py:124-176: this rank's contiguous slice of the image list. strength / mask_dir: edit_kwargs, per image; true_cfg_scale /
-    negative_prompt / brain_guidance_scale / apg_* / solver: cfg_kwargs, the same for every image."""
+    negative_prompt / brain_guidance_scale / apg_* / solver: cfg_kwargs, the same for every image; flowedit: flowedit_kwargs(...), the same
+    source description for every image."""
     from PIL import Image
     from loongx_amd.dist import shard_range
     start_idx, end_idx = shard_range(len(image_files), rank, world_size)
@@ -170,7 +183,8 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
         prompt = captions.get(img_file, "Edit this image")
         result_img = inference_single_image(model, condition_img, prompt, condition_type=condition_type, position_delta=position_delta,
                                             target_size=target_size, seed=seed, **_signals(brain_data, img_file, model.device),
-                                            **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None),
+                                            **edit_kwargs(condition_img, target_size, strength, os.path.join(mask_dir, img_file) if mask_dir else None,
+                                                          flowedit),
                                             **cfg_kwargs(true_cfg_scale, negative_prompt, brain_guidance_scale, apg_eta, apg_norm_threshold,
                                                          apg_momentum, solver))
         result_img.save(os.path.join(output_dir, img_file))
@@ -180,7 +194,8 @@ def process_image_batch(rank, world_size, model, image_files, input_dir, output_
 
 def batch_inference(model, input_dir, output_dir, caption_path=None, condition_type="SEED", target_size=512, position_delta=[0, -32],
                     seed=42, brain_data_path=None, strength=None, mask_dir=None, true_cfg_scale=None, negative_prompt=None,
-                    brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None):
+                    brain_guidance_scale=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None, solver=None,
+                    flowedit=None):
     """inference.py:255-339: all captioned images of a directory on one GPU."""
     os.makedirs(output_dir, exist_ok=True)
     brain_data = load_brain_data(brain_data_path) if brain_data_path and os.path.exists(brain_data_path) else {}
@@ -189,7 +204,7 @@ def batch_inference(model, input_dir, output_dir, caption_path=None, condition_t
     process_image_batch(0, 1, model, image_files, input_dir, output_dir, captions, brain_data, condition_type, position_delta, target_size, seed,
                         strength=strength, mask_dir=mask_dir, true_cfg_scale=true_cfg_scale, negative_prompt=negative_prompt,
                         brain_guidance_scale=brain_guidance_scale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
-                        apg_momentum=apg_momentum, solver=solver)
+                        apg_momentum=apg_momentum, solver=solver, flowedit=flowedit)
     print(f"Processed {len(image_files)} images. Results saved to {output_dir}")
 
 
@@ -301,7 +316,9 @@ def distributed_inference_worker(rank, world_size, args, config, model_loaded_ev
                             [args.position_delta_x, args.position_delta_y], args.target_size, args.seed, strength=args.strength,
                             mask_dir=args.mask_dir, true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
                             brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
-                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver)
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver,
+                            flowedit=flowedit_kwargs(args.source_prompt, args.source_guidance_scale, args.flowedit_n_max,
+                                                     args.flowedit_n_avg))
         n_total, n, dt = len(image_files), len(image_files) // world_size, time.time() - t0
     if world_size > 1:
         dist.barrier()
@@ -357,6 +374,16 @@ def main(argv=None):
     p.add_argument("--solver", type=str, default=None, choices=("euler", "dpmpp_2m"),
                    help="the sampler (generate(solver=)): euler, the first-order flow-match step (the default), or dpmpp_2m, the second-order "
                         "multistep DPM-Solver++(2M) on the same schedule at the same one forward per step")
+    p.add_argument("--source_prompt", type=str, default=None,
+                   help="FlowEdit: what the input image shows (generate(source_prompt=)); the image is then edited from this description "
+                        "towards the prompt, without inversion, by one forward at twice the batch over the last --flowedit_n_max steps")
+    p.add_argument("--source_guidance_scale", type=float, default=None,
+                   help="FlowEdit: the distilled-guidance value of the source branch, >= 0 (generate(source_guidance_scale=); default 1.5)")
+    p.add_argument("--flowedit_n_max", type=int, default=None,
+                   help="FlowEdit: how many steps, the last ones of the schedule, the edit runs (generate(flowedit_n_max=); default T - T // 7: "
+                        "24 of 28; more steps change more)")
+    p.add_argument("--flowedit_n_avg", type=int, default=None,
+                   help="FlowEdit: noise draws, and forwards, averaged per step, >= 1 (generate(flowedit_n_avg=); default 1)")
     p.add_argument("--step_cache_thresh", type=float, default=None,
                    help="step caching (TeaCache; model_config['step_cache_thresh']): skip the blocks of denoise steps whose accumulated input "
                         "distance stays under this threshold, > 0 (about 0.25 .. 0.8; larger skips more); prints the computed steps per image")
@@ -369,6 +396,9 @@ def main(argv=None):
         p.error("--brain_guidance_scale goes to the images of --input_dir / --single_image: not with --synthetic")
     if args.synthetic and any(a is not None for a in (args.apg_eta, args.apg_norm_threshold, args.apg_momentum)):
         p.error("--apg_eta / --apg_norm_threshold / --apg_momentum act on a guided call: not with --synthetic")
+    flowedit = flowedit_kwargs(args.source_prompt, args.source_guidance_scale, args.flowedit_n_max, args.flowedit_n_avg)
+    if args.synthetic and flowedit:
+        p.error("--source_prompt / --source_guidance_scale / --flowedit_n_max / --flowedit_n_avg edit an input image: not with --synthetic")
     config = get_config()
     config.setdefault("model", {})
     if args.operands:
@@ -386,7 +416,7 @@ def main(argv=None):
         result_img = inference_single_image(model, condition_img, args.prompt, condition_type=args.condition_type,
                                             position_delta=[args.position_delta_x, args.position_delta_y], target_size=args.target_size,
                                             seed=args.seed, **_signals(brain_data, name),
-                                            **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path),
+                                            **edit_kwargs(condition_img, args.target_size, args.strength, args.mask_path, flowedit),
                                             **cfg_kwargs(args.true_cfg_scale, args.negative_prompt, args.brain_guidance_scale, args.apg_eta,
                                                          args.apg_norm_threshold, args.apg_momentum, args.solver))
         os.makedirs(args.output_dir, exist_ok=True)
@@ -409,7 +439,8 @@ def main(argv=None):
                             brain_data_path=args.brain_data_path, strength=args.strength, mask_dir=args.mask_dir,
                             true_cfg_scale=args.true_cfg_scale, negative_prompt=args.negative_prompt,
                             brain_guidance_scale=args.brain_guidance_scale, apg_eta=args.apg_eta,
-                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver)
+                            apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum, solver=args.solver,
+                            flowedit=flowedit)
     else:
         print(f"Running distributed inference on {world} GPUs")
         mp.set_start_method("spawn", force=True)

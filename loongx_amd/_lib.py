@@ -150,6 +150,8 @@ _SIGS = {
     "lx_euler_step_apg": (C.c_int, [_P, _P, _I, _I] + [_F] * 7 + [_P, _P, _P, _Z, _P, _P, _P, _F, _I, _Z, _P]),
     "lx_dpmpp2m_step": (C.c_int, [_P, _P, _I, _I] + [_F] * 5 + [_P, _P, _P, _P, _F, _Z, _P]),
     "lx_dpmpp2m_step_apg": (C.c_int, [_P, _P, _I, _I] + [_F] * 5 + [_P] + [_F] * 3 + [_P, _P, _P, _Z, _P, _P, _P, _F, _I, _Z, _P]),
+    "lx_flowedit_inputs": (C.c_int, [_P, _P, _P, _P, _F, _Z, _P]),
+    "lx_flowedit_step": (C.c_int, [_P, _P, _I, _F, _P, _Z, _P]),
     "lx_convert": (C.c_int, [_P, _I, _P, _I, _Z, _P]),
     "lx_s4_scan": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "lx_s4_conv": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),

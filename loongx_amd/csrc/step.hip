@@ -1,5 +1,6 @@
 // step.hip -- the scheduler step (gfx950): the Euler step on one, two or three branches of the velocity, the inpaint blend, the img2img
-// start (lx_scale_noise), adaptive projected guidance and the second-order multistep term (DPM-Solver++(2M)). One operation written once:
+// start (lx_scale_noise), adaptive projected guidance, the second-order multistep term (DPM-Solver++(2M)) and FlowEdit's two launches
+// (lx_flowedit_inputs, lx_flowedit_step), which share the item loop and the load / store parts. One operation written once:
 // a further guidance variant is a PARTS value or a term in guided_v, and a thin entry point. The operation order is the contract of
 // include/lx.h: every rounding below is spelled out (__fsub_rn / __fmul_rn / fmaf), so that no contraction setting can move one.
 #include "common.h"
@@ -157,6 +158,69 @@ __global__ __launch_bounds__(256) void scale_noise_kernel(float* __restrict__ ou
       store_f32<4>(out, i, o);
     } else {
       for (size_t k = i; k < n && k < i + VEC; ++k) out[k] = scale_noise1(x0[k], z[k], sigma, one_minus_sigma);
+    }
+  }
+}
+
+// ---- FlowEdit (lx_flowedit_inputs, lx_flowedit_step): the step's item loop on two-part arrays ------------------------------------------
+// The inputs of one forward: s = the source noised to sigma (scale_noise1: lx_scale_noise's bits) to out[n + i], z_fe + (s - x_src) to
+// out[i]. The host takes VEC = 4 only where n % 4 == 0 (the second part is aligned only there), so the element tail is dead on that path.
+template <int W>
+__device__ __forceinline__ void flowedit_inputs_item(float* __restrict__ out, const float* __restrict__ x_src, const float* __restrict__ z_fe,
+                                                     const float* __restrict__ noise, float sigma, float one_minus_sigma, size_t n, size_t i) {
+  const Item<W> a = load_f32<W>(x_src, i), b = load_f32<W>(noise, i), zz = load_f32<W>(z_fe, i);
+  Item<W> s, r;
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    s.e[j] = scale_noise1(a.e[j], b.e[j], sigma, one_minus_sigma);
+    r.e[j] = __fadd_rn(zz.e[j], __fsub_rn(s.e[j], a.e[j]));
+  }
+  store_f32<W>(out, i, r);
+  store_f32<W>(out, n + i, s);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void flowedit_inputs_kernel(float* __restrict__ out, const float* __restrict__ x_src,
+                                                              const float* __restrict__ z_fe, const float* __restrict__ noise, float sigma,
+                                                              float one_minus_sigma, size_t n) {
+  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4 && i + 4 <= n) {
+      flowedit_inputs_item<4>(out, x_src, z_fe, noise, sigma, one_minus_sigma, n, i);
+    } else {
+      for (size_t k = i; k < n && k < i + VEC; ++k) flowedit_inputs_item<1>(out, x_src, z_fe, noise, sigma, one_minus_sigma, n, k);
+    }
+  }
+}
+
+// The update after one forward on [target; source]: z_fe += coef (m) (vt - vs). An element with m == 0 is stored as it was read.
+template <int W, bool MASK>
+__device__ __forceinline__ void flowedit_step_item(float* __restrict__ z_fe, const void* __restrict__ v, int v_bf16, float coef,
+                                                   const float* __restrict__ m, size_t n, size_t i) {
+  const Item<W> vt = load_v<W>(v, v_bf16, i), vs = load_v<W>(v, v_bf16, n + i), zz = load_f32<W>(z_fe, i);
+  Item<W> mm = zz, o;
+  if constexpr (MASK) mm = load_f32<W>(m, i);
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    float d = __fsub_rn(vt.e[j], vs.e[j]);
+    if constexpr (MASK) d = __fmul_rn(mm.e[j], d);
+    const float r = fmaf(coef, d, zz.e[j]);
+    o.e[j] = (MASK && mm.e[j] == 0.f) ? zz.e[j] : r;
+  }
+  store_f32<W>(z_fe, i, o);
+}
+
+template <int VEC, bool MASK>
+__global__ __launch_bounds__(256) void flowedit_step_kernel(float* __restrict__ z_fe, const void* __restrict__ v, int v_bf16, float coef,
+                                                            const float* __restrict__ m, size_t n) {
+  const size_t items = (n + VEC - 1) / VEC, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    const size_t i = it * VEC;
+    if (VEC == 4 && i + 4 <= n) {
+      flowedit_step_item<4, MASK>(z_fe, v, v_bf16, coef, m, n, i);
+    } else {
+      for (size_t k = i; k < n && k < i + VEC; ++k) flowedit_step_item<1, MASK>(z_fe, v, v_bf16, coef, m, n, k);
     }
   }
 }
@@ -537,4 +601,40 @@ extern "C" int lx_dpmpp2m_step_apg(float* x, const void* v, int v_is_bf16, int n
   const Multi ms{D, c, -sigma};
   return apg_entry("lx_dpmpp2m_step_apg", x, v, v_is_bf16, n_parts, scale_a, scale_b, sigma, dsigma, &ms, eta, norm_threshold, momentum, M,
                    sums, workspace, workspace_bytes, x0, z, m, sigma_next, n_images, elems, stream);
+}
+
+// ---- FlowEdit (Kulikov et al.): the inputs of one forward on [target; source], and the update of the edit state after it -----------------
+extern "C" int lx_flowedit_inputs(float* out, const float* x_src, const float* z_fe, const float* noise, float sigma, size_t n, void* stream) {
+  LX_CHECK_ARG(out && x_src && z_fe && noise, "lx_flowedit_inputs: NULL operand");
+  LX_CHECK_ARG(n > 0, "lx_flowedit_inputs: n == 0");
+  LX_CHECK_ARG(n <= SIZE_MAX / (2 * sizeof(float)), "lx_flowedit_inputs: 2n elements do not fit an address");
+  LX_CHECK_ARG(f32_is_finite(sigma) && sigma >= 0.f && sigma <= 1.f, "lx_flowedit_inputs: sigma must be finite and lie in [0, 1]");
+  const size_t obytes = 2 * n * sizeof(float), pbytes = n * sizeof(float);
+  LX_CHECK_ARG(!byte_ranges_overlap(out, obytes, x_src, pbytes) && !byte_ranges_overlap(out, obytes, z_fe, pbytes) &&
+               !byte_ranges_overlap(out, obytes, noise, pbytes),
+               "lx_flowedit_inputs: x_src, z_fe and noise may not overlap out[0, 2n)");
+  const float oms = 1.0f - sigma;
+  if (step_vec16(n, addr_bits(out, x_src, z_fe, noise), nullptr, 0))
+    hipLaunchKernelGGL(flowedit_inputs_kernel<4>, dim3(step_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, out, x_src, z_fe, noise, sigma, oms, n);
+  else hipLaunchKernelGGL(flowedit_inputs_kernel<1>, dim3(step_grid(n)), dim3(256), 0, (hipStream_t)stream, out, x_src, z_fe, noise, sigma, oms, n);
+  LX_LAUNCH_CHECK("lx_flowedit_inputs");
+  return LX_OK;
+}
+
+extern "C" int lx_flowedit_step(float* z_fe, const void* v, int v_is_bf16, float coef, const float* m, size_t n, void* stream) {
+  LX_CHECK_ARG(z_fe && v, "lx_flowedit_step: NULL z_fe or v");
+  LX_CHECK_ARG(n > 0, "lx_flowedit_step: n == 0");
+  LX_CHECK_ARG(n <= SIZE_MAX / (2 * sizeof(float)), "lx_flowedit_step: 2n elements do not fit an address");
+  LX_CHECK_ARG(f32_is_finite(coef), "lx_flowedit_step: coef is not finite");
+  const size_t pbytes = n * sizeof(float);
+  LX_CHECK_ARG(!byte_ranges_overlap(z_fe, pbytes, v, 2 * n * (v_is_bf16 ? 2 : 4)), "lx_flowedit_step: v may not overlap z_fe[0, n) (it is updated in place)");
+  LX_CHECK_ARG(!m || !byte_ranges_overlap(z_fe, pbytes, m, pbytes), "lx_flowedit_step: m may not overlap z_fe[0, n) (it is updated in place)");
+  const bool vec = step_vec16(n, addr_bits(z_fe, m), v, v_is_bf16);
+  const dim3 grid(step_grid(vec ? n / 4 : n));
+  if (vec && m) hipLaunchKernelGGL((flowedit_step_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, z_fe, v, v_is_bf16, coef, m, n);
+  else if (vec) hipLaunchKernelGGL((flowedit_step_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, z_fe, v, v_is_bf16, coef, m, n);
+  else if (m) hipLaunchKernelGGL((flowedit_step_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, z_fe, v, v_is_bf16, coef, m, n);
+  else hipLaunchKernelGGL((flowedit_step_kernel<1, false>), grid, dim3(256), 0, (hipStream_t)stream, z_fe, v, v_is_bf16, coef, m, n);
+  LX_LAUNCH_CHECK("lx_flowedit_step");
+  return LX_OK;
 }

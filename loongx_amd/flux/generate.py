@@ -38,6 +38,19 @@ Differences from the reference, all deliberate and recorded in DESIGN.md (SURVEY
       part's shape lives for the call; lx_dpmpp2m_step / lx_dpmpp2m_step_apg step in place of the Euler entries. A callback that returns
       latents keeps the history: the next step's difference is then taken against the prediction of the latents it replaced. The default,
       solver="euler", launches what it launched before; the coefficients used are the output's `lx_solver`.
+  Q12 editing a source image along a prompt change (source_prompt[_embeds], source_guidance_scale, flowedit_n_max, flowedit_n_avg; Kulikov
+      et al., FlowEdit -- PAPERS.md; neither the reference nor diffusers has it): with a description of what `image` / `image_latents`
+      shows, the call integrates an ODE from the source latents X straight to the edited ones, without inversion: Z starts as X, and over
+      the last n_max steps of the schedule every step draws n_avg noises, forms S = scale_noise(X, sigma_i, N) and R = Z + (S - X)
+      (lx_flowedit_inputs), runs ONE forward at batch 2·B·n on [R; S] with the embeddings [target; source] and the per-row guidance
+      [guidance_scale; source_guidance_scale], and updates Z += mask (s_{i+1} - s_i) / n_avg (Vt - Vs) (lx_flowedit_step). The target
+      branch is what the brain section made of the embeddings (branch F); the source embeddings are used as given, by Q7's rule and for the
+      same reason. mask_image / latent_mask become the mask of the update: kept tokens are the source bit for bit. The first noise is
+      what prepare_latents returns (the caller's `latents`, or its draw), every later one a fresh draw from the same `generator`; the fp16
+      fallback's second pass starts from Z = X at the begin index again and draws ON from the generator (it does not replay the first
+      pass's noises). A callback sees, and may replace, Z. Refused together with true CFG, brain guidance, APG, solver != "euler", the step
+      cache and strength != 1; the paper's n_min tail (plain sampling of the target over the last steps) does not exist here. What was
+      done is the output's `lx_flowedit`; a call without the keywords launches what it launched before.
 """
 from __future__ import annotations
 
@@ -51,7 +64,7 @@ import torch
 import yaml
 
 from .condition import Condition
-from .pipeline import ApgState, FluxPipelineOutput, MultistepState, calculate_shift, retrieve_timesteps
+from .pipeline import ApgState, FlowEditState, FluxPipelineOutput, MultistepState, calculate_shift, retrieve_timesteps
 from .pipeline_tools import encode_images
 from .step_cache import step_cache_config
 from .transformer import tranformer_forward
@@ -116,11 +129,14 @@ def prepare_params(prompt: Union[str, List[str]] = None, prompt_2=None, height: 
                    negative_prompt: Union[str, List[str]] = None, negative_prompt_2=None,
                    negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
                    true_cfg_scale: float = 1.0, brain_guidance_scale: float = 1.0, apg_eta: float = 1.0,
-                   apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, solver: str = "euler", **kwargs):
+                   apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, solver: str = "euler",
+                   source_prompt: Union[str, List[str]] = None, source_prompt_2=None, source_prompt_embeds: Optional[torch.Tensor] = None,
+                   source_pooled_prompt_embeds: Optional[torch.Tensor] = None, source_guidance_scale: float = 1.5,
+                   flowedit_n_max: Optional[int] = None, flowedit_n_avg: int = 1, **kwargs):
     """The reference's 18-tuple. The img2img / inpaint keywords of diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline, the true-CFG
-    keywords of its FluxPipeline and this project's brain_guidance_scale, apg_* and solver are named here (so they are not among the
-    swallowed **kwargs) and returned by prepare_inpaint_params / prepare_cfg_params / prepare_brain_cfg_params / prepare_apg_params /
-    prepare_solver_params."""
+    keywords of its FluxPipeline and this project's brain_guidance_scale, apg_*, solver and FlowEdit keywords (source_*, flowedit_*) are
+    named here (so they are not among the swallowed **kwargs) and returned by prepare_inpaint_params / prepare_cfg_params /
+    prepare_brain_cfg_params / prepare_apg_params / prepare_solver_params / prepare_flowedit_params."""
     return (prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, num_images_per_prompt, generator,
             latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict, joint_attention_kwargs, callback_on_step_end,
             callback_on_step_end_tensor_inputs, max_sequence_length)
@@ -201,6 +217,83 @@ def _solver(solver) -> bool:
     if not isinstance(solver, str) or solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     return solver == "dpmpp_2m"
+
+
+def prepare_flowedit_params(source_prompt=None, source_prompt_2=None, source_prompt_embeds=None, source_pooled_prompt_embeds=None,
+                            source_guidance_scale: float = 1.5, flowedit_n_max: Optional[int] = None, flowedit_n_avg: int = 1, **kwargs):
+    return (source_prompt, source_prompt_2, source_prompt_embeds, source_pooled_prompt_embeds, source_guidance_scale, flowedit_n_max,
+            flowedit_n_avg)
+
+
+def flowedit_default_n_max(num_inference_steps: int) -> int:
+    """T - T // 7: the paper's 24 of 28 steps, kept in proportion (at least 1)"""
+    return max(int(num_inference_steps) - int(num_inference_steps) // 7, 1)
+
+
+def _flowedit(source_prompt, source_prompt_embeds, source_pooled_prompt_embeds, source_guidance_scale, flowedit_n_max, flowedit_n_avg,
+              num_inference_steps, prompt, prompt_embeds, pooled_prompt_embeds):
+    """generate()'s FlowEdit arguments (Q12) -> (n_max, n_avg) where a source description is given, else None. The three numbers are
+    checked whether or not it is on. Every refusal is a ValueError on the host, before anything of the pipeline is touched, naming the
+    keyword."""
+    T = num_inference_steps
+    if flowedit_n_max is not None and (isinstance(flowedit_n_max, bool) or not isinstance(flowedit_n_max, (int, np.integer)) or
+                                       not isinstance(T, (int, np.integer)) or not 1 <= int(flowedit_n_max) <= int(T)):
+        raise ValueError(f"flowedit_n_max must be an int in [1, num_inference_steps = {T}] (None: T - T // 7), got {flowedit_n_max!r}")
+    if isinstance(flowedit_n_avg, bool) or not isinstance(flowedit_n_avg, (int, np.integer)) or int(flowedit_n_avg) < 1:
+        raise ValueError(f"flowedit_n_avg must be an int >= 1, got {flowedit_n_avg!r}")
+    _finite_number("source_guidance_scale", source_guidance_scale, at_least=0)
+    if source_prompt is not None and source_prompt_embeds is not None:
+        raise ValueError("Cannot forward both `source_prompt` and `source_prompt_embeds`.")
+    if (source_prompt_embeds is None) != (source_pooled_prompt_embeds is None):
+        raise ValueError("`source_prompt_embeds` and `source_pooled_prompt_embeds` have to be passed together.")
+    if source_prompt is not None:
+        n_prompts = _n_prompts(prompt, prompt_embeds)
+        if not isinstance(source_prompt, (str, list)):
+            raise ValueError(f"`source_prompt` has to be of type `str` or `list` but is {type(source_prompt)}")
+        if isinstance(source_prompt, list) and n_prompts is not None and len(source_prompt) not in (1, n_prompts):
+            raise ValueError(f"`source_prompt` has {len(source_prompt)} entries for a batch of {n_prompts} prompts: one, or one per prompt")
+    if source_prompt_embeds is not None and prompt_embeds is not None and pooled_prompt_embeds is not None:
+        _fits_positive("source_prompt_embeds", source_prompt_embeds, prompt_embeds)
+        _fits_positive("source_pooled_prompt_embeds", source_pooled_prompt_embeds, pooled_prompt_embeds)
+    if source_prompt is None and source_prompt_embeds is None:
+        return None
+    if not isinstance(T, (int, np.integer)) or isinstance(T, bool) or int(T) < 1:
+        raise ValueError(f"source_prompt: FlowEdit needs num_inference_steps as an int >= 1, got {T!r}")
+    return (flowedit_default_n_max(T) if flowedit_n_max is None else int(flowedit_n_max)), int(flowedit_n_avg)
+
+
+_FLOWEDIT_WITH = "source_prompt (FlowEdit) does not combine with {}: its velocity is the difference of its own two branches"
+
+
+def _flowedit_alone(do_true_cfg, brain_guidance_scale, want_apg, multistep, model_config, image, image_latents, strength):
+    """what FlowEdit refuses to run with (Q12): ValueErrors on the host, before anything of the pipeline is touched"""
+    if do_true_cfg:
+        raise ValueError(_FLOWEDIT_WITH.format("an active true CFG (true_cfg_scale > 1 with a negative prompt)"))
+    if float(brain_guidance_scale) > 1:
+        raise ValueError(_FLOWEDIT_WITH.format(f"brain_guidance_scale={brain_guidance_scale} (> 1)"))
+    if want_apg is not None:
+        raise ValueError(_FLOWEDIT_WITH.format("apg_eta / apg_norm_threshold / apg_momentum: there is no guidance update to project"))
+    if multistep:
+        raise ValueError(_FLOWEDIT_WITH.format('solver != "euler": every step starts from fresh noise, there is no history to extrapolate'))
+    if step_cache_config(model_config) is not None:
+        raise ValueError(_FLOWEDIT_WITH.format('model_config["step_cache_thresh"]: its probe compares consecutive block inputs, which fresh '
+                                               "noise makes meaningless"))
+    if image is None and image_latents is None:
+        raise ValueError("source_prompt (FlowEdit) describes a source image: pass `image` or `image_latents`.")
+    if not (isinstance(strength, (int, float)) and float(strength) == 1.0):
+        raise ValueError(f"strength={strength} with source_prompt (FlowEdit): flowedit_n_max plays its part, leave strength at 1")
+
+
+def _flowedit_guidance(guidance, n_images, source_guidance_scale):
+    """The per-row distilled-guidance vector of FlowEdit's batch [target; source]: `guidance` ([B·n]: the target branch's value per image)
+    followed by source_guidance_scale per image. On a transformer without guidance embeddings (`guidance` is None) there is none, and a
+    source_guidance_scale that differs from its default is one RuntimeWarning."""
+    if guidance is None:
+        if float(source_guidance_scale) != 1.5:
+            warnings.warn(f"source_guidance_scale={source_guidance_scale} on a transformer without guidance embeddings: it has no effect",
+                          RuntimeWarning, stacklevel=3)
+        return None
+    return torch.cat([guidance, torch.full((n_images,), float(source_guidance_scale), device=guidance.device, dtype=guidance.dtype)])
 
 
 def _fits_positive(name, neg, pos):
@@ -363,6 +456,13 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     # ---- the sampler (Q11): the name is checked here
     multistep = _solver(prepare_solver_params(**params))
     step_cache_config(model_config)         # (model_config step_cache_thresh / step_cache_coefficients: a bad value is a ValueError here)
+    # ---- FlowEdit (Q12): on where a source description is given; its numbers are checked here, and what it does not combine with
+    (source_prompt, source_prompt_2, source_prompt_embeds, source_pooled_prompt_embeds, source_guidance_scale, flowedit_n_max,
+     flowedit_n_avg) = prepare_flowedit_params(**params)
+    flowedit = _flowedit(source_prompt, source_prompt_embeds, source_pooled_prompt_embeds, source_guidance_scale, flowedit_n_max,
+                         flowedit_n_avg, num_inference_steps, prompt, prompt_embeds, pooled_prompt_embeds)
+    if flowedit is not None:
+        _flowedit_alone(do_true_cfg, brain_guidance_scale, want_apg, multistep, model_config, image, image_latents, strength)
     if any(a is not None for a in (image, image_latents, mask_image, latent_mask)) or strength != 1.0:
         n_prompts = _n_prompts(prompt, prompt_embeds)
         image_latents, inpaint_mask = _inpaint_source(
@@ -391,6 +491,11 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
         negative_prompt_embeds, negative_pooled_prompt_embeds, _ = self.encode_prompt(
             prompt=negative_prompt, prompt_2=negative_prompt_2, prompt_embeds=negative_prompt_embeds,
             pooled_prompt_embeds=negative_pooled_prompt_embeds, device=device, num_images_per_prompt=num_images_per_prompt,
+            max_sequence_length=max_sequence_length, lora_scale=lora_scale)
+    if flowedit is not None:
+        source_prompt_embeds, source_pooled_prompt_embeds, _ = self.encode_prompt(
+            prompt=source_prompt, prompt_2=source_prompt_2, prompt_embeds=source_prompt_embeds,
+            pooled_prompt_embeds=source_pooled_prompt_embeds, device=device, num_images_per_prompt=num_images_per_prompt,
             max_sequence_length=max_sequence_length, lora_scale=lora_scale)
     text_prompt_embeds, text_pooled_prompt_embeds = prompt_embeds, pooled_prompt_embeds      # (branch T of brain guidance: the text alone)
 
@@ -457,10 +562,26 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             negative_pooled_prompt_embeds = negative_pooled_prompt_embeds[:1].expand(pooled_prompt_embeds.shape[0], -1)
         _fits_positive("negative_prompt_embeds", negative_prompt_embeds, prompt_embeds)
         _fits_positive("negative_pooled_prompt_embeds", negative_pooled_prompt_embeds, pooled_prompt_embeds)
-    n_branches = 1 + do_brain_cfg + do_true_cfg
+    # ---- FlowEdit (Q12): the source branch is the second part of that ONE batch, [target; source]. The target is the embeddings as the
+    # brain section left them (branch F); the source embeddings are used as given, for the reason the negative ones are. Both get one row
+    # per image, so that the parts are [B·n] each.
+    if flowedit is not None:
+        rows = batch_size * num_images_per_prompt
+        for name, t in (("prompt_embeds", prompt_embeds), ("pooled_prompt_embeds", pooled_prompt_embeds),
+                        ("source_prompt_embeds", source_prompt_embeds), ("source_pooled_prompt_embeds", source_pooled_prompt_embeds)):
+            if t.shape[0] not in (1, rows):
+                raise ValueError(f"source_prompt (FlowEdit): `{name}` has batch {t.shape[0]} for {rows} image(s): one row, or one per image")
+        prompt_embeds, source_prompt_embeds = (t if t.shape[0] == rows else t[:1].expand(rows, -1, -1)
+                                               for t in (prompt_embeds, source_prompt_embeds))
+        pooled_prompt_embeds, source_pooled_prompt_embeds = (t if t.shape[0] == rows else t[:1].expand(rows, -1)
+                                                             for t in (pooled_prompt_embeds, source_pooled_prompt_embeds))
+        _fits_positive("source_prompt_embeds", source_prompt_embeds, prompt_embeds)
+        _fits_positive("source_pooled_prompt_embeds", source_pooled_prompt_embeds, pooled_prompt_embeds)
+    n_branches = 1 + do_brain_cfg + do_true_cfg + (flowedit is not None)
     if n_branches > 1:
         others = ([(text_prompt_embeds, text_pooled_prompt_embeds)] if do_brain_cfg else []) + \
-                 ([(negative_prompt_embeds, negative_pooled_prompt_embeds)] if do_true_cfg else [])
+                 ([(negative_prompt_embeds, negative_pooled_prompt_embeds)] if do_true_cfg else []) + \
+                 ([(source_prompt_embeds, source_pooled_prompt_embeds)] if flowedit is not None else [])
         prompt_embeds = torch.cat([prompt_embeds] + [e.to(prompt_embeds.dtype) for e, _ in others])
         pooled_prompt_embeds = torch.cat([pooled_prompt_embeds] + [p.to(pooled_prompt_embeds.dtype) for _, p in others])
 
@@ -493,13 +614,23 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas, mu=mu)
     n_schedule = num_inference_steps
     num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
-    if image_latents is not None:
+    flowedit_state = flowedit_begin = None
+    if flowedit is not None:
+        # (Q12) the trajectory is the last n_max steps of the schedule, from the source itself: `latents` (the caller's, or the draw) is the
+        # first noise, the edit state Z = X is what the loop carries, and the mask belongs to the state (no blend: kept tokens never move)
+        flowedit_noise = [latents.contiguous()]
+        flowedit_begin = n_schedule - flowedit[0]
+        timesteps, num_inference_steps, th_left = self.get_timesteps_from(flowedit_begin, device)
+        flowedit_state = FlowEditState(image_latents, inpaint_mask, flowedit[1])
+        latents = flowedit_state.Z
+        num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
+    elif image_latents is not None:
         # the trajectory starts at sigma[t_start] from the source noised to that level; `latents` (the caller's, or the draw) is the noise
         noise = latents.contiguous()
         timesteps, num_inference_steps, th_left = self.get_timesteps(n_schedule, strength, device)
         latents = self.scheduler.scale_noise(image_latents, n_schedule - num_inference_steps, noise)
         num_warmup_steps = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
-    step_kwargs = {} if inpaint_mask is None else {"inpaint": (image_latents, noise, inpaint_mask)}
+    step_kwargs = {} if inpaint_mask is None or flowedit is not None else {"inpaint": (image_latents, noise, inpaint_mask)}
     n_images = latents.shape[0]
     apg_state = multistep_state = None
     if multistep:
@@ -521,7 +652,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             # place of lx_euler_step_cfg / lx_euler_step_cfg3. With all three keywords at their defaults the call is not routed here.
             apg_state = ApgState(*want_apg, tuple(latents.shape), len(timesteps), device)
             step_kwargs["apg"] = apg_state
-        latents = torch.cat([latents] * n_branches)
+        if flowedit is None:
+            latents = torch.cat([latents] * n_branches)      # (FlowEdit's batch is formed per step, from Z and fresh noise: `latents` stays Z)
         if use_condition:
             condition_latents = condition_latents.repeat(n_branches * n_images // condition_latents.shape[0], 1, 1)
         user_mask = (self.joint_attention_kwargs or {}).get("attention_mask")
@@ -531,6 +663,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     guidance = None
     if self.transformer.config.guidance_embeds:
         guidance = torch.full((latents.shape[0],), float(guidance_scale), device=device, dtype=torch.float32)
+    if flowedit is not None:
+        guidance = _flowedit_guidance(guidance, n_images, source_guidance_scale)
     prompt_embeds = prompt_embeds.contiguous()
     pooled_prompt_embeds = pooled_prompt_embeds.contiguous()
 
@@ -555,9 +689,38 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
             apg_state.zero()                  # (empty momentum: the fp16 fallback's second pass starts as a fresh call does)
         if multistep_state is not None:
             multistep_state.zero()            # (no history: the same)
+        if flowedit_state is not None:
+            flowedit_state.zero()             # (Z = X again; the noises are NOT replayed: the second pass draws on from the generator)
+            latents = flowedit_state.Z
         with adapter_weight_tiles(engine, n_branches), self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
+                    continue
+                if flowedit_state is not None:
+                    # (Q12) n_avg noises, the inputs of all their forwards from the same Z, then per forward one launch that updates Z
+                    noises = [flowedit_noise.pop() if flowedit_noise else
+                              self.prepare_latents(n_images, num_channels_latents, height, width, torch.float32, device, generator, None)[0]
+                              for _ in range(flowedit_state.n_avg)]
+                    batches = self.scheduler.flowedit_inputs(flowedit_state, noises)
+                    timestep = t.expand(batches.shape[1]).to(batches.dtype)
+                    for k in range(flowedit_state.n_avg):
+                        noise_pred = tranformer_forward(
+                            self.transformer, model_config=model_config,
+                            condition_latents=condition_latents if use_condition else None,
+                            condition_ids=condition_ids if use_condition else None,
+                            condition_type_ids=condition_type_ids if use_condition else None,
+                            hidden_states=batches[k], timestep=timestep / 1000, guidance=guidance, pooled_projections=pooled_prompt_embeds,
+                            encoder_hidden_states=prompt_embeds, txt_ids=text_ids, img_ids=latent_image_ids,
+                            joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False, lx_schedule=(i, sched_ts))[0]
+                        latents = self.scheduler.step(noise_pred, t, batches[k], return_dict=False, flowedit=flowedit_state)[0]
+                    if callback_on_step_end is not None:
+                        scope = dict(locals())
+                        callback_outputs = callback_on_step_end(self, i, t, {k: scope[k] for k in callback_on_step_end_tensor_inputs})
+                        given = callback_outputs.pop("latents", latents)
+                        if given is not latents:                            # (its latents become the edit state)
+                            flowedit_state.Z.copy_(given)
+                        prompt_embeds = callback_outputs.pop("prompt_embeds", prompt_embeds)
+                    progress_bar.update()
                     continue
                 timestep = t.expand(latents.shape[0]).to(latents.dtype)
                 noise_pred = tranformer_forward(
@@ -609,7 +772,9 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
                 warnings.warn(what + "; recomputing this image with bf16 operands", RuntimeWarning, stacklevel=2)
                 pipeline.transformer.invalidate_conditioning()
                 timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, n_schedule, device, None, sigmas, mu=mu)      # (step index back to 0)
-                if image_latents is not None:                 # (and on to t_start again: the same start latents, the same blend)
+                if flowedit_state is not None:                # (Q12: the begin index again; denoise puts Z = X and draws on from the generator)
+                    timesteps, num_inference_steps, _ = self.get_timesteps_from(flowedit_begin, device)
+                elif image_latents is not None:               # (and on to t_start again: the same start latents, the same blend)
                     timesteps, num_inference_steps, _ = self.get_timesteps(n_schedule, strength, device)
                 latents = denoise(start_latents, prompt_embeds, dict(model_config or {}, operands="bf16"))
                 operands_used = "bf16 (fp16 overflow fallback)"
@@ -644,4 +809,8 @@ def generate(model, pipeline, conditions: List[Condition] = None, config_path: s
     return FluxPipelineOutput(images=image, lx_operands=operands_used, lx_step_cache=step_cache_report,
                               lx_apg=None if apg_state is None else apg_state.sums,
                               lx_solver=None if multistep_state is None else {"solver": "dpmpp_2m",
-                                                                              "coefficients": list(multistep_state.coefficients)})
+                                                                              "coefficients": list(multistep_state.coefficients)},
+                              lx_flowedit=None if flowedit_state is None else {
+                                  "n_max": flowedit[0], "n_avg": flowedit[1], "begin_index": flowedit_begin,
+                                  "sigmas": [s for _, s, _ in flowedit_state.taken], "coefs": [c for _, _, c in flowedit_state.taken],
+                                  "guidance_scale": float(guidance_scale), "source_guidance_scale": float(source_guidance_scale)})

@@ -2,7 +2,8 @@
 (src/flux/generate.py:72-394), for MI355X.  Restated from diffusers==0.31.0 (train/requirements.txt:1): latent packing,
 latent image ids, calculate_shift, FlowMatchEulerDiscreteScheduler.  The Euler update runs in HIP (lx_euler_step).
 Beyond what the reference calls, from diffusers' FluxImg2ImgPipeline / FluxInpaintPipeline: scale_noise, set_begin_index, get_timesteps,
-the packed latent mask (pack_mask) and the per-step blend (lx_scale_noise, lx_euler_step_blend).
+the packed latent mask (pack_mask) and the per-step blend (lx_scale_noise, lx_euler_step_blend). Beyond diffusers: the guided, projected
+and second-order steps, and FlowEdit's two scheduler functions (flowedit_inputs, step(flowedit=); lx_flowedit_inputs, lx_flowedit_step).
 
 Text encoders (T5/CLIP) and the VAE are outside the denoise hot path ("next"): pass `prompt_embeds`,
 `pooled_prompt_embeds` and `output_type="latent"`, or plug callables in via `text_encoder=` / `vae=`.
@@ -65,6 +66,45 @@ class MultistepState:
         self.D.zero_()
         self.have = False
         self.coefficients = []
+
+
+class FlowEditState:
+    """What FlowEdit carries through the steps of one call (FlowMatchEulerDiscreteScheduler.flowedit_inputs / step(flowedit=); generate's
+    source_prompt): the source latents X and the edit state Z (fp32, contiguous, one part's shape [B·n, ...], on X's device; Z starts as
+    X), the mask (X's shape; 1 edit, 0 keep) or None, n_avg, the inputs of a step's n_avg forwards ([n_avg, 2·B·n, ...]: row k is
+    [target; source] of the k-th forward), how many of them have been applied (`pending` counts down from n_avg to 0), and the record of
+    the steps taken: (step index, sigma, coef) per forward, host floats holding fp32 values. zero() puts Z = X again and empties the
+    record. The analogue of MultistepState."""
+
+    def __init__(self, X: torch.Tensor, mask: Optional[torch.Tensor] = None, n_avg: int = 1):
+        if not isinstance(X, torch.Tensor) or X.dim() < 1 or X.shape[0] == 0:
+            raise ValueError("FlowEditState: X is the packed source latents, a tensor [B, ...]")
+        if isinstance(n_avg, bool) or not isinstance(n_avg, (int, np.integer)) or int(n_avg) < 1:
+            raise ValueError(f"FlowEditState: n_avg must be an int >= 1, got {n_avg!r}")
+        self.X = X.to(torch.float32).contiguous()
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(self.X.shape) or mask.device != self.X.device:
+                raise ValueError(f"FlowEditState: the mask must have X's shape {tuple(self.X.shape)} on its device, got "
+                                 f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+            mask = mask.to(torch.float32).contiguous()
+        self.mask, self.n_avg = mask, int(n_avg)
+        self.Z = self.X.clone()
+        self.inputs = torch.empty((self.n_avg, 2 * self.X.shape[0]) + tuple(self.X.shape[1:]), dtype=torch.float32, device=self.X.device)
+        self.pending = 0
+        self.taken: List[tuple] = []
+
+    def zero(self):
+        self.Z.copy_(self.X)
+        self.pending = 0
+        self.taken = []
+
+
+def flowedit_coefficient(sig_host, i: int, n_avg: int = 1) -> float:
+    """The coefficient of one forward's update of FlowEdit's step i on the schedule `sig_host` (its fp32 sigmas, the final 0 included):
+    (s_{i+1} - s_i) / n_avg, the difference formed in fp32 as step() forms it, the quotient in float64 and rounded once to fp32; a Python
+    float. Host only."""
+    ds32 = np.float32(sig_host[i + 1]) - np.float32(sig_host[i])
+    return float(np.float32(np.float64(ds32) / n_avg))
 
 
 def multistep_coefficient(sig_host, i: int, begin: int = 0) -> float:
@@ -144,8 +184,58 @@ class FlowMatchEulerDiscreteScheduler:
         sigma = float(self._sig_host[self._sigma_index(sigma_index_or_timestep)])
         return ops.scale_noise(sample.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), sigma)
 
+    def flowedit_inputs(self, state: "FlowEditState", noises) -> torch.Tensor:
+        """The inputs of the n_avg forwards of FlowEdit's step at the current step index (lx_flowedit_inputs, one launch per forward), all
+        formed from the same Z before any update of this step: for the k-th noise N_k (X's shape, fp32), row k of state.inputs becomes
+        [Z + (S_k - X); S_k] with S_k = scale_noise(X, sigma_i, N_k). Returns state.inputs, [n_avg, 2·B·n, ...]; step(flowedit=state) then
+        takes the forwards' outputs one by one, in this order. A mismatch is a ValueError before any launch."""
+        if self.sigmas is None:
+            raise ValueError("flowedit_inputs: call set_timesteps first")
+        if not isinstance(state, FlowEditState):
+            raise ValueError(f"flowedit_inputs: state must be a FlowEditState, got {type(state).__name__}")
+        i = self._step_index
+        if not 0 <= i < len(self.timesteps_host):
+            raise ValueError(f"flowedit_inputs: step index {i} is past the schedule of {len(self.timesteps_host)} steps")
+        if state.pending:
+            raise ValueError(f"flowedit_inputs: {state.pending} forward(s) of the previous inputs have not been applied with step(flowedit=)")
+        noises = list(noises)
+        if len(noises) != state.n_avg:
+            raise ValueError(f"flowedit_inputs: {len(noises)} noise tensor(s) for n_avg = {state.n_avg}")
+        for k, nz in enumerate(noises):
+            if not isinstance(nz, torch.Tensor) or tuple(nz.shape) != tuple(state.X.shape) or nz.device != state.X.device:
+                raise ValueError(f"flowedit_inputs: noise {k} must have the source latents' shape {tuple(state.X.shape)} on their device, got "
+                                 f"{tuple(nz.shape) if isinstance(nz, torch.Tensor) else type(nz).__name__}")
+        if tuple(state.Z.shape) != tuple(state.X.shape) or state.Z.dtype != torch.float32 or not state.Z.is_contiguous():
+            raise ValueError(f"flowedit_inputs: the edit state Z {tuple(state.Z.shape)} must be fp32, contiguous and of X's shape")
+        sigma = float(self._sig_host[i])
+        for k, nz in enumerate(noises):
+            ops.flowedit_inputs(state.X, state.Z, nz.to(torch.float32).contiguous(), sigma, out=state.inputs[k])
+        state.pending = state.n_avg
+        return state.inputs
+
+    def _flowedit_step(self, state: "FlowEditState", model_output: torch.Tensor):
+        """step(flowedit=state): one forward's update, Z += mask * coef * (Vt - Vs) (lx_flowedit_step), coef = flowedit_coefficient(...);
+        the step index advances after the n_avg-th."""
+        if not isinstance(state, FlowEditState):
+            raise ValueError(f"step(flowedit=...): expected a FlowEditState, got {type(state).__name__}")
+        if not state.pending:
+            raise ValueError("step(flowedit=...): no inputs are pending; call flowedit_inputs(state, noises) for this step first")
+        i = self._step_index
+        want = (2 * state.X.shape[0],) + tuple(state.X.shape[1:])
+        if tuple(model_output.shape) != want or model_output.device != state.Z.device:
+            raise ValueError(f"step(flowedit=...): model_output {tuple(model_output.shape)} must be [target; source] of shape {want} on the "
+                             "state's device")
+        v = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
+        coef = flowedit_coefficient(self._sig_host, i, state.n_avg)
+        ops.flowedit_step(state.Z, v.contiguous(), coef, state.mask)
+        state.taken.append((i, float(self._sig_host[i]), coef))
+        state.pending -= 1
+        if not state.pending:
+            self._step_index += 1
+        return (state.Z,)
+
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, inpaint=None, true_cfg_scale=None,
-             brain_guidance_scale=None, apg=None, multistep=None):
+             brain_guidance_scale=None, apg=None, multistep=None, flowedit=None):
         """prev = sample(fp32) + (sigma_next - sigma) * model_output, cast to model_output.dtype (diffusers semantics).
         inpaint = (image_latents, noise, mask), fp32 contiguous in sample's shape: prev is then blended with the source noised to the next
         level, mask * prev + (1 - mask) * scale_noise(image_latents, sigma_next, noise), in the same launch (lx_euler_step_blend).
@@ -163,7 +253,16 @@ class FlowMatchEulerDiscreteScheduler:
         multistep = a MultistepState made for one part's shape (generate's solver="dpmpp_2m"): the step is DPM-Solver++(2M), the same step
         plus c * (D - D_prev) with D = sample - sigma * velocity the denoised prediction along whatever velocity the step runs (guided,
         projected under apg) and c = multistep_coefficient(...), 0 on the state's first step; one launch of lx_dpmpp2m_step, or of
-        lx_dpmpp2m_step_apg with apg, in place of the Euler entries. The state keeps D and records c. Without it nothing changes."""
+        lx_dpmpp2m_step_apg with apg, in place of the Euler entries. The state keeps D and records c. Without it nothing changes.
+        flowedit = a FlowEditState whose inputs flowedit_inputs() formed for this step (generate's source_prompt): model_output is one
+        forward's [target; source] velocities, `sample` is not read, and the edit state gets Z += mask * coef * (Vt - Vs) in one launch
+        of lx_flowedit_step, coef = (sigma_next - sigma) / n_avg; the step index advances after the n_avg-th forward. Returns (Z,), the
+        state's own fp32 buffer. With none of the other keywords: FlowEdit's velocity is the difference of its two branches."""
+        if flowedit is not None:
+            if inpaint is not None or true_cfg_scale is not None or brain_guidance_scale is not None or apg is not None or multistep is not None:
+                raise ValueError("step(flowedit=...): FlowEdit steps along the difference of its two branches; inpaint, true_cfg_scale, "
+                                 "brain_guidance_scale, apg and multistep do not combine with it (its mask belongs to the state)")
+            return self._flowedit_step(flowedit, model_output)
         if apg is not None and brain_guidance_scale is None and true_cfg_scale is None:
             raise ValueError("step(apg=...): adaptive projected guidance acts on a guidance update; pass true_cfg_scale and/or "
                              "brain_guidance_scale with it")
@@ -456,9 +555,22 @@ class LxFluxPipeline:
         if num_inference_steps - t_start < 1:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
                              f"{num_inference_steps - t_start} which is < 1 and not appropriate for this pipeline.")
+        timesteps, _, timesteps_host = self.get_timesteps_from(t_start)
+        return timesteps, num_inference_steps - t_start, timesteps_host
+
+    def get_timesteps_from(self, t_start: int, device=None):
+        """get_timesteps with the start given as a step of the schedule, not as a strength (FlowEdit begins at T - n_max): after the
+        scheduler's set_timesteps, returns (timesteps[t_start:], T - t_start, timesteps_host[t_start:]) and sets the scheduler's begin index
+        to t_start. Anything but an int in [0, T) is a ValueError."""
         sch = self.scheduler
+        if sch.timesteps is None:
+            raise ValueError("get_timesteps_from: call the scheduler's set_timesteps first")
+        total = len(sch.timesteps_host) // sch.order
+        if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 0 <= int(t_start) < total:
+            raise ValueError(f"get_timesteps_from({t_start!r}): the start must be an int in [0, {total})")
+        t_start = int(t_start)
         sch.set_begin_index(t_start * sch.order)
-        return sch.timesteps[t_start * sch.order:], num_inference_steps - t_start, sch.timesteps_host[t_start * sch.order:]
+        return sch.timesteps[t_start * sch.order:], total - t_start, sch.timesteps_host[t_start * sch.order:]
 
     @staticmethod
     def pack_mask(mask, batch, height, width):

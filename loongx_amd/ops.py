@@ -738,6 +738,39 @@ def dpmpp2m_step_apg(x: torch.Tensor, v: torch.Tensor, sigma: float, dsigma: flo
                                   n // n_images, _stream()), "lx_dpmpp2m_step_apg")
 
 
+def flowedit_inputs(x_src: torch.Tensor, z_fe: torch.Tensor, noise: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inputs of one FlowEdit forward (lx_flowedit_inputs): out[1] = the source x_src noised to sigma (scale_noise's bits), out[0] =
+    z_fe + (out[1] - x_src). x_src, z_fe and noise are fp32, contiguous, of one shape; out is fp32 contiguous with twice their element
+    count, [target; source], allocated as [2, *shape] when not given."""
+    for t, name in ((x_src, "x_src"), (z_fe, "z_fe"), (noise, "noise")):
+        _req(t, torch.float32, name)
+    out = torch.empty((2,) + tuple(x_src.shape), dtype=torch.float32, device=x_src.device) if out is None else out
+    _req(out, torch.float32, "out")
+    n = x_src.numel()
+    assert z_fe.numel() == n and noise.numel() == n and out.numel() == 2 * n, "flowedit_inputs: x_src, z_fe and noise hold n elements, out 2n"
+    assert all(t.is_contiguous() for t in (x_src, z_fe, noise, out)), "flowedit_inputs: contiguous operands"
+    check(lib.lx_flowedit_inputs(out.data_ptr(), x_src.data_ptr(), z_fe.data_ptr(), noise.data_ptr(), float(sigma), n, _stream()),
+          "lx_flowedit_inputs")
+    return out
+
+
+def flowedit_step(z_fe: torch.Tensor, v: torch.Tensor, coef: float, m: Optional[torch.Tensor] = None) -> None:
+    """FlowEdit's update after one forward, in place (lx_flowedit_step): z_fe += coef * m * (v[:n] - v[n:]) with v = [target; source], fp32
+    or bf16, of twice z_fe's element count; m (fp32, z_fe's element count; None: no mask) is 1 where the edit acts and 0 where the element
+    keeps its bits. All contiguous; nothing is synchronised."""
+    _req(z_fe, torch.float32, "z_fe")
+    if v.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"v: expected float32 or bfloat16, got {v.dtype}")
+    n = z_fe.numel()
+    assert v.numel() == 2 * n, "flowedit_step: v holds two parts of z_fe's element count"
+    if m is not None:
+        _req(m, torch.float32, "m")
+        assert m.numel() == n, "flowedit_step: m has z_fe's element count"
+    assert all(t.is_contiguous() for t in (z_fe, v, m) if t is not None), "flowedit_step: contiguous operands"
+    check(lib.lx_flowedit_step(z_fe.data_ptr(), v.data_ptr(), int(v.dtype == torch.bfloat16), float(coef), _p(m), n, _stream()),
+          "lx_flowedit_step")
+
+
 def convert(dst: torch.Tensor, src: torch.Tensor) -> None:
     assert dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()
     fmt = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
