@@ -106,6 +106,59 @@ enum {
                             LX_OPERANDS_FP8 / k_segs >= 2 / LX_EPI_SPLIT_BF16. model_config["operands"] = "fp16" / dtype=torch.float16. */
 };
 
+/* ------------------------------------------------------------------------------------------------
+ * Store contract: what every 16- and 8-bit store makes of an fp32 value x on its last step. One row per producer and format;
+ * tests/test_store_formats_gpu.py holds the same table as a literal (CONTRACT), asserts it bit for bit on an MI355X and prints it
+ * under -s. "pair" is the split-bf16 format: hi = bf16(x), lo = bf16(x - hi).
+ *
+ *   rne            round to nearest, ties to even; the target format's subnormals are produced (bf16: 127, fp16: 1023, e4m3: 7 of them),
+ *                  fp32 subnormal inputs are not flushed
+ *   inf / max      +-inf / +-the largest finite value (65504, 448), of x's sign
+ *   nan            some NaN code
+ *   -max           the NEGATIVE largest finite value, whatever the NaN's sign: what the clamp makes of a NaN
+ *   -max; s: +max  ... of a quiet NaN; a SIGNALLING NaN (quiet bit clear, either sign) gives the POSITIVE largest value. Only lx_convert
+ *                  can meet one: everywhere else arithmetic (a scale, a bias, a normalisation) has quieted the NaN before the clamp
+ *   (a, b)         the hi and lo words of a pair
+ *   none           no contract
+ *   -              cannot occur / does not apply
+ *
+ *   producer                 format rounding beyond range  +-inf       NaN            counted in f16_ovf
+ *   lx_convert               bf16   rne      inf           inf         nan            -
+ *   lx_convert               f16    rne      max           max         -max; s: +max  no counter
+ *   lx_convert_f16           f16    rne      max           max         nan            beyond, inf
+ *   lx_convert_fp8           e4m3   rne      max           max         -max           -
+ *   lx_split_bf16            pair   rne      (inf, -inf)   (inf, nan)  (nan, nan)     -
+ *   lx_gemm_bf16 epilogue    bf16   rne      inf           inf         nan            -
+ *   lx_gemm_bf16 epilogue    f16    rne      max           max         -max           beyond, inf; NaN not
+ *   lx_gemm_bf16 epilogue    e4m3   rne      max           max         -max           -
+ *   lx_gemm_bf16 epilogue    pair   rne      (inf, -inf)   (inf, nan)  (nan, nan)     -
+ *   lx_ln_modulate*          bf16   rne      inf           inf         nan            -
+ *   lx_ln_modulate*          f16    rne      max           max         -max           beyond, inf; NaN not
+ *   lx_ln_modulate*          e4m3   rne      max           max         -max           -
+ *   lx_ln_modulate*          pair   rne      (inf, -inf)   (inf, nan)  (nan, nan)     -
+ *   lx_groupnorm_silu*       bf16   rne      inf           inf         nan            -
+ *   lx_groupnorm_silu*       f16    rne      max           max         -max           beyond, inf; NaN not
+ *   lx_groupnorm_silu*       pair   rne      (inf, -inf)   (inf, nan)  (nan, nan)     -
+ *   lx_attn_fwd* O           bf16   rne      -             none        none           -
+ *   lx_attn_fwd* O           f16    rne      max           none        none           beyond
+ *
+ * Specified before this table and held as such (a device that differs is a bug): rne everywhere, subnormals honoured, bf16 overflow to
+ * +-inf, fp16 stores never inf -- saturated to +-65504 and counted where a counter exists (|x| > 65504 BEFORE rounding: 65519.99 rounds
+ * to 65504 and still counts) --, e4m3 saturated to +-448, lx_convert_f16 keeps NaN. The rest records what the device does:
+ *   - a NaN that reaches a saturating fp16 store other than lx_convert_f16 becomes -65504 and is NOT counted (the clamp's median
+ *     drops it, and so does the maximum the counter is fed from): f16_overflow = "raise" never sees it; the fp32 residual stream does;
+ *   - a NaN that reaches an e4m3 store becomes -448;
+ *   - the pair of +-inf is (+-inf, NaN), the pair of a finite x that bf16 rounds to +-inf is (+-inf, -+inf): hi + lo is a NaN in both;
+ *   - with k_segs = 3 an inf in A meets the zero lo image of an exactly representable W: inf * 0, the row is NaN, not inf.
+ * Where a value is computed before it is stored (LayerNorm, GroupNorm) the classes are those of the value computed: a NaN or +-inf among
+ * the inputs of a row / group makes its statistics non-numbers (GroupNorm: x = +inf gives variance inf - inf, which max(variance, 0)
+ * turns into 0, so the rest of the group is -inf * gamma and the element itself NaN).
+ * lx_attn_fwd* has NO contract for NaN or +-inf operands: attn.hip and attn4.hip are built with -fno-honor-nans (the online softmax's
+ * row maxima would otherwise pay a quieting instruction per operand) and mask with -1e30, never with NaN or inf. Finite operands only:
+ * O is probabilities times V, so no finite V reaches past bf16's range; a V column of +-7e4 comes out within an ulp in bf16 and as exactly
+ * +-65504, counted, under LX_ATTN_O_F16; one of +-3e4 stays uncounted (8-wave max-tracking and bounded, 4-wave, masked and e4m3 kernels).
+ * ------------------------------------------------------------------------------------------------ */
+
 typedef struct lx_gemm_desc {
   const void* A;        /* [M,K] bf16, lda */
   const void* W;        /* [N,K] bf16, ldw (nn.Linear.weight layout) */
